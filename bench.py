@@ -8,8 +8,13 @@ problems already resident in HBM.
   --gpus N>1: BASELINE configs[2]: ONE batch of 32768 robots sharded contiguously over the N ranks (16384 / 8192 / 4096
               per GPU at N = 2 / 4 / 8: strong scaling of config 3), no data-path collective; RCCL only gathers the
               counters.  --total-batch / --batch override either default (--batch = per GPU, weak scaling).
+A plain run sets up, warms up, times the K steps and prints the headline line (solver figures and roofline from the timed
+answers).  --full adds everything else the benchmark measures and checks, each outside the timed region: presolve
+accounting, rollout, transfers, the other BASELINE configs and the CPU baseline that re-checks the GPU answers.
+--dump-outputs DIR writes the answers of the last timed step as .npy files (dump_outputs).
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -221,6 +226,26 @@ def transfer_times(inp, out, dev, kern_ms):
                     "what a caller that keeps nothing resident would see; not `value`"}
 
 
+def dump_outputs(path, out, num_rows, lo, suffix, max_bytes):
+    """--dump-outputs: what plan_step_batch handed its caller in the last timed step, one DIR/<name><suffix>.npy per array:
+    U, X, theta, omega, obj, status, iters in float64 (the integers exactly), active unpacked to float32 0 / 1 per row in
+    canonical row order, and index = each written robot's index in the whole batch.  Beyond max_bytes a fixed, seeded
+    sample of robots is written (in batch order), so that two builds given the same arguments write the same robots."""
+    import lipmpc
+    h = {k: out[k].cpu().numpy() for k in ("U", "X", "theta", "omega", "obj", "status", "iters", "active")}
+    arrs = {k: h[k].astype(np.float64) for k in ("U", "X", "theta", "omega", "obj", "status", "iters")}
+    arrs["active"] = lipmpc.unpack_active(h["active"], num_rows).astype(np.float32)
+    B = h["U"].shape[0]
+    arrs["index"] = lo + np.arange(B, dtype=np.float64)
+    per_robot = sum(a[0].nbytes for a in arrs.values())
+    if B * per_robot > max_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(B, max_bytes // per_robot, replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -234,12 +259,20 @@ def main():
     ap.add_argument("--finish-rounds", type=int, default=0, help="lipmpc_params.finish_rounds (0 = library default)")
     ap.add_argument("--fields", type=int, default=0,
                     help="distinct obstacle fields (0 = one per robot); fewer: fields are reused by several robots (profiling runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures and checks (never `value`): presolve "
+                         "accounting, rollout, transfers, the other BASELINE configs and the CPU baseline with its parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the compact extras (BASELINE configs 3 on one GPU, 4 and 5: a few seconds; never `value`)")
+                    help="with --full: skip the compact extras (BASELINE configs 3 on one GPU, 4 and 5: a few seconds)")
     ap.add_argument("--all-configs", action="store_true",
-                    help="extras in full: + config 5 through HBM rings and in closed loop (fleet of 4096 robots, 30 samples)")
+                    help="implies --full; extras in full: + config 5 through HBM rings and in closed loop (fleet of 4096 robots, 30 samples)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the answers of the last timed step as DIR/<name>.npy (float64 / float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full or args.all_configs
 
     what, arg = plan_launch(args.gpus, os.environ)
     if what == "error":
@@ -307,7 +340,6 @@ def main():
     scheduled = B > resident and os.environ.get("LIPMPC_BENCH_SCHEDULE") == "1"
     if scheduled:
         solver.set_schedule(B)
-    walker = lipmpc.BatchedLipMpc(lipmpc.LipMpcParams(N=N, n_obs_max=n_obs, v_max=5, flags=lipmpc.FLAG_INTERIOR), local_rank)
 
     # ---- synthetic inputs (seeded per rank), placed in HBM before the timed region -------------
     inp = make_inputs(lipmpc, synth, B, N, n_obs, lo, rank, dev, local_rank, n_fields=args.fields or None, walk_steps=30 if N <= 8 else 20)
@@ -352,17 +384,21 @@ def main():
     elapsed = time.perf_counter() - t0
 
     kern_ms = ev0.elapsed_time(ev1) / args.steps
-    order_detail = None
-    if scheduled:
-        order_detail = launch_order_figures(solver, args.steps, B, (state, foot), (state_b, foot_b), goal, obs_xy, obs_nv, delta, out, dev)
-        order_detail["one_step_stale_order"] = B * args.steps / elapsed
-    # the answers of the batch itself, with the certificate margins the CPU check filters on (outside the timed region:
-    # the identification margin costs logarithms)
-    out = solver.plan_step_batch(state, goal, foot, obs_xy, obs_nv, delta, with_diag=True, with_working=True, with_c_eta=n_obs > 0)
-    torch.cuda.synchronize(dev)
+    # the solver figures of the line are those of the last timed step's answers
     status = out["status"].cpu().numpy()
     iters = out["iters"].cpu().numpy()
     n_ok = int(np.sum((status == 0) | (status == 4)))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, P.num_rows, lo, "" if world == 1 else f".rank{rank}", (60 << 20) // world)
+    order_detail = None
+    if scheduled and full:
+        order_detail = launch_order_figures(solver, args.steps, B, (state, foot), (state_b, foot_b), goal, obs_xy, obs_nv, delta, out, dev)
+        order_detail["one_step_stale_order"] = B * args.steps / elapsed
+    if full:
+        # the answers of the batch itself, with the certificate margins the CPU check filters on (outside the timed region:
+        # the identification margin costs logarithms)
+        out = solver.plan_step_batch(state, goal, foot, obs_xy, obs_nv, delta, with_diag=True, with_working=True, with_c_eta=n_obs > 0)
+        torch.cuda.synchronize(dev)
     # RCCL all-gather of {seconds, problems, solved}: the only collective, after the timed region
     t_max, total_B, total_ok, _ = sharding.gather_counters(elapsed, B, n_ok, device=None if rehearse else dev)
 
@@ -434,9 +470,9 @@ def main():
                                  "instruction counters of the same launch (profiles/), a utilisation figure, whereas "
                                  "frac prices the work a dense solver would do"},
         }
-        if world == 1 and n_obs > 0 and not (P.flags & (lipmpc.FLAG_INTERIOR | lipmpc.FLAG_NO_PRESOLVE)):
+        if full and world == 1 and n_obs > 0 and not (P.flags & (lipmpc.FLAG_INTERIOR | lipmpc.FLAG_NO_PRESOLVE)):
             res["roofline"].update(presolve_accounting(lipmpc, P, solver, inp, out, kern_ms, peak, args.steps, dev))
-        if world == 1:
+        if full and world == 1:
             res["rollout"] = rollout_throughput(lipmpc, walker, obs_xy, obs_nv, goal, delta, dev)
             rec = _traffic_record(f"rollout_N{N}_obs{n_obs}_B{B}_k40")
             if rec:      # builder's PMC passes over this very launch (tools/profile_round.sh rollout)
@@ -455,11 +491,11 @@ def main():
             warm_walker = lipmpc.BatchedLipMpc(lipmpc.LipMpcParams(N=N, n_obs_max=n_obs, v_max=5,
                                                                    flags=lipmpc.FLAG_INTERIOR | lipmpc.FLAG_WARM_START), local_rank)
             res["rollout_warm_start"] = rollout_throughput(lipmpc, warm_walker, obs_xy, obs_nv, goal, delta, dev)
-        if world == 1:
+        if full and world == 1:
             res["transfers"] = transfer_times(inp, out, dev, kern_ms)
-        if world == 1 and not args.no_other_configs:
+        if full and world == 1 and not args.no_other_configs:
             res["other_configs"] = other_configs(lipmpc, synth, dev, full=args.all_configs)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(P, state, goal, foot, obs_xy, obs_nv, delta, out)
         if real_stdout is not None:
             sys.stdout.flush()

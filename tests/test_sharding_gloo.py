@@ -180,3 +180,39 @@ def test_rccl_counter_gather_on_one_gpu():
     c = d["config"]["counters"]
     assert c["collective"] == "all_gather" and c["backend"] == "nccl" and c["device"].startswith("cuda") and c["world"] == 1
     assert d["solver"]["solved_frac"] > 0.95 and abs(d["value"] - 4096 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_the_timed_answers(tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline line without the --full extras, and --dump-outputs writes the
+    answers of the last timed step: float arrays of the batch's shapes whose statuses and iterations are the line's own
+    solver figures, under 64 MB in all."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LIPMPC_BENCH_REHEARSE", "LIPMPC_FORCE_DIST")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["unit"] == "solves/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4096 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert not {"cpu_baseline", "other_configs", "rollout", "transfers"} & set(d) and "frac_no_presolve" not in d["roofline"]
+    N, n_obs, B = 8, 10, 4096
+    shapes = {"U": (B, N, 2), "X": (B, N + 1, 4), "theta": (B, N + 1), "omega": (B, N), "obj": (B,), "status": (B,),
+              "iters": (B,), "active": (B, 9 * N + (N + 1) * n_obs), "index": (B,)}
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in shapes)
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64e6
+    a = {k: np.load(tmp_path / (k + ".npy")) for k in shapes}
+    for k, shape in shapes.items():
+        assert a[k].shape == shape and a[k].dtype in (np.float32, np.float64), (k, a[k].shape, a[k].dtype)
+    assert np.array_equal(a["index"], np.arange(B))
+    assert np.isin(a["active"], (0.0, 1.0)).all()
+    st, cnt = np.unique(a["status"], return_counts=True)
+    assert {str(int(s)): int(c) for s, c in zip(st, cnt)} == d["solver"]["status_hist"]
+    assert a["iters"].mean() == d["solver"]["mean_iters"] and int(a["iters"].max()) == d["solver"]["max_iters"]
+    assert np.isin(a["status"], (0, 4)).mean() > 0.95 and np.isfinite(a["U"][a["status"] == 0]).all()

@@ -6,9 +6,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 G=$R/gpurun_out
 bash $R/tools/profile_workload.sh r04_cfg5_scan cfg5 "lidar_" > $G/prof_r04_cfg5_scan.log 2>&1
 bash $R/tools/profile_workload.sh r04_cfg5_solve cfg5 "plan_step_kernel" > $G/prof_r04_cfg5_solve.log 2>&1
-python3 $R/bench.py > $G/r04_final_bench.json 2> $G/r04_final_bench.err
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $G/r04_final_bench_steps20.json 2> $G/r04_final_bench_steps20.err
-python3 $R/bench.py --no-cpu-baseline --all-configs > $G/r04_all_configs_bench.json 2> $G/r04_all_configs_bench.err
+python3 $R/bench.py --full > $G/r04_final_bench.json 2> $G/r04_final_bench.err
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $G/r04_final_bench_steps20.json 2> $G/r04_final_bench_steps20.err
+python3 $R/bench.py --full --no-cpu-baseline --all-configs > $G/r04_all_configs_bench.json 2> $G/r04_all_configs_bench.err
 mkdir -p $G/r04_dev_tools
 python3 $R/tools/lidar_order.py 2>&1 | grep -v amdgpu.ids > $G/r04_dev_tools/r04_lidar_order.txt
 bash $R/tools/lidar_timeline.sh cfg5 2>&1 | tail -1 > $G/r04_dev_tools/r04_lidar_timeline.txt

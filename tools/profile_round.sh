@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects the rocprofv3 evidence bench.py's numbers are judged against (run on the GPU box from the repo root):
-#   1. --kernel-trace --stats of the default bench command      -> <out>/kernel_stats.csv, bench line, launch durations
+#   1. --kernel-trace --stats of the bench command with --full  -> <out>/kernel_stats.csv, bench line, launch durations
 #   2. separate --pmc passes (never combined with trace domains other than --kernel-trace)
 #        FETCH_SIZE | WRITE_SIZE                                   HBM traffic (gfx950: FETCH_SIZE x 2, MI355X_MICROARCH.md)
 #        SQ_INSTS_VALU SQ_ACTIVE_INST_VALU | SQ_WAVE_CYCLES SQ_BUSY_CYCLES      issue / occupancy
@@ -16,7 +16,7 @@ EXTRA="$@"
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 $R/bench.py --no-cpu-baseline --no-other-configs $EXTRA > $O/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d prof_stats -- python3 $R/bench.py --full --no-cpu-baseline --no-other-configs $EXTRA > $O/bench_stats.log 2>&1
 find /tmp/prof_stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 python3 - "$O" <<'PY'
 import csv, glob, sys
@@ -37,7 +37,7 @@ for c in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_S
          "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_MFMA_MOPS_F64" \
          "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_WAIT_ANY" "SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_SMEM SQ_INSTS_VMEM_RD"; do
   rm -rf /tmp/prof_pmc
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/prof_pmc -- python3 $R/bench.py --no-cpu-baseline --no-other-configs --steps 10 --warmup 2 $EXTRA > $O/bench_pmc.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d prof_pmc -- python3 $R/bench.py --full --no-cpu-baseline --no-other-configs --steps 10 --warmup 2 $EXTRA > $O/bench_pmc.log 2>&1
   python3 - "$O" <<'PY'
 import csv, glob, sys, collections, os, re
 RX = re.compile(os.environ.get('KERNEL_RX', r'plan_step_kernel<.*true>'))
