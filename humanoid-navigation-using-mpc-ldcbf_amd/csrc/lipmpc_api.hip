@@ -1,4 +1,6 @@
 // lipmpc_api.hip — C ABI (include/lipmpc.h): handle, parameter checks, kernel dispatch, state advance.
+#include <type_traits>
+
 #include "lipmpc_kernel.hpp"
 
 using namespace lipmpc_dev;
@@ -14,12 +16,7 @@ __global__ void advance_kernel(long B, double ch, double sh_over_beta, double be
   if (st != LIPMPC_STATUS_SOLVED && st != LIPMPC_STATUS_UNCERTIFIED) return;
   double* x = state + b * 5;
   const double ux = U[b * N * 2 + 0], uy = U[b * N * 2 + 1];
-  const double px = x[0], vx = x[1], py = x[2], vy = x[3];
-  // A_l x + B_l u  (HumanoidMpc.py:34-48)
-  x[0] = ch * px + sh_over_beta * vx + (1.0 - ch) * ux;
-  x[1] = beta_sh * px + ch * vx - beta_sh * ux;
-  x[2] = ch * py + sh_over_beta * vy + (1.0 - ch) * uy;
-  x[3] = beta_sh * py + ch * vy - beta_sh * uy;
+  lip_advance(ch, sh_over_beta, beta_sh, ux, uy, x[0], x[1], x[2], x[3]);
   x[4] = theta[b * (N + 1) + 1];
   foot[b] = (int8_t)(-foot[b]);
 }
@@ -49,11 +46,7 @@ __global__ void fleet_update_kernel(long B, int k_max, double stop_obj, double c
   const double ux = U[b * N * 2 + 0], uy = U[b * N * 2 + 1];
   if (w) {
     last_obj[b] = obj[b];
-    const double px = x[0], vx = x[1], py = x[2], vy = x[3];
-    x[0] = ch * px + sh_over_beta * vx + (1.0 - ch) * ux;
-    x[1] = beta_sh * px + ch * vx - beta_sh * ux;
-    x[2] = ch * py + sh_over_beta * vy + (1.0 - ch) * uy;
-    x[3] = beta_sh * py + ch * vy - beta_sh * uy;
+    lip_advance(ch, sh_over_beta, beta_sh, ux, uy, x[0], x[1], x[2], x[3]);
     x[4] = theta[b * (N + 1) + 1];
     foot[b] = (int8_t)(-foot[b]);
     n_steps[b] += 1;
@@ -157,6 +150,36 @@ struct lipmpc_handle {
   bool have_streams;
 };
 
+// The instantiation table: f(G, NOBS_L, NVAR) as std::integral_constant arguments for the handle's (G, nobs_l, nvar), the last
+// row slot count of a list taking every larger nobs_l.  The objects that hold these instantiations are the INST_OBJS of the
+// Makefile: a triple added here needs its object there, and the reverse.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <int G, int NVAR, int NL, int... MORE, class F>
+static void dispatch_nl(int nobs_l, F& f) {
+  if constexpr (sizeof...(MORE) == 0) f(IntC<G>{}, IntC<NL>{}, IntC<NVAR>{});
+  else if (nobs_l == NL) f(IntC<G>{}, IntC<NL>{}, IntC<NVAR>{});
+  else dispatch_nl<G, NVAR, MORE...>(nobs_l, f);
+}
+template <class F>
+static void with_instantiation(const lipmpc_handle* h, F&& f) {
+  if (h->G == 16 && h->nvar == 8) dispatch_nl<16, 8, 0, 2, 5, 7>(h->nobs_l, f);
+  else if (h->G == 16) dispatch_nl<16, 16, 0, 2, 5, 7, 13, 25>(h->nobs_l, f);
+  else dispatch_nl<32, 32, 0, 2, 5, 7, 13, 25>(h->nobs_l, f);
+}
+
+// The solver body of split class `cls` (split_slots(cls) row slots per lane) over its list: the objects list_32_<slots>.o, the
+// LIST_NLS of the Makefile
+static_assert(split_slots(0) == 1 && split_slots(1) == 2 && split_slots(2) == 4 && split_slots(3) == 13 && split_slots(4) == 25,
+              "the Makefile's LIST_NLS builds the bodies of the classes");
+template <int C = 0>
+static void launch_class_body(int cls, const KArgs& k, long B, const int32_t* ws, const StepIO& io, int32_t* cost,
+                              hipStream_t stream) {
+  if constexpr (C + 1 < SPLIT_CLASSES) {
+    if (cls != C) return launch_class_body<C + 1>(cls, k, B, ws, io, cost, stream);
+  }
+  launch_solve_list<32, split_slots(C), 32>(k, B, C, ws, io, cost, stream);
+}
+
 extern "C" {
 
 int lipmpc_default_params(lipmpc_params* p) {
@@ -250,96 +273,62 @@ int lipmpc_set_workspace(lipmpc_handle* h, void* workspace, int64_t capacity) {
   return LIPMPC_OK;
 }
 
-#define LAUNCH(GG, NL, NV)                                                                                     \
-  launch_plan_step<GG, NL, NV>(h->k, (long)B, state, goal, first_foot, delta, obs_xy, obs_nv, U, X, theta, omega, obj, \
-                               status, iters, (unsigned long long*)active, (unsigned long long*)working, c_eta, diag, bounds, c_eta_in, sched, overflow, stream)
+// Split launch: classes -> lists -> one kernel per solver body, side by side.  The rare, long bodies go first on their own
+// streams (a few waves each, they must not queue behind 2048 short ones); the caller's stream takes the 1-slot body and
+// waits for the others.  A failure after the fork enqueues no further body, but every side stream that took the fork is still
+// joined back to the caller's stream (nothing of this launch outlives the caller's stream; a capture stays joined).
+static int split_step(lipmpc_handle* h, long B, const StepIO& io, int32_t* sched, hipStream_t stream) {
+  constexpr int GPW = WAVE / 32;
+  const unsigned blocks = (unsigned)((B + GPW - 1) / GPW);
+  int32_t* ws = h->ws;
+  int32_t* cost = sched ? sched + SCHED_ORDER + B : nullptr;
+  hipLaunchKernelGGL((classify_kernel<32>), dim3(blocks), dim3(WAVE), 0, stream, h->k, B, io.state, io.goal, io.delta, io.obs_xy,
+                     io.obs_nv, io.bounds, io.c_eta_in, ws);
+  if (hipGetLastError() != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(split_bin_kernel, dim3(1), dim3(BIN_THREADS), 0, stream, B, ws);
+  if (hipGetLastError() != hipSuccess) return LIPMPC_E_HIP;
+  const int top = split_class_of((h->p.n_obs_max + 1) / 2);
+  // Which body goes where: the waves of a kernel are placed in launch order and a kernel that starts first takes the free
+  // SIMDs first.  The 1-slot body has the most problems and the cheapest ones: it goes LAST, on a side stream (a side
+  // stream's kernel starts ~10 us after the caller's stream's: the fork event); the 2-slot body -- a third of the problems,
+  // dearer ones -- takes the caller's stream and with it the first pick of the SIMDs; the rare bodies with more slots start
+  // next to it.  (Measured at N = 16 / 50 obstacles, B = 4096: 1-slot body on the caller's stream 0.640 ms, this 0.6xx.)
+  if (hipEventRecord(h->fork_ev, stream) != hipSuccess) return LIPMPC_E_HIP;
+  const int on_main = top >= 1 ? 1 : 0;
+  int joined[SPLIT_CLASSES - 1], n_joined = 0;        // side streams whose join event is recorded
+  bool ok = true;
+  for (int c = top; c >= 0 && ok; --c) {
+    if (c == on_main) continue;
+    const int si = c < on_main ? c : c - 1;                                // four side streams for the four other classes
+    hipStream_t st = h->side[si];
+    if (hipStreamWaitEvent(st, h->fork_ev, 0) != hipSuccess) { ok = false; break; }
+    launch_class_body(c, h->k, B, ws, io, cost, st);
+    ok = hipGetLastError() == hipSuccess;
+    if (hipEventRecord(h->join_ev[si], st) == hipSuccess) joined[n_joined++] = si;
+    else ok = false;
+  }
+  if (ok) {
+    launch_class_body(on_main, h->k, B, ws, io, cost, stream);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  for (int i = 0; i < n_joined; ++i) ok = hipStreamWaitEvent(stream, h->join_ev[joined[i]], 0) == hipSuccess && ok;
+  return ok ? LIPMPC_OK : LIPMPC_E_HIP;
+}
 
-static int plan_step_impl(lipmpc_handle* h, int64_t B, const double* state, const double* goal,
-                          const int8_t* first_foot, const double* delta, const double* obs_xy,
-                          const int32_t* obs_nv, const double* c_eta_in, double* U, double* X, double* theta, double* omega,
-                          double* obj, int32_t* status, int32_t* iters, uint64_t* active, uint64_t* working, double* c_eta,
-                          double* diag, const double* bounds, const int32_t* overflow, void* hip_stream) {
+static int plan_step_impl(lipmpc_handle* h, int64_t B, const StepIO& io, void* hip_stream) {
   if (!h || B < 0) return LIPMPC_E_ARG;
   if (B == 0) return LIPMPC_OK;
-  if (!state || !goal || !first_foot || !U || !X || !theta || !omega || !obj || !status || !iters || !active)
+  if (!io.state || !io.goal || !io.first_foot || !io.U || !io.X || !io.theta || !io.omega || !io.obj || !io.status || !io.iters ||
+      !io.active)
     return LIPMPC_E_ARG;
-  if (h->p.n_obs_max > 0 && !c_eta_in && (!obs_xy || !obs_nv)) return LIPMPC_E_ARG;
+  if (h->p.n_obs_max > 0 && !io.c_eta_in && (!io.obs_xy || !io.obs_nv)) return LIPMPC_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return LIPMPC_E_HIP;
   hipStream_t stream = (hipStream_t)hip_stream;
   int32_t* sched = (h->sched && B <= h->sched_cap) ? h->sched : nullptr;
   if (h->ws && B <= h->ws_cap && B <= BIN_MAX_B && split_capable(h)) {
-    // Split launch: classes -> lists -> one kernel per solver body, side by side.  The rare, long bodies go first on their own
-    // streams (a few waves each, they must not queue behind 2048 short ones); the caller's stream takes the 1-slot body and
-    // waits for the others.
-    constexpr int GPW = WAVE / 32;
-    const unsigned blocks = (unsigned)((B + GPW - 1) / GPW);
-    int32_t* ws = h->ws;
-    int32_t* cost = sched ? sched + SCHED_ORDER + B : nullptr;
-    hipLaunchKernelGGL((classify_kernel<32>), dim3(blocks), dim3(WAVE), 0, stream, h->k, (long)B, state, goal, delta, obs_xy, obs_nv,
-                       bounds, c_eta_in, ws);
-    hipLaunchKernelGGL(split_bin_kernel, dim3(1), dim3(BIN_THREADS), 0, stream, (long)B, ws);
-    const int top = split_class_of((h->p.n_obs_max + 1) / 2);
-#define LIST(NL, CLS, ST)                                                                                                     \
-  launch_solve_list<32, NL, 32>(h->k, (long)B, CLS, ws, state, goal, first_foot, delta, obs_xy, obs_nv, U, X, theta, omega, obj, status, \
-                                iters, (unsigned long long*)active, (unsigned long long*)working, c_eta, diag, bounds, c_eta_in, cost,  \
-                                overflow, ST)
-    static_assert(split_slots(0) == 1 && split_slots(1) == 2 && split_slots(2) == 4 && split_slots(3) == 13 && split_slots(4) == 25,
-                  "the LIST() calls below name the bodies of the classes");
-    // Which body goes where: the waves of a kernel are placed in launch order and a kernel that starts first takes the free
-    // SIMDs first.  The 1-slot body has the most problems and the cheapest ones: it goes LAST, on a side stream (a side
-    // stream's kernel starts ~10 us after the caller's stream's: the fork event); the 2-slot body -- a third of the problems,
-    // dearer ones -- takes the caller's stream and with it the first pick of the SIMDs; the rare bodies with more slots start
-    // next to it.  (Measured at N = 16 / 50 obstacles, B = 4096: 1-slot body on the caller's stream 0.640 ms, this 0.6xx.)
-    if (hipEventRecord(h->fork_ev, stream) != hipSuccess) return LIPMPC_E_HIP;
-    const int on_main = top >= 1 ? 1 : 0;
-    for (int c = top; c >= 0; --c) {
-      if (c == on_main) continue;
-      const int si = c < on_main ? c : c - 1;                                // four side streams for the four other classes
-      hipStream_t st = h->side[si];
-      if (hipStreamWaitEvent(st, h->fork_ev, 0) != hipSuccess) return LIPMPC_E_HIP;
-      switch (c) {
-        case 4: LIST(25, 4, st); break;
-        case 3: LIST(13, 3, st); break;
-        case 2: LIST(4, 2, st); break;
-        case 1: LIST(2, 1, st); break;
-        default: LIST(1, 0, st); break;
-      }
-      if (hipEventRecord(h->join_ev[si], st) != hipSuccess) return LIPMPC_E_HIP;
-    }
-    if (on_main == 1) LIST(2, 1, stream); else LIST(1, 0, stream);
-    for (int c = top; c >= 0; --c) {
-      if (c == on_main) continue;
-      if (hipStreamWaitEvent(stream, h->join_ev[c < on_main ? c : c - 1], 0) != hipSuccess) return LIPMPC_E_HIP;
-    }
-#undef LIST
-    if (sched) hipLaunchKernelGGL(order_by_cost_kernel, dim3(1), dim3(1024), 0, stream, (long)B, sched);
-    return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
-  }
-  if (h->G == 16 && h->nvar == 8) {
-    switch (h->nobs_l) {
-      case 0: LAUNCH(16, 0, 8); break;
-      case 2: LAUNCH(16, 2, 8); break;
-      case 5: LAUNCH(16, 5, 8); break;
-      default: LAUNCH(16, 7, 8); break;
-    }
-  } else if (h->G == 16) {
-    switch (h->nobs_l) {
-      case 0: LAUNCH(16, 0, 16); break;
-      case 2: LAUNCH(16, 2, 16); break;
-      case 5: LAUNCH(16, 5, 16); break;
-      case 7: LAUNCH(16, 7, 16); break;
-      case 13: LAUNCH(16, 13, 16); break;
-      default: LAUNCH(16, 25, 16); break;
-    }
+    if (split_step(h, (long)B, io, sched, stream) != LIPMPC_OK) return LIPMPC_E_HIP;
   } else {
-    switch (h->nobs_l) {
-      case 0: LAUNCH(32, 0, 32); break;
-      case 2: LAUNCH(32, 2, 32); break;
-      case 5: LAUNCH(32, 5, 32); break;
-      case 7: LAUNCH(32, 7, 32); break;
-      case 13: LAUNCH(32, 13, 32); break;
-      default: LAUNCH(32, 25, 32); break;
-    }
+    with_instantiation(h, [&](auto G, auto NL, auto NV) { launch_plan_step<G, NL, NV>(h->k, (long)B, io, sched, stream); });
   }
   if (sched) hipLaunchKernelGGL(order_by_cost_kernel, dim3(1), dim3(1024), 0, stream, (long)B, sched);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
@@ -359,8 +348,10 @@ int lipmpc_plan_step_batch(lipmpc_handle* h, int64_t B, const double* state, con
                            const int32_t* obs_nv, double* U, double* X, double* theta, double* omega,
                            double* obj, int32_t* status, int32_t* iters, uint64_t* active, uint64_t* working, double* c_eta,
                            double* diag, const double* bounds, void* hip_stream) {
-  return plan_step_impl(h, B, state, goal, first_foot, delta, obs_xy, obs_nv, nullptr, U, X, theta, omega, obj, status, iters,
-                        active, working, c_eta, diag, bounds, nullptr, hip_stream);
+  const StepIO io{state, goal, first_foot, delta, obs_xy, obs_nv, U, X, theta, omega, obj, status, iters,
+                  (unsigned long long*)active, (unsigned long long*)working, c_eta, diag, bounds, /*c_eta_in=*/nullptr,
+                  /*overflow=*/nullptr};
+  return plan_step_impl(h, B, io, hip_stream);
 }
 
 int lipmpc_plan_step_batch_c_eta(lipmpc_handle* h, int64_t B, const double* state, const double* goal,
@@ -369,13 +360,10 @@ int lipmpc_plan_step_batch_c_eta(lipmpc_handle* h, int64_t B, const double* stat
                                  int32_t* status, int32_t* iters, uint64_t* active, uint64_t* working, double* diag,
                                  const double* bounds, void* hip_stream) {
   if (h && h->p.n_obs_max > 0 && !c_eta_in) return LIPMPC_E_ARG;
-  return plan_step_impl(h, B, state, goal, first_foot, delta, nullptr, nullptr, c_eta_in, U, X, theta, omega, obj, status,
-                        iters, active, working, nullptr, diag, bounds, overflow, hip_stream);
+  const StepIO io{state, goal, first_foot, delta, /*obs_xy=*/nullptr, /*obs_nv=*/nullptr, U, X, theta, omega, obj, status, iters,
+                  (unsigned long long*)active, (unsigned long long*)working, /*c_eta=*/nullptr, diag, bounds, c_eta_in, overflow};
+  return plan_step_impl(h, B, io, hip_stream);
 }
-
-#define LAUNCH_RO(GG, NL, NV)                                                                                    \
-  launch_rollout<GG, NL, NV>(h->k, (long)B, k_max, mpc_step, stop_obj, state0, goal, first_foot, delta, obs_xy, obs_nv, \
-                             X_pred, U_pred, n_steps, last_status, total_iters, bounds, stream)
 
 int lipmpc_rollout_batch(lipmpc_handle* h, int64_t B, int32_t k_max, int32_t mpc_step, double stop_obj,
                          const double* state0, const double* goal, const int8_t* first_foot, const double* delta,
@@ -388,32 +376,10 @@ int lipmpc_rollout_batch(lipmpc_handle* h, int64_t B, int32_t k_max, int32_t mpc
   if (h->p.n_obs_max > 0 && (!obs_xy || !obs_nv)) return LIPMPC_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return LIPMPC_E_HIP;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (h->G == 16 && h->nvar == 8) {
-    switch (h->nobs_l) {
-      case 0: LAUNCH_RO(16, 0, 8); break;
-      case 2: LAUNCH_RO(16, 2, 8); break;
-      case 5: LAUNCH_RO(16, 5, 8); break;
-      default: LAUNCH_RO(16, 7, 8); break;
-    }
-  } else if (h->G == 16) {
-    switch (h->nobs_l) {
-      case 0: LAUNCH_RO(16, 0, 16); break;
-      case 2: LAUNCH_RO(16, 2, 16); break;
-      case 5: LAUNCH_RO(16, 5, 16); break;
-      case 7: LAUNCH_RO(16, 7, 16); break;
-      case 13: LAUNCH_RO(16, 13, 16); break;
-      default: LAUNCH_RO(16, 25, 16); break;
-    }
-  } else {
-    switch (h->nobs_l) {
-      case 0: LAUNCH_RO(32, 0, 32); break;
-      case 2: LAUNCH_RO(32, 2, 32); break;
-      case 5: LAUNCH_RO(32, 5, 32); break;
-      case 7: LAUNCH_RO(32, 7, 32); break;
-      case 13: LAUNCH_RO(32, 13, 32); break;
-      default: LAUNCH_RO(32, 25, 32); break;
-    }
-  }
+  with_instantiation(h, [&](auto G, auto NL, auto NV) {
+    launch_rollout<G, NL, NV>(h->k, (long)B, k_max, mpc_step, stop_obj, state0, goal, first_foot, delta, obs_xy, obs_nv, X_pred,
+                              U_pred, n_steps, last_status, total_iters, bounds, stream);
+  });
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 

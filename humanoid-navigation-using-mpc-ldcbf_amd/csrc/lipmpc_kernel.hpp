@@ -182,6 +182,16 @@ __global__ __launch_bounds__(WAVE) void solve_list_kernel(
                                  diag, nullptr, cost_out);
 }
 
+// x+ = A_l x + B_l u of the CoM (px, vx, py, vy) under the input u = (ux, uy) (HumanoidMpc.py:34-48), in place
+__device__ __forceinline__ void lip_advance(double ch, double sh_over_beta, double beta_sh, double ux, double uy, double& px,
+                                            double& vx, double& py, double& vy) {
+  const double px0 = px, vx0 = vx, py0 = py, vy0 = vy;
+  px = ch * px0 + sh_over_beta * vx0 + (1.0 - ch) * ux;
+  vx = beta_sh * px0 + ch * vx0 - beta_sh * ux;
+  py = ch * py0 + sh_over_beta * vy0 + (1.0 - ch) * uy;
+  vy = beta_sh * py0 + ch * vy0 - beta_sh * uy;
+}
+
 // ------------------------------------------------------------------------------------------
 // kernel 2: the closed loop of HumanoidMPC.run_simulation on the device (lipmpc_rollout_batch),
 // HumanoidMpc.py:380-459: per sample k: stop if the previous objective < 0.05 (:392); on MPC samples
@@ -245,13 +255,7 @@ __global__ __launch_bounds__(WAVE) void rollout_kernel(
         theta1 = in.th0 + omega0 * P.tau;
       }
       if (!fin) {
-        if (is_mpc) {
-          const double px = in.p0x, vx = in.v0x, py = in.p0y, vy = in.v0y;
-          in.p0x = P.ch * px + P.sh_over_beta * vx + (1.0 - P.ch) * ukx;
-          in.v0x = P.beta_sh * px + P.ch * vx - P.beta_sh * ukx;
-          in.p0y = P.ch * py + P.sh_over_beta * vy + (1.0 - P.ch) * uky;
-          in.v0y = P.beta_sh * py + P.ch * vy - P.beta_sh * uky;
-        }
+        if (is_mpc) lip_advance(P.ch, P.sh_over_beta, P.beta_sh, ukx, uky, in.p0x, in.v0x, in.p0y, in.v0y);
         in.th0 = theta1;
         if ((k + 1) % mpc_step == 0) in.foot0 = -in.foot0;
         if (in.valid && lane == 0) {
@@ -266,13 +270,19 @@ __global__ __launch_bounds__(WAVE) void rollout_kernel(
   if (in.valid && lane == 0) { n_steps[pb] = k_done; last_status[pb] = st_last; total_iters[pb] = it_sum; }
 }
 
-// host-side launcher of one instantiation (defined in lipmpc_inst.hip, one object per (G, NOBS_L))
+// The buffers of one MPC step (lipmpc_plan_step_batch / _c_eta), in the order the step kernels take them.  Host side only: the
+// launchers in lipmpc_inst.hip spell them out as kernel arguments, so every kernel keeps its own __restrict__ parameter list.
+struct StepIO {
+  const double* state; const double* goal; const int8_t* first_foot; const double* delta;
+  const double* obs_xy; const int32_t* obs_nv;
+  double* U; double* X; double* theta; double* omega; double* obj; int32_t* status; int32_t* iters;
+  unsigned long long* active; unsigned long long* working; double* c_eta; double* diag;
+  const double* bounds; const double* c_eta_in; const int32_t* overflow;
+};
+
+// host-side launchers of one instantiation (defined in lipmpc_inst.hip, one object per (G, NOBS_L, NVAR))
 template <int G, int NOBS_L, int NVAR>
-void launch_plan_step(const KArgs& k, long B, const double* state, const double* goal, const int8_t* first_foot,
-                      const double* delta, const double* obs_xy, const int32_t* obs_nv, double* U, double* X,
-                      double* theta, double* omega, double* obj, int32_t* status, int32_t* iters,
-                      unsigned long long* active, unsigned long long* working, double* c_eta, double* diag, const double* bounds,
-                      const double* c_eta_in, int32_t* sched, const int32_t* overflow_in, hipStream_t stream);
+void launch_plan_step(const KArgs& k, long B, const StepIO& io, int32_t* sched, hipStream_t stream);
 template <int G, int NOBS_L, int NVAR>
 void launch_rollout(const KArgs& k, long B, int k_max, int mpc_step, double stop_obj, const double* state0,
                     const double* goal, const int8_t* first_foot, const double* delta, const double* obs_xy,
@@ -280,10 +290,6 @@ void launch_rollout(const KArgs& k, long B, int k_max, int mpc_step, double stop
                     int32_t* total_iters, const double* bounds, hipStream_t stream);
 // one solver body of the split launch over its class's list (32 lanes per problem; defined in lipmpc_inst.hip)
 template <int G, int NL, int NVAR>
-void launch_solve_list(const KArgs& k, long B, int cls, const int32_t* ws, const double* state, const double* goal,
-                       const int8_t* first_foot, const double* delta, const double* obs_xy, const int32_t* obs_nv, double* U,
-                       double* X, double* theta, double* omega, double* obj, int32_t* status, int32_t* iters,
-                       unsigned long long* active, unsigned long long* working, double* c_eta, double* diag, const double* bounds,
-                       const double* c_eta_in, int32_t* cost_out, const int32_t* overflow_in, hipStream_t stream);
+void launch_solve_list(const KArgs& k, long B, int cls, const int32_t* ws, const StepIO& io, int32_t* cost_out, hipStream_t stream);
 
 }  // namespace lipmpc_dev

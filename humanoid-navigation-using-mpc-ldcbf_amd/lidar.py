@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .compat import HumanoidMPC, _ring_of
-from .solver import _ptr
+from .solver import _check, _ptr, _step_out_ptrs
 
 NOISE_STD = 0.01           # range_finder_wth_polygons_dbscan.py:163
 DBSCAN_EPS = 0.3           # :100
@@ -89,14 +89,9 @@ class LidarSensor:
                                 ("c_eta", (B, self.n_obs_max, 4), torch.float64), ("n_inferred", (B,), torch.int32),
                                 ("overflow", (B,), torch.int32), ("hits", (B, self.resolution, 2), torch.float64),
                                 ("labels", (B, self.resolution), torch.int32)):
-            t = out.get(name)
-            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous()):
-                raise ValueError(f"out['{name}']: expected contiguous {dt} {shape} on {dev}")
-        if (state.dtype != torch.float64 or state.dim() != 2 or state.shape[1] != 5 or state.device != dev or not state.is_contiguous()):
-            raise ValueError(f"state: expected contiguous float64 [B,5] on {dev}")
-        if noise is not None and (tuple(noise.shape) != (B, self.resolution, 2) or noise.dtype != torch.float64
-                                  or noise.device != dev or not noise.is_contiguous()):
-            raise ValueError(f"noise: expected contiguous float64 {(B, self.resolution, 2)} on {dev}")
+            _check(out.get(name), shape, dt, dev, f"out['{name}']")
+        _check(state, (B, 5), torch.float64, dev, "state", required=True)
+        _check(noise, (B, self.resolution, 2), torch.float64, dev, "noise")
         stream = torch.cuda.current_stream(dev).cuda_stream
         n_env, v_env, shared, exy, env = self.n_env, self.v_env, 1, self.env_xy, self.env_nv
         if env_xy is not None:
@@ -146,7 +141,7 @@ class LidarSensor:
         if P.n_obs_max != self.n_obs_max or P.v_max != self.v_max or solver.device != self.device:
             raise ValueError("solver and sensor must share n_obs_max, v_max and the device")
         B = solver._check_inputs(state, goal, first_foot, None, None, delta, need_obstacles=False)
-        solver._check_optional(bounds, (B, 4), torch.float64, "bounds")
+        _check(bounds, (B, 4), torch.float64, self.device, "bounds")
         if sen is None:
             sen = self.alloc_outputs(B, rings=False, c_eta=True)
         if out is None:
@@ -154,12 +149,8 @@ class LidarSensor:
         else:
             solver._check_outputs(out, B)
         for name, shape, dt in (("c_eta", (B, self.n_obs_max, 4), torch.float64), ("n_inferred", (B,), torch.int32), ("overflow", (B,), torch.int32)):
-            t = sen.get(name)
-            if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"sen['{name}']: expected contiguous {dt} {shape} on {self.device}")
-        if noise is not None and (tuple(noise.shape) != (B, self.resolution, 2) or noise.dtype != torch.float64
-                                  or noise.device != self.device or not noise.is_contiguous()):
-            raise ValueError(f"noise: expected contiguous float64 {(B, self.resolution, 2)} on {self.device}")
+            _check(sen.get(name), shape, dt, self.device, f"sen['{name}']", required=True)
+        _check(noise, (B, self.resolution, 2), torch.float64, self.device, "noise")
         if schedule is not None and (schedule.dtype != torch.int32 or schedule.device != self.device or not schedule.is_contiguous()
                                      or schedule.numel() != int(self.lib.lipmpc_lidar_schedule_words(B))):
             raise ValueError("schedule: a buffer of make_schedule(B) for this B")
@@ -168,8 +159,7 @@ class LidarSensor:
             solver._h, B, self.resolution, self.n_env, self.v_env, 1, self.lidar_range, DBSCAN_EPS, DBSCAN_MIN_SAMPLES,
             _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(self.env_xy), _ptr(self.env_nv), _ptr(self.table),
             _ptr(noise), _ptr(sen["c_eta"]), _ptr(sen["n_inferred"]), _ptr(sen["overflow"]), _ptr(schedule),
-            _ptr(out["U"]), _ptr(out["X"]), _ptr(out["theta"]), _ptr(out["omega"]), _ptr(out["obj"]), _ptr(out["status"]),
-            _ptr(out["iters"]), _ptr(out["active"]), _ptr(out.get("working")), _ptr(out.get("diag")), _ptr(bounds), C.c_void_p(stream))
+            *_step_out_ptrs(out), _ptr(bounds), C.c_void_p(stream))
         _lib.check(rc, "lipmpc_sense_plan_step_batch")
         return sen, out
 

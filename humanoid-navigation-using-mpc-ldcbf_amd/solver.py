@@ -67,6 +67,24 @@ def _ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _check(t, shape, dtype, device, name, required=False):
+    """A buffer whose raw pointer goes to a kernel: a contiguous ``dtype`` tensor of ``shape`` on ``device``, or None when
+    not ``required``; anything else is a ValueError naming it."""
+    if t is None:
+        if required:
+            raise ValueError(f"{name} is required")
+        return
+    if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous {dtype} {shape} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _step_out_ptrs(out, c_eta_slot=False):
+    """The output pointers of a step in the order of the C ABI: U .. working[, c_eta when the entry point has that slot],
+    diag (absent optional outputs: NULL)."""
+    names = ("U", "X", "theta", "omega", "obj", "status", "iters", "active", "working") + (("c_eta",) if c_eta_slot else ()) + ("diag",)
+    return [_ptr(out.get(k)) for k in names]
+
+
 class BatchedLipMpc:
     """One handle = one (device, parameter set).  ``plan_step_batch`` solves B independent MPC
     steps; ``advance`` applies the reference's state update to the states in place."""
@@ -89,8 +107,8 @@ class BatchedLipMpc:
     def set_workspace(self, capacity):
         """Split launch of this handle's step solves (lipmpc_set_workspace): for 32-lane problems (N > 8) in the exact mode
         the step runs as classification -> index lists -> one kernel per solver body (each with its own register
-        allocation); same optimum, statuses and active sets as the single kernel (a problem may run in another body there:
-        last-bit differences).  The handle sets one up by itself for the batch sizes it sees
+        allocation); same optimum and active sets as the single kernel, a status may differ only between SOLVED and UNCERTIFIED
+        (a problem may run in another body there: last-bit differences).  The handle sets one up by itself for the batch sizes it sees
         (``auto_workspace``); 0 = back to the single dispatching kernel."""
         capacity = int(capacity)
         nbytes = int(self.lib.lipmpc_workspace_bytes(self._h, capacity)) if capacity > 0 else 0
@@ -139,23 +157,15 @@ class BatchedLipMpc:
         return out
 
     def _check_inputs(self, state, goal, first_foot, obs_xy, obs_nv, delta, need_obstacles=True):
-        P = self.params
+        P, dev = self.params, self.device
         B = state.shape[0]
-
-        def need(t, shape, dtype, name):
-            if t is None:
-                raise ValueError(f"{name} is required")
-            if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"{name}: expected contiguous {dtype} {shape} on {self.device}, got "
-                                 f"{t.dtype} {tuple(t.shape)} on {t.device}")
-        need(state, (B, 5), torch.float64, "state")
-        need(goal, (B, 2), torch.float64, "goal")
-        need(first_foot, (B,), torch.int8, "first_foot")
+        _check(state, (B, 5), torch.float64, dev, "state", required=True)
+        _check(goal, (B, 2), torch.float64, dev, "goal", required=True)
+        _check(first_foot, (B,), torch.int8, dev, "first_foot", required=True)
         if P.n_obs_max > 0 and need_obstacles:
-            need(obs_xy, (B, P.n_obs_max, P.v_max, 2), torch.float64, "obs_xy")
-            need(obs_nv, (B, P.n_obs_max), torch.int32, "obs_nv")
-        if delta is not None:
-            need(delta, (B,), torch.float64, "delta")
+            _check(obs_xy, (B, P.n_obs_max, P.v_max, 2), torch.float64, dev, "obs_xy", required=True)
+            _check(obs_nv, (B, P.n_obs_max), torch.int32, dev, "obs_nv", required=True)
+        _check(delta, (B,), torch.float64, dev, "delta")
         return B
 
     # ---- the hot path -----------------------------------------------------------------------------
@@ -168,7 +178,7 @@ class BatchedLipMpc:
         valid once the current stream is synchronised.  ``active`` = the rows tight at the optimum (slack <= 1e-7: unique),
         ``working`` = the rows carrying a multiplier in the finish's certificate (include/lipmpc.h)."""
         B = self._check_inputs(state, goal, first_foot, obs_xy, obs_nv, delta)
-        self._check_optional(bounds, (B, 4), torch.float64, "bounds")
+        _check(bounds, (B, 4), torch.float64, self.device, "bounds")
         if out is None:
             out = self.alloc_outputs(B, with_c_eta, with_diag, with_working)
         else:
@@ -177,9 +187,7 @@ class BatchedLipMpc:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.lipmpc_plan_step_batch(
             self._h, B, _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(obs_xy), _ptr(obs_nv),
-            _ptr(out["U"]), _ptr(out["X"]), _ptr(out["theta"]), _ptr(out["omega"]), _ptr(out["obj"]),
-            _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["active"]), _ptr(out.get("working")), _ptr(out.get("c_eta")),
-            _ptr(out.get("diag")), _ptr(bounds), C.c_void_p(stream))
+            *_step_out_ptrs(out, c_eta_slot=True), _ptr(bounds), C.c_void_p(stream))
         _lib.check(rc, "lipmpc_plan_step_batch")
         return out
 
@@ -191,13 +199,10 @@ class BatchedLipMpc:
         overflow [B] int32 or None: the flags of whoever produced the rows (LidarSensor.sense: the scan's clusters did not fit
         the obstacle slots); a flagged problem is not solved against its truncated list: status STATUS_SENSOR_OVERFLOW, NaN
         outputs (advance() leaves the robot where it is)."""
-        P = self.params
         B = self._check_inputs(state, goal, first_foot, None, None, delta, need_obstacles=False)
-        if (c_eta_in is None or tuple(c_eta_in.shape) != (B, P.n_obs_max, 4) or c_eta_in.dtype != torch.float64
-                or c_eta_in.device != self.device or not c_eta_in.is_contiguous()):
-            raise ValueError(f"c_eta_in: expected contiguous float64 {(B, P.n_obs_max, 4)} on {self.device}")
-        self._check_optional(bounds, (B, 4), torch.float64, "bounds")
-        self._check_optional(overflow, (B,), torch.int32, "overflow")
+        _check(c_eta_in, (B, self.params.n_obs_max, 4), torch.float64, self.device, "c_eta_in", required=True)
+        _check(bounds, (B, 4), torch.float64, self.device, "bounds")
+        _check(overflow, (B,), torch.int32, self.device, "overflow")
         if out is None:
             out = self.alloc_outputs(B, False, with_diag, with_working)
         else:
@@ -206,36 +211,31 @@ class BatchedLipMpc:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.lipmpc_plan_step_batch_c_eta(
             self._h, B, _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(c_eta_in), _ptr(overflow),
-            _ptr(out["U"]), _ptr(out["X"]), _ptr(out["theta"]), _ptr(out["omega"]), _ptr(out["obj"]),
-            _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["active"]), _ptr(out.get("working")), _ptr(out.get("diag")),
-            _ptr(bounds), C.c_void_p(stream))
+            *_step_out_ptrs(out), _ptr(bounds), C.c_void_p(stream))
         _lib.check(rc, "lipmpc_plan_step_batch_c_eta")
         return out
 
-    def _check_optional(self, t, shape, dtype, name):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
-            raise ValueError(f"{name}: expected contiguous {dtype} {shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-
-    def _check_outputs(self, out, B, with_c_eta=False):
+    def _check_outputs(self, out, B):
         """caller-supplied output buffers must have the shapes alloc_outputs gives (raw pointers go to the kernel)"""
-        ref = {"U": ((B, self.params.N, 2), torch.float64), "X": ((B, self.params.N + 1, 4), torch.float64),
-               "theta": ((B, self.params.N + 1), torch.float64), "omega": ((B, self.params.N), torch.float64),
+        P, dev = self.params, self.device
+        ref = {"U": ((B, P.N, 2), torch.float64), "X": ((B, P.N + 1, 4), torch.float64),
+               "theta": ((B, P.N + 1), torch.float64), "omega": ((B, P.N), torch.float64),
                "obj": ((B,), torch.float64), "status": ((B,), torch.int32), "iters": ((B,), torch.int32),
-               "active": ((B, self.params.active_words), torch.int64)}
+               "active": ((B, P.active_words), torch.int64)}
         for k, (shape, dt) in ref.items():
             if k not in out:
                 raise ValueError(f"out['{k}'] missing")
-            self._check_optional(out[k], shape, dt, f"out['{k}']")
-        self._check_optional(out.get("c_eta"), (B, self.params.n_obs_max, 4), torch.float64, "out['c_eta']")
-        self._check_optional(out.get("diag"), (B, _lib.DIAG_WORDS), torch.float64, "out['diag']")
-        self._check_optional(out.get("working"), (B, self.params.active_words), torch.int64, "out['working']")
+            _check(out[k], shape, dt, dev, f"out['{k}']")
+        _check(out.get("c_eta"), (B, P.n_obs_max, 4), torch.float64, dev, "out['c_eta']")
+        _check(out.get("diag"), (B, _lib.DIAG_WORDS), torch.float64, dev, "out['diag']")
+        _check(out.get("working"), (B, P.active_words), torch.int64, dev, "out['working']")
 
     def advance(self, state, first_foot, out):
         """In place: state <- (A_l x + B_l U[:,0], theta[:,1]), first_foot <- -first_foot for the
         problems whose status is solved (HumanoidMpc.py:432-447)."""
         B = state.shape[0]
-        self._check_optional(state, (B, 5), torch.float64, "state")
-        self._check_optional(first_foot, (B,), torch.int8, "first_foot")
+        _check(state, (B, 5), torch.float64, self.device, "state")
+        _check(first_foot, (B,), torch.int8, self.device, "first_foot")
         self._check_outputs(out, B)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.lipmpc_advance_batch(self._h, B, _ptr(state), _ptr(first_foot), _ptr(out["U"]),
@@ -256,9 +256,9 @@ class BatchedLipMpc:
                                 ("X_pred", (B, k_max + 1, 5), torch.float64), ("U_pred", (B, k_max, 3), torch.float64)):
             if name not in fleet:
                 raise ValueError(f"fleet['{name}'] missing")
-            self._check_optional(fleet[name], shape, dt, f"fleet['{name}']")
+            _check(fleet[name], shape, dt, self.device, f"fleet['{name}']")
         self._check_outputs(out, B)
-        self._check_optional(overflow, (B,), torch.int32, "overflow")
+        _check(overflow, (B,), torch.int32, self.device, "overflow")
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.lipmpc_fleet_update_batch(
             self._h, B, int(k_max), float(stop_obj), _ptr(fleet["state"]), _ptr(fleet["first_foot"]), _ptr(fleet["walking"]),
@@ -272,7 +272,7 @@ class BatchedLipMpc:
         """Closed loop on the device (HumanoidMpc.py:345-459) for B robots: returns dict(X_pred [B,k_max+1,5],
         U_pred [B,k_max,3], n_steps [B], last_status [B], total_iters [B]); rows beyond n_steps are undefined."""
         B = self._check_inputs(state0, goal, first_foot, obs_xy, obs_nv, delta)
-        self._check_optional(bounds, (B, 4), torch.float64, "bounds")
+        _check(bounds, (B, 4), torch.float64, self.device, "bounds")
         if int(k_max) < 1 or int(mpc_step) < 1:
             raise ValueError("k_max and mpc_step must be positive")
         dev = self.device

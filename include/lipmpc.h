@@ -170,12 +170,15 @@ int64_t lipmpc_schedule_words(int64_t B);
  * (304 B of scratch per lane at N = 16 / 50 obstacles).  With a workspace the step runs as: one classification pass (the
  * front end alone: which body each problem needs), a one-workgroup stable counting sort into one index list per body, and ONE
  * KERNEL PER BODY over its list, the kernels side by side on streams the handle owns (fork / join by events on the caller's
- * stream, so the call stays asynchronous and stream-ordered, and can be captured in a graph).  Results are bit-identical
- * to the single-kernel launch; problems of one class share waves.  Ignored (single kernel) for N <= 8, for the flags that
- * keep every row, and for batches larger than the workspace was sized for.  While it is set, the order of
- * lipmpc_set_schedule is not applied (the costs are still left).
+ * stream, so the call stays asynchronous and stream-ordered, and can be captured in a graph).  Against the single-kernel
+ * launch the results have the same optimum and the same tight set; a status may differ only between SOLVED and UNCERTIFIED
+ * (a problem may run in another solver body, whose sums run in another order: last-bit differences).  For a given batch
+ * the split launch is deterministic from run to run; problems of one class share waves.  Ignored (single kernel) for
+ * N <= 8, for the flags that keep every row, and for batches larger than the workspace was sized for.  While it is set,
+ * the order of lipmpc_set_schedule is not applied (the costs are still left).
  * `workspace`: device buffer of lipmpc_workspace_bytes(h, capacity) bytes, contents arbitrary, owned by the caller, alive
- * until unset (NULL) or the handle is destroyed; launches on it must be stream-ordered. */
+ * until unset (NULL) or the handle is destroyed.  The workspace, like the handle's side streams and events, is shared by
+ * every launch of the handle: all step launches of a handle that has one must be stream-ordered. */
 int64_t lipmpc_workspace_bytes(const lipmpc_handle* h, int64_t capacity);
 int lipmpc_set_workspace(lipmpc_handle* h, void* workspace, int64_t capacity);
 
