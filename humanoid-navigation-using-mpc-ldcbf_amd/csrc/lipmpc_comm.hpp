@@ -115,9 +115,40 @@ template <int G> __device__ __forceinline__ double gsum(double x) {
   if constexpr (G == 32) x += gxor<G, 16>(x);
   return x;
 }
+// v_max_f64 / v_min_f64 as written.  fmax / fmin compile, in IEEE mode, to the same instruction behind one
+// canonicalisation (v_max_f64 x, x) of every operand the compiler cannot prove canonical: each DPP move's result, each
+// loop-carried or selected value -- about 40 instructions per interior-point iteration, most of them on the chain of a
+// group reduction.  Canonicalising quiets a signalling NaN and changes no other bit; every operand these take is the
+// result of FP arithmetic (or a move of one), which is never a signalling NaN, so the result is the same bits.
+__device__ __forceinline__ double vmax(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ double vmin(double a, double b) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// fmax(m, fabs(x)), fmax(0.0, fabs(x)), fmax(0.0, x)
+__device__ __forceinline__ double vmax_abs(double m, double x) {
+  double r;
+  asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(m), "v"(x));
+  return r;
+}
+__device__ __forceinline__ double vmax0_abs(double x) {
+  double r;
+  asm("v_max_f64 %0, 0, |%1|" : "=v"(r) : "v"(x));
+  return r;
+}
+__device__ __forceinline__ double vmax0(double x) {
+  double r;
+  asm("v_max_f64 %0, 0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
 template <int G> __device__ __forceinline__ double gmin(double x) {
-  x = fmin(x, gxor<G, 1>(x)); x = fmin(x, gxor<G, 2>(x)); x = fmin(x, gxor<G, 4>(x)); x = fmin(x, gxor<G, 8>(x));
-  if constexpr (G == 32) x = fmin(x, gxor<G, 16>(x));
+  x = vmin(x, gxor<G, 1>(x)); x = vmin(x, gxor<G, 2>(x)); x = vmin(x, gxor<G, 4>(x)); x = vmin(x, gxor<G, 8>(x));
+  if constexpr (G == 32) x = vmin(x, gxor<G, 16>(x));
   return x;
 }
 template <int G> __device__ __forceinline__ int gmin_int(int x) {
@@ -126,8 +157,8 @@ template <int G> __device__ __forceinline__ int gmin_int(int x) {
   return x;
 }
 template <int G> __device__ __forceinline__ double gmax(double x) {
-  x = fmax(x, gxor<G, 1>(x)); x = fmax(x, gxor<G, 2>(x)); x = fmax(x, gxor<G, 4>(x)); x = fmax(x, gxor<G, 8>(x));
-  if constexpr (G == 32) x = fmax(x, gxor<G, 16>(x));
+  x = vmax(x, gxor<G, 1>(x)); x = vmax(x, gxor<G, 2>(x)); x = vmax(x, gxor<G, 4>(x)); x = vmax(x, gxor<G, 8>(x));
+  if constexpr (G == 32) x = vmax(x, gxor<G, 16>(x));
   return x;
 }
 // (value, index) arg-min with ties to the lower index (numpy argmin order on canonical rows)

@@ -111,10 +111,10 @@
       double w[NR], d[NR];
       double mu_l = 0.0, rpmax_l = 0.0, zmax_l = 0.0;
 #pragma unroll
-      for (int i = 0; i < NR; ++i) {
+      for (int i = 0; i < NR; ++i) {                       // (vmax*: fmax without the canonicalisations, lipmpc_comm.hpp)
         mu_l = fma(s[i], z[i], mu_l);
-        rpmax_l = fmax(rpmax_l, fabs(rp[i]));
-        zmax_l = fmax(zmax_l, z[i]);
+        rpmax_l = i == 0 ? vmax0_abs(rp[i]) : vmax_abs(rpmax_l, rp[i]);
+        zmax_l = i == 0 ? vmax0(z[i]) : vmax(zmax_l, z[i]);
       }
       mu_l = fma(ball_w * s[R_M], z[R_M], mu_l);           // the other n_d - 1 copies of the ballast row
       // streamed rows, pass A: residual statistics, K blocks and predictor weights in one sweep
@@ -213,7 +213,7 @@
         const double mu_aff = fma(a_aff * a_aff, gsum<G>(s2_l), (1.0 - a_aff) * musum) * inv_m;
         const double ratio = mu_aff * chain_rcp(mu);
         double sigma = ratio * ratio * ratio;
-        sigma = fmax(sigma, lds_mu[grp][1]);      // no-progress safeguard: floor computed at the top of the iteration
+        sigma = vmax(sigma, lds_mu[grp][1]);      // no-progress safeguard: floor computed at the top of the iteration
         const double sigma_mu = sigma * mu;
         PH(4)
         // corrector: rc = s z + ds_a dz_a - sigma mu

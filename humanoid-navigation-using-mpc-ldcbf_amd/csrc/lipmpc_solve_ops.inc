@@ -103,6 +103,8 @@
     bool ok = true;
     const int ln = fresh(lane);
     dpp_fence();
+    double pnext = 0.0;                                   // G = 16: pivot of the next step, broadcast at the end of the step
+    if constexpr (FUSED) pnext = gbcast<G, 0>(Krow[0]);
     static_for<0, NV>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
       if constexpr (FUSED) {
@@ -110,13 +112,15 @@
         // updates of the step as one asm statement.  (Issuing the updates BETWEEN the links of the next step's pivot chain --
         // "lookahead", tried in round 4 -- gains nothing: a dependent FP64 instruction costs 7 cycles against 4.6 for an
         // independent one, the chain is issue slots, not latency; profiles/r04_dev_tools/r04_iter_cost_lookahead_factorisation.txt.)
-        const double pj = gbcast<G, j>(Krow[j]);
+        const double pj = pnext;                          // gbcast<G, j>(Krow[j])
         ok = ok && (pj > 0.0);
         const double ip = fast_rcp(pj);
         const double nf = zero_unless(ln > j, Krow[j] * -ip);
-        ipiv = (ln == j) ? ip : ipiv;
+        // ipiv ends as ip_l on lane l either way; (ln > j - 1) is the mask of the step before, (ln == j) one more compare.
+        // (With NV < G the lanes past the variables keep 0.5: ln == j there.)
+        ipiv = ((NV < G) ? (ln == j) : (ln > j - 1)) ? ip : ipiv;
         Xl[j] = nf;
-        FactorStep<NV, j>::run(Krow, nf);
+        FactorStep<NV, j>::run(Krow, nf, pnext);
       } else {
         // Two DPP rows per problem.  Row j of the Schur complement equals its column j, and the column is lane-distributed
         // (lane cc holds S[cc][j] in Krow[j]): ONE cross-row exchange per step makes both 16-lane halves of the column

@@ -1,8 +1,13 @@
-"""Dev tool: instruction histogram of the loops of plan_step_kernel in a hipcc -S listing (block comments name the loop)."""
+"""Dev tool: instruction histogram of the loops of plan_step_kernel in a hipcc -S listing (block comments name the loop).
+    python tools/loop_hist.py LISTING.s [TOP_N] [KERNEL_PREFIX]
+KERNEL_PREFIX selects the instantiation, e.g. _ZN10lipmpc_dev16plan_step_kernelILi16ELi5ELi16ELb1 for the headline
+<16, 5, 16, true>; the whole function is scanned (it has more than one s_endpgm).  In that kernel the interior-point
+loops of the 5-, 2- and 1-slot bodies come in that order."""
 import re, sys, collections
 lines = open(sys.argv[1]).read().split('\n')
-start = [i for i, l in enumerate(lines) if l.startswith('_ZN10lipmpc_dev16plan_step_kernel')][0]
-end = [i for i, l in enumerate(lines) if 's_endpgm' in l and i > start][0]
+prefix = sys.argv[3] if len(sys.argv) > 3 else '_ZN10lipmpc_dev16plan_step_kernel'
+start = [i for i, l in enumerate(lines) if l.startswith(prefix)][0]
+end = [i for i, l in enumerate(lines) if l.startswith('.Lfunc_end') and i > start][0]
 cur = None
 loops = collections.defaultdict(list)
 for l in lines[start:end]:
