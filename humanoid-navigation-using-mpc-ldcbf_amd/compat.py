@@ -66,8 +66,11 @@ class HumanoidMPC:
         # reference seeds its next solve with the shifted prediction, HumanoidMpc.py:450-455): same optimum, 15-30 % fewer
         # iterations.  Off by default: the interior iterate a step stops at depends on where it started, and the closed
         # loops that reproduce the reference's figures (tests/golden/make_pdf_pins.py) are the cold-started ones -- the
-        # 7-sub-goal maze run ends in an infeasible corner 90 steps early when warm-started.
+        # 7-sub-goal maze run ends in an infeasible corner 90 steps early when warm-started.  The step-by-step loop (sensed
+        # obstacles, overridden hooks) carries the same seeding from sample to sample in a one-robot warm-start record
+        # (lipmpc_set_warm_start) of each step solver.
         self._warm_start = warm_start
+        self.solver_iters = []          # interior-point iterations of every MPC step of the last step-by-step run
         self._device = device
         self._solver = None
         self._ce_solver = None
@@ -86,7 +89,11 @@ class HumanoidMPC:
                          sampling_time=self.sampling_time,
                          flags=(0 if self._exact else FLAG_INTERIOR) | (FLAG_WARM_START if self._warm_start else 0),
                          tol_interior=self._interior_tol)
-        return BatchedLipMpc(p, self._device)
+        sv = BatchedLipMpc(p, self._device)
+        if self._warm_start:
+            sv.set_warm_start(1)        # (a new handle = a new, zeroed record: the next step starts cold; N = 1 / more than
+                                        # 14 obstacle slots: no record, every step cold)
+        return sv
 
     def _plan_rings(self, state5, s0):
         rings = self._get_obstacle_rings(state5[0], state5[2])
@@ -152,14 +159,25 @@ class HumanoidMPC:
                 elif n2 != n2:                    # NaN from the hook (degenerate geometry): let the solver report it
                     rows.append(np.array([0.0, 0.0, np.nan, np.nan]))
         n_obs = len(rows)
-        if self._ce_solver is None or self._ce_solver.params.n_obs_max != n_obs:
+        if self._warm_start:
+            # grow-only slots (at least a LiDAR sensor's 12), empty ones eta = (0, 0): a sensed environment changes its row
+            # count from scan to scan, and a rebuilt solver would drop the warm-start record
+            have = self._ce_solver.params.n_obs_max if self._ce_solver is not None else 0
+            n_slots = max(n_obs, have, 12)
+            if self._ce_solver is None or n_slots != have:
+                self._ce_solver = self._make_solver(n_slots, 3)
+        elif self._ce_solver is None or self._ce_solver.params.n_obs_max != n_obs:
             p = LipMpcParams(N=self.N_horizon, n_obs_max=n_obs, v_max=3, sampling_time=self.sampling_time,
                              flags=0 if self._exact else FLAG_INTERIOR, tol_interior=self._interior_tol)
             self._ce_solver = BatchedLipMpc(p, self._device)
         sv = self._ce_solver
+        n_slots = sv.params.n_obs_max
         dev = sv.device
         t = lambda arr, dt: torch.as_tensor(np.ascontiguousarray(arr), dtype=dt, device=dev)
-        ce = t(np.array(rows).reshape(1, n_obs, 4) if n_obs else np.zeros((1, 0, 4)), torch.float64)
+        ce_h = np.zeros((1, n_slots, 4))
+        if n_obs:
+            ce_h[0, :n_obs] = np.array(rows).reshape(n_obs, 4)
+        ce = t(ce_h, torch.float64)
         out = sv.plan_step_batch_c_eta(t(state5[None, :], torch.float64), t(np.asarray(self.goal, float)[None, :], torch.float64),
                                        t(np.array([s0], np.int8), torch.int8), ce,
                                        None if delta is None else t(np.array([delta]), torch.float64))
@@ -209,6 +227,7 @@ class HumanoidMPC:
         ch, sh, beta = self._lip()
         k = 0
         hooked = self._hooks_overridden()
+        self.solver_iters = []
         for k in range(self.num_inputs):
             is_mpc = k % self.mpc_step == 0
             st = X_pred[:, k].copy()
@@ -228,6 +247,7 @@ class HumanoidMPC:
             self.precomputed_theta, self.precomputed_omega = r["theta"], r["omega"]
             if is_mpc:
                 self.last_status = int(r["status"])
+                self.solver_iters.append(int(r["iters"]))
                 if self.last_status not in (STATUS_SOLVED, STATUS_UNCERTIFIED):
                     if self.verbosity > 0:
                         print(f"===== ERROR ({k}) ===== solver status {self.last_status}")  # :419-429

@@ -145,6 +145,8 @@ struct lipmpc_handle {
   int64_t sched_cap;    // largest batch it holds
   int32_t* ws;          // optional split-launch workspace (lipmpc_set_workspace), device memory owned by the caller
   int64_t ws_cap;
+  double* warm;         // optional warm-start records (lipmpc_set_warm_start), device memory owned by the caller
+  int64_t warm_cap;     // problems they hold
   hipStream_t side[SPLIT_CLASSES - 1];     // the solver bodies of a split launch run side by side (created with the workspace)
   hipEvent_t fork_ev, join_ev[SPLIT_CLASSES - 1];
   bool have_streams;
@@ -325,7 +327,13 @@ static int plan_step_impl(lipmpc_handle* h, int64_t B, const StepIO& io, void* h
   if (hipSetDevice(h->device) != hipSuccess) return LIPMPC_E_HIP;
   hipStream_t stream = (hipStream_t)hip_stream;
   int32_t* sched = (h->sched && B <= h->sched_cap) ? h->sched : nullptr;
-  if (h->ws && B <= h->ws_cap && B <= BIN_MAX_B && split_capable(h)) {
+  if (h->warm) {
+    if (B > h->warm_cap) return LIPMPC_E_ARG;
+    // (lipmpc_set_warm_start admits the warm_capable instantiations only; no other is ever launched here)
+    with_instantiation(h, [&](auto G, auto NL, auto NV) {
+      if constexpr (NL <= (G == 32 ? 2 : 7)) launch_warm_step<G, NL, NV>(h->k, (long)B, io, sched, h->warm, stream);
+    });
+  } else if (h->ws && B <= h->ws_cap && B <= BIN_MAX_B && split_capable(h)) {
     if (split_step(h, (long)B, io, sched, stream) != LIPMPC_OK) return LIPMPC_E_HIP;
   } else {
     with_instantiation(h, [&](auto G, auto NL, auto NV) { launch_plan_step<G, NL, NV>(h->k, (long)B, io, sched, stream); });
@@ -342,6 +350,22 @@ int lipmpc_set_schedule(lipmpc_handle* h, int32_t* schedule, int64_t capacity) {
 }
 
 int64_t lipmpc_schedule_words(int64_t B) { return B < 0 ? LIPMPC_E_ARG : SCHED_ORDER + 2L * B; }
+
+// the instantiations with warm_step_kernel (lipmpc_inst.hip: WARM_INST): horizons of 2 and more, register rows, and on 32 lanes
+// at most 2 row slots per lane -- the 32-lane bodies with 5 and 7 slots spill to scratch (240 B per lane at 7)
+static bool warm_capable(const lipmpc_handle* h) { return h->p.N >= 2 && h->nobs_l <= (h->G == 32 ? 2 : 7); }
+
+int64_t lipmpc_warm_words(const lipmpc_params* p) { return p ? 1L + 2L * p->N + lipmpc_num_rows(p) : LIPMPC_E_ARG; }
+
+int lipmpc_set_warm_start(lipmpc_handle* h, double* record, int64_t capacity) {
+  if (!h || capacity < 0) return LIPMPC_E_ARG;
+  if (!record || capacity == 0) { h->warm = nullptr; h->warm_cap = 0; return LIPMPC_OK; }
+  if (!(h->p.flags & LIPMPC_FLAG_WARM_START)) return LIPMPC_E_ARG;      // (warm => every row kept: the one presolve rule)
+  if (!warm_capable(h)) return LIPMPC_E_UNSUPPORTED;
+  h->warm = record;
+  h->warm_cap = capacity;
+  return LIPMPC_OK;
+}
 
 int lipmpc_plan_step_batch(lipmpc_handle* h, int64_t B, const double* state, const double* goal,
                            const int8_t* first_foot, const double* delta, const double* obs_xy,
@@ -394,6 +418,7 @@ int lipmpc_sense_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resolution
   if (!h || B < 0) return LIPMPC_E_ARG;
   if (h->p.n_obs_max < 1) return LIPMPC_E_UNSUPPORTED;        // a handle without obstacle slots has nothing to sense into
   if (!c_eta || !goal || !first_foot || !U || !X || !theta || !omega || !obj || !status || !iters || !active) return LIPMPC_E_ARG;
+  if (h->warm && B > h->warm_cap) return LIPMPC_E_ARG;       // (refused before the scan is enqueued)
   const int rc = lipmpc_lidar_c_eta_batch(h->device, B, resolution, n_env, v_env, env_shared, lidar_range, eps, min_samples,
                                           h->p.n_obs_max, h->p.v_max, state, env_xy, env_nv, ray_table, noise, c_eta, n_inferred,
                                           overflow, nullptr, nullptr, nullptr, nullptr, schedule, hip_stream);

@@ -12,6 +12,28 @@ namespace lipmpc_dev {
 // local row slots of a lane
 constexpr int R_RU = 0, R_RL = 1, R_VU = 2, R_VL = 3, R_M = 4, R_CBF = 5;
 
+// Canonical row index (include/lipmpc.h: reach(4N) | manoeuvr(N) | vel(4N) | LDCBF((N+1) n_obs)) of local row slot i / of LDCBF
+// slot t of lane (stage a, coordinate c); perm maps the obstacle slot 2t + c to its obstacle.  The manoeuvrability slot names
+// its stage's row on both lanes of the stage: only the c = 0 lane holds it.  ONE map for the finish's `active` / `working`
+// bits and the warm-start records (warm_step_kernel).  (A callable of references, the shape of the lambda it replaced: the
+// solver bodies compile to the same instructions.)
+struct CanonicalRows {
+  const int& a;
+  const int& c;
+  const int& N;
+  const KArgs& P;
+  const int* const& perm;
+  __device__ __forceinline__ int operator()(int i) const {
+    if (i == R_RU) return 4 * a + c;
+    if (i == R_RL) return 4 * a + 2 + c;
+    if (i == R_VU) return 5 * N + 4 * a + c;
+    if (i == R_VL) return 5 * N + 4 * a + 2 + c;
+    if (i == R_M) return 4 * N + a;
+    return ldcbf(i - R_CBF);
+  }
+  __device__ __forceinline__ int ldcbf(int t) const { return 9 * N + (a + 1) * P.n_obs + perm[2 * t + c]; }
+};
+
 // one problem's inputs as the group sees them / what the closed loop needs back
 struct StepIn {
   double p0x, v0x, p0y, v0y, th0, gx, gy, foot0, delta;
@@ -85,7 +107,9 @@ template <int G> struct FrontOut {
 
 // Front end of a step (shared by every solver body of a kernel): theta / omega, closest point and normal per obstacle,
 // presolve, compaction of the obstacles that still have a row into the leading slots.
-template <int G, int MAXOBS, bool PREFETCH = true>
+// RECORD: warm_step_kernel's own instantiation.  No code of its own: a front end shared with plan_step_kernel changed the
+// instructions the compiler chose for that kernel (lipmpc_kernel.hpp: warm_step_kernel)
+template <int G, int MAXOBS, bool PREFETCH = true, bool RECORD = false>
 __device__ __forceinline__ FrontOut<G> front_end(
     const KArgs& P, const StepIn& in, const double* __restrict__ obs_xy, const int32_t* __restrict__ obs_nv,
     double* __restrict__ theta_out, double* __restrict__ omega_out, double* __restrict__ c_eta,

@@ -1,7 +1,8 @@
 // lipmpc_inst.hip — one explicit instantiation of the step kernel per object file:
 // compiled with -DINST_G=<16|32> -DINST_NL=<0|2|5|7|13|25> -DINST_NV=<variable slots: INST_G, or 8 for horizons up to 4> (see Makefile).
 // -DINST_LIST: the solver body of the split launch with INST_NL row slots per lane instead (solve_list_kernel: one kernel per
-// body, each with its own register allocation).
+// body, each with its own register allocation).  The register-row objects (INST_NL <= 7; on 32 lanes INST_NL <= 2, the bodies
+// that compile without scratch) also hold the step with warm-start records (warm_step_kernel).
 #include "lipmpc_kernel.hpp"
 
 namespace lipmpc_dev {
@@ -30,6 +31,18 @@ void launch_plan_step(const KArgs& k, long B, const StepIO& io, int32_t* sched, 
                      io.diag, io.bounds, io.c_eta_in, sched, io.overflow);
 }
 template void launch_plan_step<INST_G, INST_NL, INST_NV>(const KArgs&, long, const StepIO&, int32_t*, hipStream_t);
+
+#if INST_NL <= (INST_G == 32 ? 2 : 7)      // (warm_capable in lipmpc_api.hip)
+template <int G, int NOBS_L, int NVAR>
+void launch_warm_step(const KArgs& k, long B, const StepIO& io, int32_t* sched, double* warm_rec, hipStream_t stream) {
+  constexpr int GPW = WAVE / G;
+  const unsigned blocks = (unsigned)((B + GPW - 1) / GPW);
+  hipLaunchKernelGGL((warm_step_kernel<G, NOBS_L, NVAR>), dim3(blocks), dim3(WAVE), 0, stream, k, B, io.state, io.goal, io.first_foot,
+                     io.delta, io.obs_xy, io.obs_nv, io.U, io.X, io.theta, io.omega, io.obj, io.status, io.iters, io.active,
+                     io.working, io.c_eta, io.diag, io.bounds, io.c_eta_in, sched, io.overflow, warm_rec);
+}
+template void launch_warm_step<INST_G, INST_NL, INST_NV>(const KArgs&, long, const StepIO&, int32_t*, double*, hipStream_t);
+#endif
 
 template <int G, int NOBS_L, int NVAR>
 void launch_rollout(const KArgs& k, long B, int k_max, int mpc_step, double stop_obj, const double* state0,

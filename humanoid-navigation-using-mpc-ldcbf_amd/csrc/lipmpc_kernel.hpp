@@ -18,7 +18,8 @@
 // certified primal active-set finish on NOBS_L row slots per lane); step_body picks the body: in the exact mode with the
 // presolve the smallest of {1, 2, 7, the handle's} slots that holds the wave's neediest problem.  Kernels: plan_step_kernel
 // (one step for B problems, optionally in the cost order of the previous launch: lipmpc_set_schedule; DISPATCH = with /
-// without the small bodies) and rollout_kernel (the whole closed loop per robot, one launch).
+// without the small bodies), warm_step_kernel (the same step warm-started from and written back to caller-owned records:
+// lipmpc_set_warm_start) and rollout_kernel (the whole closed loop per robot, one launch).
 //
 // Reference semantics followed (HumanoidNavigation/...):
 //   theta/omega            MPC/HumanoidMpc.py:137-160
@@ -116,6 +117,91 @@ __global__ __launch_bounds__(WAVE) void plan_step_kernel(
   const StepIn in = load_step_in(P, pb, prob_raw < B, state, goal, first_foot, delta_in, bounds, overflow_in);
   step_body<G, NOBS_L, NVAR, DISPATCH>(P, in, obs_xy, obs_nv, U, X, theta_out, omega_out, obj_out, status_out, iters_out, active_out,
                                        working_out, c_eta, diag, c_eta_in, nullptr, sched ? sched + SCHED_ORDER + B : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// kernel 1c: one MPC step for B problems, each warm-started from its record (lipmpc_set_warm_start)
+// ------------------------------------------------------------------------------------------
+// The record of problem b (warm_rec + b * (1 + 2N + m_tot) doubles): word 0 = 1.0 when it holds a step result, then q of the
+// interior-point phase (2N, stage-major) and its multipliers in canonical row order.  The kernel stages the record into the
+// WarmIO block of its group in the lane layout the solver parks (q on lane l, slot i's multiplier on row 1 + i), the solver
+// reads it back shifted by one stage exactly as in the closed-loop kernel, and after the solve the parked block goes back to the
+// record in canonical order.  The body is the plain one with every row kept (LIPMPC_FLAG_WARM_START: no presolve); the front
+// end keeps every obstacle in its own slot (cold = false: no compaction), so LDCBF slot 2t + c is obstacle 2t + c.  Register
+// rows only (NOBS_L <= 7: the block holds WARM_ROWS slots), on 32 lanes NOBS_L <= 2 (lipmpc_inst.hip).  Every canonical word of a record is written by exactly one lane; padding
+// groups (prob_raw >= B) start cold and write nothing.  Own instantiations of front_end and step_solve (template flag RECORD):
+// sharing theirs with plan_step_kernel changed how that kernel compiles.
+template <int G, int NOBS_L, int NVAR>
+__global__ __launch_bounds__(WAVE) void warm_step_kernel(
+    KArgs P, long B, const double* __restrict__ state, const double* __restrict__ goal,
+    const int8_t* __restrict__ first_foot, const double* __restrict__ delta_in,
+    const double* __restrict__ obs_xy, const int32_t* __restrict__ obs_nv,
+    double* __restrict__ U, double* __restrict__ X, double* __restrict__ theta_out,
+    double* __restrict__ omega_out, double* __restrict__ obj_out, int32_t* __restrict__ status_out,
+    int32_t* __restrict__ iters_out, unsigned long long* __restrict__ active_out,
+    unsigned long long* __restrict__ working_out, double* __restrict__ c_eta,
+    double* __restrict__ diag, const double* __restrict__ bounds, const double* __restrict__ c_eta_in,
+    int32_t* __restrict__ sched, const int32_t* __restrict__ overflow_in, double* __restrict__ warm_rec) {
+  constexpr int GPW = WAVE / G;
+  constexpr int MAXOBS = 2 * NOBS_L;
+  constexpr int RING_CAP = (G == 16) ? 64 : 256;
+  constexpr int NR = R_CBF + NOBS_L;
+  static_assert(NR <= WARM_ROWS, "the warm-start block holds the register row slots only");
+  if (blockDim.x != WAVE) __builtin_trap();          // see plan_step_kernel
+  __shared__ double lds_ring[GPW][MAXOBS > 0 ? RING_CAP : 1][2];
+  __shared__ double lds_obs[GPW][MAXOBS > 0 ? MAXOBS : 1][4];
+  __shared__ int lds_perm[GPW][MAXOBS > 0 ? MAXOBS : 1];
+  __shared__ int lds_flag[GPW];
+  __shared__ double lds_warm[GPW][1 + WARM_ROWS][G];
+  const int grp = threadIdx.x / G;
+  const int lane = threadIdx.x & (G - 1);
+  const long prob_raw = (long)blockIdx.x * GPW + grp;
+  long pb = prob_raw < B ? prob_raw : (B - 1);        // (the schedule as in plan_step_kernel: records stay indexed by problem)
+  if (sched && sched[SCHED_VALID] == (int)B) {
+    const long r = sched[SCHED_ORDER + pb];
+    if (r >= 0 && r < B) pb = r;
+  }
+  const StepIn in = load_step_in(P, pb, prob_raw < B, state, goal, first_foot, delta_in, bounds, overflow_in);
+  const int N = P.N;
+  const int a = lane >> 1, c = lane & 1;
+  double* rec = warm_rec + pb * (long)(1 + 2 * N + P.m_tot);
+  double* rec_z = rec + 1 + 2 * N;
+  double* wl = &lds_warm[grp][0][0];
+  const int* perm = lds_perm[grp];
+  const CanonicalRows ci{a, c, N, P, perm};
+  WarmIO ws;
+  ws.lds = wl;
+  ws.have = in.valid && rec[0] == 1.0;
+  const FrontOut<G> F = front_end<G, MAXOBS, true, true>(P, in, obs_xy, obs_nv, theta_out, omega_out, c_eta, c_eta_in, false,
+                                                         lds_ring[grp], lds_obs[grp], lds_perm[grp], &lds_flag[grp]);
+  // does slot i of this lane name a canonical row?  (lanes past the horizon, the c = 1 manoeuvrability slot and obstacle slots
+  // past n_obs do not)
+  auto has_row = [&](int i) -> bool {
+    if (a >= N) return false;
+    if (i == R_M) return c == 0;
+    if (i >= R_CBF) return perm[2 * (i - R_CBF) + c] < P.n_obs;
+    return true;
+  };
+  if (ws.have) {
+    wl[lane] = a < N ? rec[1 + lane] : 0.0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+      wl[(1 + i) * G + lane] = has_row(i) ? rec_z[ci(i)] : 0.0;
+  }
+  wave_sync();
+  const StepOut r = step_solve<G, NOBS_L, NVAR, false, true>(P, in, F, lds_obs[grp], lds_perm[grp], U, X, obj_out, status_out,
+                                                             iters_out, active_out, working_out, diag, &ws,
+                                                             sched ? sched + SCHED_ORDER + B : nullptr);
+  // the solver parked this step's interior-point result in wl (absent rows as 0) and synchronised the wave: back to the record,
+  // unshifted; the constant k = 0 rows are 0
+  if (in.valid) {
+    if (a < N) rec[1 + lane] = wl[lane];
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+      if (has_row(i)) rec_z[ci(i)] = wl[(1 + i) * G + lane];
+    for (int j = lane; j < P.n_obs; j += G) rec_z[9 * N + j] = 0.0;     // the constant k = 0 rows of obstacle j
+    if (lane == 0) rec[0] = (r.status == LIPMPC_STATUS_SOLVED || r.status == LIPMPC_STATUS_UNCERTIFIED) ? 1.0 : 0.0;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -283,6 +369,9 @@ struct StepIO {
 // host-side launchers of one instantiation (defined in lipmpc_inst.hip, one object per (G, NOBS_L, NVAR))
 template <int G, int NOBS_L, int NVAR>
 void launch_plan_step(const KArgs& k, long B, const StepIO& io, int32_t* sched, hipStream_t stream);
+// the step with warm-start records (register-row instantiations only: NOBS_L <= 7)
+template <int G, int NOBS_L, int NVAR>
+void launch_warm_step(const KArgs& k, long B, const StepIO& io, int32_t* sched, double* warm_rec, hipStream_t stream);
 template <int G, int NOBS_L, int NVAR>
 void launch_rollout(const KArgs& k, long B, int k_max, int mpc_step, double stop_obj, const double* state0,
                     const double* goal, const int8_t* first_foot, const double* delta, const double* obs_xy,

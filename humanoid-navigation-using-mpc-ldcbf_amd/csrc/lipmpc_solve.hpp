@@ -7,7 +7,8 @@ namespace lipmpc_dev {
 
 // The solve of one problem on one group of G lanes, from the front end's half-spaces: NOBS_L LDCBF row slots per lane
 // (obstacle slots 0 .. 2 NOBS_L - 1 of `obs`).  Output pointers may be null.
-template <int G, int NOBS_L, int NVAR = G, bool LEAN = false>
+// RECORD: the caller writes the parked warm-start block to a record (warm_step_kernel): rows not in the problem park 0.
+template <int G, int NOBS_L, int NVAR = G, bool LEAN = false, bool RECORD = false>
 __device__ __forceinline__ StepOut step_solve(
     const KArgs& P, const StepIn& in, const FrontOut<G>& F, const double (*obs)[4], const int* perm,
     double* __restrict__ U, double* __restrict__ X, double* __restrict__ obj_out, int32_t* __restrict__ status_out,

@@ -6,19 +6,15 @@
     wave_sync();                              // (every lane has read its neighbours' previous values by now)
     warm->lds[lane] = q;
 #pragma unroll
-    for (int i = 0; i < NR && i < WARM_ROWS; ++i) warm->lds[(1 + i) * G + lane] = z[i];
+    for (int i = 0; i < NR && i < WARM_ROWS; ++i) {
+      if constexpr (RECORD) warm->lds[(1 + i) * G + lane] = pres[i] ? z[i] : 0.0;
+      else warm->lds[(1 + i) * G + lane] = z[i];
+    }
     wave_sync();
   }
   // canonical row index (include/lipmpc.h) of a local row slot / of streamed row t
-  auto ci_of = [&](int i) -> int {
-    if (i == R_RU) return 4 * a + c;
-    if (i == R_RL) return 4 * a + 2 + c;
-    if (i == R_VU) return 5 * N + 4 * a + c;
-    if (i == R_VL) return 5 * N + 4 * a + 2 + c;
-    if (i == R_M) return 4 * N + a;
-    return 9 * N + (a + 1) * P.n_obs + perm[2 * (i - R_CBF) + c];
-  };
-  auto ci_s = [&](int t) -> int { return 9 * N + (a + 1) * P.n_obs + perm[2 * t + c]; };
+  const CanonicalRows ci_of{a, c, N, P, perm};
+  auto ci_s = [&](int t) -> int { return ci_of.ldcbf(t); };
 
   // diagnostics: identification margin min |log(z/(1e5 s))| and final mu of the interior-point phase;
   // initial working set z > 1e5 s

@@ -142,6 +142,7 @@ class LidarSensor:
             raise ValueError("solver and sensor must share n_obs_max, v_max and the device")
         B = solver._check_inputs(state, goal, first_foot, None, None, delta, need_obstacles=False)
         _check(bounds, (B, 4), torch.float64, self.device, "bounds")
+        solver._check_warm(B)
         if sen is None:
             sen = self.alloc_outputs(B, rings=False, c_eta=True)
         if out is None:
@@ -232,14 +233,18 @@ class UnknownEnvFleet:
     HumanoidMPCUnknownEnvironment.py:30-68) for a whole batch and without a host round trip per sample — scan, step
     solve and state advance are enqueued back to back; with ``use_graph`` one sample is captured in a HIP graph and
     replayed.  One MPC solve per sample (sampling_time = DELTA_T), the reference's stop rule (previous objective <
-    0.05) and stop-on-failed-solve per robot."""
+    0.05) and stop-on-failed-solve per robot.  ``warm_start=True``: every solve starts from the robot's previous step,
+    shifted by one stage (the reference's seeding, HumanoidMpc.py:448-455), through a warm-start record per robot that each
+    run zeroes before its first sample (N >= 2, at most 14 obstacle slots)."""
 
     def __init__(self, env_rings, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
-                 exact=False, interior_tol=1e-6, device=None):
-        from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR
+                 exact=False, interior_tol=1e-6, device=None, warm_start=False):
+        from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR, FLAG_WARM_START
         self.sensor = LidarSensor(env_rings, lidar_range, resolution, n_obs_max, v_max, device)
+        self.warm_start = bool(warm_start)
         self.solver = BatchedLipMpc(LipMpcParams(N=N_horizon, n_obs_max=n_obs_max, v_max=v_max,
-                                                 flags=0 if exact else FLAG_INTERIOR, tol_interior=interior_tol),
+                                                 flags=(0 if exact else FLAG_INTERIOR) | (FLAG_WARM_START if warm_start else 0),
+                                                 tol_interior=interior_tol),
                                     self.sensor.device_index)
         self.device = self.sensor.device
 
@@ -251,6 +256,8 @@ class UnknownEnvFleet:
         if pl is not None and pl["key"] == key:
             return pl
         dev, sn, sv = self.device, self.sensor, self.solver
+        if self.warm_start and not sv.set_warm_start(B):      # (outside any capture; grow-only)
+            raise ValueError("warm_start: the warm-start record needs N >= 2 and at most 14 obstacle slots")
         f64 = dict(dtype=torch.float64, device=dev)
         fl = dict(state=torch.zeros((B, 5), **f64), first_foot=torch.ones((B,), dtype=torch.int8, device=dev),
                   walking=torch.ones((B,), dtype=torch.int8, device=dev), last_obj=torch.zeros((B,), **f64),
@@ -291,6 +298,7 @@ class UnknownEnvFleet:
             for n in ("n_steps", "last_status", "n_overflow", "sample"):
                 fl[n].zero_()
             fl["X_pred"].zero_(); fl["U_pred"].zero_(); fl["X_pred"][:, 0] = state0
+            sv.reset_warm_start()                            # every run starts cold (no-op without a record)
             if gen is not None:
                 gen.manual_seed(int(noise_seed))
 

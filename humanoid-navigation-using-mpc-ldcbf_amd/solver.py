@@ -14,8 +14,9 @@ from . import _lib
 STATUS_SOLVED, STATUS_MAX_ITER, STATUS_INFEASIBLE, STATUS_DEGENERATE, STATUS_UNCERTIFIED = 0, 1, 2, 3, 4
 STATUS_SENSOR_OVERFLOW = 5     # a scan's clusters did not fit the obstacle slots: not solved (sense_plan_step, plan_step_batch_c_eta(overflow=)), robot stopped (fleet loop)
 FLAG_INTERIOR = 1
-FLAG_WARM_START = 2      # rollout: start every step from the previous step's shifted interior-point result
+FLAG_WARM_START = 2      # start every step from the previous step's shifted interior-point result (rollout; steps: set_warm_start)
 FLAG_NO_PRESOLVE = 4     # keep the LDCBF rows the leg-reach rows make redundant in the solve (include/lipmpc.h)
+_LIPMPC_E_UNSUPPORTED = -2
 
 
 @dataclass
@@ -103,6 +104,51 @@ class BatchedLipMpc:
         self.auto_workspace = True
         self._ws, self._ws_cap = None, 0
         self._split_capable = int(self.lib.lipmpc_workspace_bytes(self._h, 1)) > 0
+        self._warm, self._warm_cap = None, 0
+        self.warm_words = int(self.lib.lipmpc_warm_words(C.byref(cp)))
+
+    def set_warm_start(self, capacity):
+        """Warm-start records for this handle's step launches (lipmpc_set_warm_start): allocates a zeroed
+        [capacity, warm_words] float64 record and registers it.  Every later plan_step_batch / plan_step_batch_c_eta /
+        LidarSensor.sense_plan_step of at most ``capacity`` problems starts problem b from its record, shifted by one stage,
+        and writes its own interior-point result back (word 0 = 1.0 after a SOLVED / UNCERTIFIED step, else 0.0: the next
+        step starts cold).  Needs FLAG_WARM_START (ValueError otherwise).  Returns False, and registers nothing, where the
+        library does not support it (N = 1, more than 14 obstacle slots, N > 8 with more than 4).  Grow-only: a capacity at or below the current
+        one keeps the record; a larger one is refused while a graph is being captured (the graph holds the pointer)."""
+        capacity = int(capacity)
+        if not self.params.flags & FLAG_WARM_START:
+            raise ValueError("set_warm_start needs a handle with FLAG_WARM_START (a warm solve keeps every row)")
+        if capacity <= self._warm_cap:
+            return True
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_warm_start: cannot grow the warm-start record while a graph is being captured")
+        rec = torch.zeros((capacity, self.warm_words), dtype=torch.float64, device=self.device)
+        rc = self.lib.lipmpc_set_warm_start(self._h, _ptr(rec), capacity)
+        if rc == _LIPMPC_E_UNSUPPORTED:
+            return False
+        _lib.check(rc, "lipmpc_set_warm_start")
+        self._warm, self._warm_cap = rec, capacity
+        return True
+
+    @property
+    def warm_record(self):
+        """The registered [capacity, warm_words] warm-start record (include/lipmpc.h: word 0 = 1.0 when it holds a result,
+        then q [2N] and z [num_rows] of the interior-point phase), or None."""
+        return self._warm
+
+    def reset_warm_start(self, mask=None):
+        """Next step of all robots (mask None) or of the robots where ``mask`` [capacity] is true starts cold: zeroes
+        word 0 of their records (respawned robots).  Asynchronous on the current stream."""
+        if self._warm is None:
+            return
+        if mask is None:
+            self._warm[:, 0].zero_()
+        else:
+            self._warm[:, 0].masked_fill_(torch.as_tensor(mask, device=self.device).to(torch.bool), 0.0)
+
+    def _check_warm(self, B):
+        if self._warm is not None and B > self._warm_cap:
+            raise ValueError(f"batch of {B} problems > the warm-start record's capacity {self._warm_cap}")
 
     def set_workspace(self, capacity):
         """Split launch of this handle's step solves (lipmpc_set_workspace): for 32-lane problems (N > 8) in the exact mode
@@ -184,6 +230,7 @@ class BatchedLipMpc:
         else:
             self._check_outputs(out, B)
         self._ensure_workspace(B)
+        self._check_warm(B)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.lipmpc_plan_step_batch(
             self._h, B, _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(obs_xy), _ptr(obs_nv),
@@ -208,6 +255,7 @@ class BatchedLipMpc:
         else:
             self._check_outputs(out, B)
         self._ensure_workspace(B)
+        self._check_warm(B)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.lipmpc_plan_step_batch_c_eta(
             self._h, B, _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(c_eta_in), _ptr(overflow),

@@ -32,7 +32,8 @@ extern "C" {
                                 * 4: lipmpc_plan_step_batch_c_eta takes the producer's overflow flags;
                                 * 5: `active` is the primal tight set of the returned point (LIPMPC_TIGHT_TOL), the finish's
                                 *    working set moves to the new optional output `working`, diag is [B,8],
-                                *    + lipmpc_set_workspace / lipmpc_workspace_bytes */
+                                *    + lipmpc_set_workspace / lipmpc_workspace_bytes;
+                                *    backward-compatible additions since: + lipmpc_set_warm_start / lipmpc_warm_words */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -60,11 +61,15 @@ extern "C" {
 #define LIPMPC_FLAG_INTERIOR 1  /* skip the active-set finish: return the strictly interior
                                    interior-point iterate (what IPOPT hands the reference's loop) */
 
-#define LIPMPC_FLAG_WARM_START 2 /* lipmpc_rollout_batch: every MPC step of a robot's run starts from the previous step's
-                                   interior-point result shifted by one stage (positions; multipliers clipped to [3, 100])
-                                   instead of "stand still", z = 30 -- the reference seeds its next solve with the shifted
-                                   prediction, HumanoidMpc.py:450-455.  Same optimum, fewer iterations (-15..-30 %).
-                                   Ignored for more than 14 obstacle slots and for N = 1. */
+#define LIPMPC_FLAG_WARM_START 2 /* every MPC step of a robot's closed loop starts from the previous step's interior-point
+                                   result shifted by one stage (positions; multipliers clipped to [3, 100]) instead of
+                                   "stand still", z = 30 -- the reference seeds its next solve with the shifted prediction,
+                                   HumanoidMpc.py:450-455.  Same optimum, fewer iterations (-15..-30 %).
+                                   lipmpc_rollout_batch: within the launch.  The step entry points (lipmpc_plan_step_batch,
+                                   _c_eta, lipmpc_sense_plan_step_batch): through the warm-start records of
+                                   lipmpc_set_warm_start; without records every step starts cold (with every row kept).
+                                   Not for more than 14 obstacle slots or N = 1 (the rollout ignores the flag there,
+                                   lipmpc_set_warm_start refuses); records also not for N > 8 with more than 4 slots. */
 #define LIPMPC_FLAG_NO_PRESOLVE 4 /* keep every LDCBF row in the solve.  By default (exact mode, cold start) the rows that the
                                    leg-reach rows make redundant -- obstacle j at stage k with eta_j.(p_0 - c_j) - delta >
                                    k * (largest CoM step the reach rows allow) + 1e-3: never active, never violated -- are
@@ -139,6 +144,7 @@ int64_t lipmpc_active_words(const lipmpc_params* p);
  *  c_eta  [B,n_obs_max,4] (c_x,c_y,eta_x,eta_y) or NULL
  *  bounds [B,4] or NULL: per-problem (V_MAX_x, V_MAX_y, ALPHA, OMEGA_MAX) replacing the handle's values —
  *         the knobs the reference's bounds_tuning sweep mutates in `conf` (bounds_tuning.py:17-26)
+ *  A handle with warm-start records (lipmpc_set_warm_start) starts each problem from its record and writes the record back.
  *  diag   [B,LIPMPC_DIAG_WORDS] or NULL: 0 active-set rounds used, 1 final equality residual of the finish,
  *         2 identification margin min_i |log(z_i/(1e5 s_i))| of the interior-point phase, 3 certificate margin =
  *         min(smallest multiplier on the working set, smallest slack outside it): ~0 flags a weakly determined WORKING set,
@@ -163,6 +169,25 @@ int lipmpc_plan_step_batch(lipmpc_handle* h, int64_t B,
  * caller and alive until it is unset (NULL) or the handle destroyed; launches on it must be stream-ordered. */
 int lipmpc_set_schedule(lipmpc_handle* h, int32_t* schedule, int64_t capacity);
 int64_t lipmpc_schedule_words(int64_t B);
+
+/* Optional WARM-START RECORDS for the step entry points (lipmpc_plan_step_batch, _c_eta, lipmpc_sense_plan_step_batch): the
+ * seeding of HumanoidMpc.py:448-455 for loops driven from the host.  Record of problem b = lipmpc_warm_words(p) doubles at
+ * record + b * lipmpc_warm_words(p):
+ *   word 0        1.0 = the rest holds a step result; anything else = no result, start cold (a zeroed record starts cold)
+ *   1 .. 2N       q of the interior-point phase: footstep positions, stage-major (x_0, y_0, x_1, y_1, ...)
+ *   2N+1 ..       z of the interior-point phase in canonical row order (lipmpc_num_rows); rows not in the problem are 0,
+ *                 the constant k = 0 LDCBF rows included
+ * Every step launch of the handle reads problem b's record: word 0 = 1.0 starts the solve from it shifted by one stage (stage
+ * k takes stage k+1's positions and multipliers, the last stage extrapolates; multipliers clipped to [3, 100]), otherwise
+ * cold.  After the solve it writes this step's UNSHIFTED interior-point result back (exact mode: the iterate before the
+ * active-set finish), word 0 = 1.0 if the status is SOLVED or UNCERTIFIED, else 0.0 -- a failed step makes the next one
+ * cold.  Records are indexed by problem, so a schedule (lipmpc_set_schedule) may be set too.  Every row is kept in a warm
+ * solve, which is why the handle must carry LIPMPC_FLAG_WARM_START (else LIPMPC_E_ARG).  LIPMPC_E_UNSUPPORTED for N = 1, for
+ * more than 14 obstacle slots, and for N > 8 with more than 4 obstacle slots.  While records are set, a launch of more than `capacity` problems returns LIPMPC_E_ARG.
+ * `record`: device buffer of capacity * lipmpc_warm_words(p) doubles, zeroed once by the caller, owned by the caller and
+ * alive until unset (NULL or capacity 0) or the handle destroyed; launches that share it must be stream-ordered. */
+int lipmpc_set_warm_start(lipmpc_handle* h, double* record, int64_t capacity);
+int64_t lipmpc_warm_words(const lipmpc_params* p);     /* 1 + 2N + lipmpc_num_rows(p) */
 
 /* Optional workspace for the SPLIT LAUNCH of a handle's step solves.  For 32-lane problems (N > 8) in the exact mode the
  * step kernel holds the solver bodies of 1, 2, 7 and the handle's LDCBF row slots per lane next to each other and a wave
