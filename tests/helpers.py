@@ -1,4 +1,5 @@
 """Shared test helpers (CPU side)."""
+import dataclasses
 import math
 
 import numpy as np
@@ -187,11 +188,12 @@ def crowded_batch(N, n_obs, B, seed):
     return st, goal, foot, xy, nv
 
 
-def closed_loop_problems(N, n_obs, ntraj, steps, seed=0, delta=0.0, fields=None, goal=(10.0, 10.0)):
+def closed_loop_problems(N, n_obs, ntraj, steps, seed=0, delta=0.0, fields=None, goal=(10.0, 10.0), params=None):
     """Yield (state, goal, s0, obstacles, delta) along oracle closed-loop walks from the origin
-    (interior iterates advance the loop), i.e. reachable walking states."""
+    (interior iterates advance the loop), i.e. reachable walking states.  params: an O.Params whose robot
+    constants the walk uses (its N is replaced by ``N``); None = the reference's config."""
     rng = np.random.default_rng(seed)
-    P = O.Params(N=N)
+    P = O.Params(N=N) if params is None else dataclasses.replace(params, N=N)
     A, B = O.lip_matrices(P)
     for t in range(ntraj):
         obs = fields[t] if fields is not None else synthetic_field(rng, n_obs, 0.5, 9.5)
@@ -203,6 +205,157 @@ def closed_loop_problems(N, n_obs, ntraj, steps, seed=0, delta=0.0, fields=None,
             if r["status"] != O.STATUS_SOLVED:
                 break
             st = np.concatenate([A @ st[:4] + B @ r["U"][0], [r["theta"][1]]])
+
+
+# --------------------------------------------------------------------------------------------------------------
+# robot parameters other than the reference's config.yml (tests/test_params_oracle.py, tests/test_params_gpu.py)
+# --------------------------------------------------------------------------------------------------------------
+# LipMpcParams overrides.  The defaults hide whole classes of slips: l_max = -l_min and equal x / y bounds (an axis swap
+# or l_max in place of -l_min gives the same numbers), dt == sampling_time, h_com = 1 (beta = sqrt(g / h_com)).
+PARAM_SETS = {
+    "ref": dict(),                                                        # the defaults, as a control
+    "cfg_alt": dict(l_max=(0.1732, 0.1732), l_min=(-0.1732, -0.1732), alpha=1.44),     # config.yml's commented alternative
+    "asym": dict(l_max=(0.14, 0.08), l_min=(-0.06, -0.12), v_min=(-0.05, 0.05), v_max_xy=(0.7, 0.3), ell=0.08, omega_max=0.6),
+    "dyn": dict(dt=0.3, h_com=0.8, sampling_time=0.1, l_max=(0.12, 0.09), l_min=(-0.08, -0.11)),       # mpc_step = 3
+    # mpc_step = 2; l_max_x = 0.22 so that V_MAX_x stays reachable: v_k <= kappa l_max_x - v_min_x (see test_params_oracle)
+    "tall": dict(dt=0.5, h_com=1.25, g=9.6, sampling_time=0.25, v_max_xy=(1.0, 0.5), alpha=2.0, l_max=(0.22, 0.1)),
+}
+NON_DEFAULT_SETS = tuple(k for k in PARAM_SETS if k != "ref")
+
+# O.Params field <- LipMpcParams field (LipMpcParams.v_max is the vertex-slot count; O.Params.v_max is V_MAX)
+ORACLE_FIELD_MAP = {"N": "N", "dt": "dt", "g": "g", "h_com": "h_com", "alpha": "alpha", "l_max": "l_max", "l_min": "l_min",
+                    "v_min": "v_min", "v_max": "v_max_xy", "omega_max": "omega_max", "ell": "ell",
+                    "sampling_time": "sampling_time", "tol": "tol", "tol_interior": "tol_interior", "max_iter": "max_iter",
+                    "finish_rounds": "finish_rounds", "k0_tol": "k0_tol"}
+ORACLE_FROM_FLAGS = ("presolve", "warm_start")           # O.Params fields that LipMpcParams carries as flags
+HANDLE_ONLY_FIELDS = ("n_obs_max", "v_max", "flags")      # LipMpcParams fields with no O.Params counterpart (slots, flags)
+
+
+def lip_params(name, **kw):
+    """LipMpcParams of the set ``name`` with the handle's own fields (N, n_obs_max, flags, ...) from ``kw``."""
+    import lipmpc
+    return lipmpc.LipMpcParams(**{**PARAM_SETS[name], **kw})
+
+
+def oracle_params(P):
+    """The O.Params of a LipMpcParams: every physical constant and solver knob, presolve / warm start from the flags
+    (FLAG_INTERIOR is the oracle's exact=False, an argument of plan_step, not a parameter)."""
+    import lipmpc
+    kw = {o: getattr(P, f) for o, f in ORACLE_FIELD_MAP.items()}
+    kw = {k: (tuple(v) if isinstance(v, (tuple, list)) else v) for k, v in kw.items()}
+    return O.Params(**kw, presolve=not (P.flags & lipmpc.FLAG_NO_PRESOLVE), warm_start=bool(P.flags & lipmpc.FLAG_WARM_START))
+
+
+# canonical row families of the step problem (O.build_qp_position_form): name -> row indices of a horizon N
+ROW_FAMILIES = ("reach_hi_x", "reach_hi_y", "reach_lo_x", "reach_lo_y", "manoeuvr", "vel_hi_x", "vel_hi_y", "vel_lo_x", "vel_lo_y",
+                "ldcbf")
+
+
+def row_family_rows(N, n_obs):
+    fam = {}
+    for i, f in enumerate(ROW_FAMILIES[:4]):
+        fam[f] = np.arange(N) * 4 + i
+    fam["manoeuvr"] = 4 * N + np.arange(N)
+    for i, f in enumerate(ROW_FAMILIES[5:9]):
+        fam[f] = 5 * N + np.arange(N) * 4 + i
+    fam["ldcbf"] = 9 * N + n_obs + np.arange(N * n_obs)          # stages 1..N (the k = 0 rows are constants of the step)
+    return fam
+
+
+def family_counts(active_bits, N, n_obs):
+    """Problems in which each row family has a tight row: active_bits [B, num_rows] bool."""
+    return {f: int(np.any(active_bits[:, r], axis=1).sum()) for f, r in row_family_rows(N, n_obs).items()}
+
+
+def row_family_batch(name, N, n_obs, B, seed, walk_share=0.25, fail_share=0.05, v_slots=5):
+    """A batch at parameter set ``name`` in which every row family is tight in some problems: robots at any heading with
+    goals ahead, beside and behind them (the reach rows in all four directions, the manoeuvrability row), initial
+    velocities anywhere the first stage can absorb, up to both ends of that range (the walking-velocity rows, and the
+    backward reach row: a robot moving backwards fast must step back as far as it may), small obstacles within reach of the
+    horizon and far away (LDCBF rows, rows the presolve drops), both feet; plus closed_loop_problems walks at the same
+    parameters (``walk_share`` of the batch).  The synthetic states are drawn in surplus and screened with the C oracle:
+    all but ``fail_share`` of them are problems it solves, the rest failures (failure codes stay in play).
+    Returns dict(state [B,5], goal [B,2], foot [B] int8, xy [B,n_obs,v_slots,2], nv [B,n_obs] int32, delta [B]) and
+    ``rings(b)``, the obstacle list of problem b."""
+    import c_oracle
+    LP = lip_params(name, N=N, n_obs_max=n_obs, v_max=v_slots)
+    P = oracle_params(LP)
+    rng = np.random.default_rng(seed)
+    n_walk = int(round(walk_share * B))
+    st = np.zeros((B, 5)); goal = np.zeros((B, 2)); foot = np.ones(B, np.int8); delta = np.zeros(B)
+    xy = np.zeros((B, n_obs, v_slots, 2)); nv = np.zeros((B, n_obs), np.int32)
+    b = 0
+    if n_walk:
+        walks = closed_loop_problems(N, n_obs, 10 ** 6, 14, seed=seed + 1, params=P, goal=(9.0, 7.5))
+        while b < n_walk:
+            s, g, s0, obs, d = next(walks)
+            st[b], goal[b], foot[b], delta[b] = s, g, s0, d
+            for j, r in enumerate(obs):
+                xy[b, j, : len(r)] = r; nv[b, j] = len(r)
+            b += 1
+    # synthetic part, drawn in surplus until the screen has passed enough
+    step, kap = O.reach_step(P), P.kappa
+    lo, hi = np.array(P.v_min, float), np.array(P.v_max, float)
+    # robot-frame initial velocity: v_1 = -v_0 + kappa (p_1 - p_0) must reach [v_min, v_max], so v_0 may lie anywhere in
+    # [kappa l_min - v_max, kappa l_max - v_min] (longitudinal; lateral likewise, the foot offset aside)
+    span_x = (kap * P.l_min[0] - hi[0], kap * P.l_max[0] - lo[0])
+    span_y = (kap * (P.l_min[1] - P.ell) - hi[1], kap * (P.l_max[1] + P.ell) + hi[1])
+    need, n_fail = B - n_walk, int(round(fail_share * (B - n_walk)))
+    keep_ok, keep_fail = [], []
+    for _round in range(12):
+        M = 2 * need
+        cst = np.zeros((M, 5)); cgoal = np.zeros((M, 2)); cfoot = np.ones(M, np.int8); cdelta = np.zeros(M)
+        cxy = np.zeros((M, n_obs, v_slots, 2)); cnv = np.zeros((M, n_obs), np.int32)
+        for i in range(M):
+            p0 = rng.uniform(2.0, 8.0, 2)
+            th = rng.uniform(-np.pi, np.pi)
+            s0 = 1 if rng.random() < 0.5 else -1
+            kind = rng.integers(0, 5)
+            v_loc = np.array([rng.uniform(lo[0], hi[0]), rng.uniform(-hi[1], hi[1])])
+            if kind == 1:
+                v_loc[0] = rng.uniform(*span_x)
+            elif kind == 2:
+                v_loc[0] = rng.uniform(span_x[0], 0.3 * span_x[0])
+            elif kind == 3:
+                v_loc[1] = rng.uniform(*span_y) * (1 if rng.random() < 0.5 else -1)
+            elif kind == 4:     # moving backwards, goal (straight) ahead: the first stage runs into V_MAX / the manoeuvrability row
+                v_loc[0] = rng.uniform(span_x[0], 0.0)
+            c, s = np.cos(th), np.sin(th)
+            cst[i] = [p0[0], c * v_loc[0] - s * v_loc[1], p0[1], s * v_loc[0] + c * v_loc[1], th]
+            cfoot[i] = s0
+            rel = rng.choice([0.0, np.pi / 2, -np.pi / 2, np.pi, rng.uniform(-np.pi, np.pi)])     # ahead, beside, behind, anywhere
+            dist = rng.uniform(0.05, 1.0) if rng.random() < 0.3 else rng.uniform(1.0, 7.0)
+            if kind == 4:
+                rel, dist = (0.0 if rng.random() < 0.5 else rng.uniform(-0.5, 0.5)), rng.uniform(2.0, 7.0)
+            cgoal[i] = p0 + dist * np.array([np.cos(th + rel), np.sin(th + rel)])
+            # obstacles: a few small triangles within reach of the horizon, the rest beyond it, in random slots
+            near = rng.integers(0, min(n_obs, 4) + 1) if n_obs else 0
+            for j in range(n_obs):
+                rad = rng.uniform(0.25, max(0.3, 0.8 * step * N)) if j < near else rng.uniform(step * N + 1.0, step * N + 6.0)
+                ang = th + rng.uniform(-1.2, 1.2) if (j < near and rng.random() < 0.6) else rng.uniform(0, 2 * np.pi)
+                cc = p0 + rad * np.array([np.cos(ang), np.sin(ang)])
+                a0 = rng.uniform(0, 2 * np.pi)
+                cxy[i, j, :3] = cc + 0.08 * np.array([[np.cos(a0 + t), np.sin(a0 + t)] for t in (0.0, 2.1, 4.2)])   # CCW triangle
+                cnv[i, j] = 3
+            if n_obs:
+                perm = rng.permutation(n_obs)
+                cxy[i], cnv[i] = cxy[i, perm], cnv[i, perm]
+            cdelta[i] = rng.choice([0.0, 0.0, 0.05])
+        r = c_oracle.plan_step_batch(LP, cst, cgoal, cfoot, cxy if n_obs else None, cnv if n_obs else None, cdelta, n_threads=8)
+        solved = np.isin(r["status"], (O.STATUS_SOLVED, O.STATUS_UNCERTIFIED))
+        cand = (cst, cgoal, cfoot, cdelta, cxy, cnv)
+        keep_ok += [tuple(a[i] for a in cand) for i in np.where(solved)[0]]
+        keep_fail += [tuple(a[i] for a in cand) for i in np.where(~solved)[0]]
+        if len(keep_ok) >= need - n_fail and len(keep_fail) >= n_fail:
+            break
+    take = keep_fail[:n_fail] + keep_ok[: need - len(keep_fail[:n_fail])]
+    assert len(take) == need, (name, N, n_obs, len(keep_ok), len(keep_fail))
+    order = rng.permutation(need)                           # failures anywhere in the batch
+    for i, t in zip(range(n_walk, B), (take[o] for o in order)):
+        st[i], goal[i], foot[i], delta[i], xy[i], nv[i] = t
+    out = dict(state=st, goal=goal, foot=foot, xy=xy, nv=nv, delta=delta)
+    out["rings"] = lambda i: [xy[i, j, : nv[i, j]] for j in range(n_obs) if nv[i, j] > 0]
+    return out
 
 
 # --------------------------------------------------------------------------------------------------------------
