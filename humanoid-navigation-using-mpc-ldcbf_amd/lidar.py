@@ -136,7 +136,10 @@ class LidarSensor:
         """One MPC step of the unknown-environment variant in one C call (lipmpc_sense_plan_step_batch): scan + constraint
         assembly, then ``solver``'s step against the assembled half-spaces.  ``solver``: a BatchedLipMpc whose
         n_obs_max / v_max are this sensor's.  Returns (sen, out) as ``sense(..., c_eta=True, rings=False)`` and
-        ``plan_step_batch_c_eta`` would."""
+        ``plan_step_batch_c_eta`` would -- the same bits, whatever the solver served before: the step takes the split launch
+        with the workspace of the current stream exactly as ``plan_step_batch_c_eta`` does (streams and graphs: as
+        ``BatchedLipMpc.plan_step_batch``).  A ``schedule`` buffer, like the solver's schedule and warm-start records, is
+        shared by every launch it is given to: those must be ordered on one stream."""
         P = solver.params
         if P.n_obs_max != self.n_obs_max or P.v_max != self.v_max or solver.device != self.device:
             raise ValueError("solver and sensor must share n_obs_max, v_max and the device")
@@ -155,6 +158,7 @@ class LidarSensor:
         if schedule is not None and (schedule.dtype != torch.int32 or schedule.device != self.device or not schedule.is_contiguous()
                                      or schedule.numel() != int(self.lib.lipmpc_lidar_schedule_words(B))):
             raise ValueError("schedule: a buffer of make_schedule(B) for this B")
+        solver._ensure_workspace(B)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.lipmpc_sense_plan_step_batch(
             solver._h, B, self.resolution, self.n_env, self.v_env, 1, self.lidar_range, DBSCAN_EPS, DBSCAN_MIN_SAMPLES,

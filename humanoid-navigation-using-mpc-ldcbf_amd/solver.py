@@ -102,7 +102,10 @@ class BatchedLipMpc:
         _lib.check(self.lib.lipmpc_create(C.byref(cp), self.device_index, C.byref(self._h)), "lipmpc_create")
         # split launch (one kernel per solver body): the library says whether this handle's steps can use it
         self.auto_workspace = True
-        self._ws, self._ws_cap = None, 0
+        self._ws, self._ws_cap = None, 0           # the workspace registered last
+        self._ws_by_stream = {}                    # stream -> (workspace, capacity) of the eager launches on it: grow-only
+        self._kept = []                            # every buffer ever registered with the library (a captured graph may hold it)
+        self._side_streams = False                 # the library made its side streams / events (first workspace registered)
         self._split_capable = int(self.lib.lipmpc_workspace_bytes(self._h, 1)) > 0
         self._warm, self._warm_cap = None, 0
         self.warm_words = int(self.lib.lipmpc_warm_words(C.byref(cp)))
@@ -154,26 +157,68 @@ class BatchedLipMpc:
         """Split launch of this handle's step solves (lipmpc_set_workspace): for 32-lane problems (N > 8) in the exact mode
         the step runs as classification -> index lists -> one kernel per solver body (each with its own register
         allocation); same optimum and active sets as the single kernel, a status may differ only between SOLVED and UNCERTIFIED
-        (a problem may run in another body there: last-bit differences).  The handle sets one up by itself for the batch sizes it sees
-        (``auto_workspace``); 0 = back to the single dispatching kernel."""
+        (a problem may run in another body there: last-bit differences).  The workspace holds one launch's class keys and
+        lists, so two launches must never share one unless they are ordered.
+        By default (``auto_workspace``) the handle manages this itself and this call is not needed: every step launch
+        registers, right before its C call, a workspace of its own stream (grow-only per stream), and a launch being captured
+        in a graph gets one of its own that no other launch or graph uses -- launches on different streams, graph replays and
+        eager launches may then overlap freely (they share the handle's side streams, which only orders them).
+        An explicit call registers ONE workspace of ``capacity`` problems (0 = back to the single dispatching kernel); with
+        ``auto_workspace = False`` it stays registered, and the caller takes over the C contract: every step launch of the handle
+        uses it, on any stream, so all of them -- graph replays included -- must be ordered on one stream.  Buffers the handle
+        has registered are never freed while it lives (a captured graph may hold them); keep the handle alive as long as its
+        graphs are replayed.  Refused (RuntimeError) while a graph is being captured before the handle's first workspace: the
+        first one makes the handle's side streams and events."""
         capacity = int(capacity)
+        ws = self._new_workspace(capacity)
+        self._register_workspace(ws, capacity)
+
+    def _new_workspace(self, capacity):
+        """A workspace buffer of ``capacity`` problems that the handle keeps for its lifetime, or None (not split-capable)."""
         nbytes = int(self.lib.lipmpc_workspace_bytes(self._h, capacity)) if capacity > 0 else 0
-        self._ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=self.device) if nbytes > 0 else None
-        self._ws_cap = capacity if self._ws is not None else 0
-        _lib.check(self.lib.lipmpc_set_workspace(self._h, _ptr(self._ws), self._ws_cap), "lipmpc_set_workspace")
+        if nbytes <= 0:
+            return None
+        if not self._side_streams and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the first split launch (workspace) of a handle makes its side streams and events, which cannot "
+                               "happen during a graph capture: run one step of the handle, or set_workspace, before capturing")
+        ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=self.device)
+        self._kept.append(ws)
+        return ws
+
+    def _register_workspace(self, ws, capacity):
+        cap = capacity if ws is not None else 0
+        _lib.check(self.lib.lipmpc_set_workspace(self._h, _ptr(ws), cap), "lipmpc_set_workspace")
+        self._ws, self._ws_cap = ws, cap
+        self._side_streams = self._side_streams or ws is not None
 
     def _ensure_workspace(self, B):
-        if self.auto_workspace and B > getattr(self, "_ws_cap", 0) and self._split_capable:
-            self.set_workspace(B)
+        """Right before a step's C call (auto_workspace): register the workspace of the current stream, grown to B if needed,
+        or, while a graph is being captured, a new one that belongs to this captured launch alone."""
+        if not (self.auto_workspace and self._split_capable) or B < 1:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            self._register_workspace(self._new_workspace(B), B)
+            return
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws, cap = self._ws_by_stream.get(key, (None, 0))
+        if B > cap:
+            ws, cap = self._new_workspace(B), B
+            self._ws_by_stream[key] = (ws, cap)
+        self._register_workspace(ws, cap)
 
     def set_schedule(self, capacity):
         """Launch order for this handle's step solves (lipmpc_set_schedule): every plan_step_batch / plan_step_batch_c_eta of
         at most ``capacity`` problems leaves each problem's cost and the order -- costliest first, like with like -- the
         next launch of the same batch size places them in.  Pays off beyond the 4096 problems the GPU holds at once,
-        when consecutive launches see the same or slowly moving problems; results never depend on it.  0 = off."""
+        when consecutive launches see the same or slowly moving problems; results never depend on it.  0 = off.
+        One buffer for every launch of the handle, on any stream: launches with a schedule -- graph replays included -- must be
+        ordered on one stream (the caller's to order, unlike the workspace).  A replaced buffer is kept while the handle lives
+        (a graph captured with it still writes there)."""
         capacity = int(capacity)
         self._sched = (torch.zeros((int(self.lib.lipmpc_schedule_words(capacity)),), dtype=torch.int32, device=self.device)
                        if capacity > 0 else None)
+        if self._sched is not None:
+            self._kept.append(self._sched)
         _lib.check(self.lib.lipmpc_set_schedule(self._h, _ptr(self._sched), capacity), "lipmpc_set_schedule")
 
     def __del__(self):
@@ -222,7 +267,13 @@ class BatchedLipMpc:
         bounds [B,4] (V_MAX_x, V_MAX_y, ALPHA, OMEGA_MAX) per problem or None.
         Returns dict(U,X,theta,omega,obj,status,iters,active[,c_eta][,diag][,working]) of device tensors; results are
         valid once the current stream is synchronised.  ``active`` = the rows tight at the optimum (slack <= 1e-7: unique),
-        ``working`` = the rows carrying a multiplier in the finish's certificate (include/lipmpc.h)."""
+        ``working`` = the rows carrying a multiplier in the finish's certificate (include/lipmpc.h).
+        Streams and graphs: launches of one handle on different streams need no ordering between them, and a step may be
+        captured in a graph and replayed next to eager launches -- the split launch's workspace is per stream, and per captured
+        launch (set_workspace; not with ``auto_workspace = False``).  The first split launch of a handle cannot be captured
+        (RuntimeError, nothing enqueued): run one eagerly first.  What the caller orders: the schedule (set_schedule) and the
+        warm-start records (set_warm_start) are one buffer per handle, so launches that use them must be ordered on one stream;
+        inputs and outputs are the caller's as usual."""
         B = self._check_inputs(state, goal, first_foot, obs_xy, obs_nv, delta)
         _check(bounds, (B, 4), torch.float64, self.device, "bounds")
         if out is None:
@@ -245,7 +296,7 @@ class BatchedLipMpc:
         This is what a subclass overriding the reference's _get_list_c_and_eta / _compute_single_lcbf hooks feeds.
         overflow [B] int32 or None: the flags of whoever produced the rows (LidarSensor.sense: the scan's clusters did not fit
         the obstacle slots); a flagged problem is not solved against its truncated list: status STATUS_SENSOR_OVERFLOW, NaN
-        outputs (advance() leaves the robot where it is)."""
+        outputs (advance() leaves the robot where it is).  Streams and graphs: as plan_step_batch."""
         B = self._check_inputs(state, goal, first_foot, None, None, delta, need_obstacles=False)
         _check(c_eta_in, (B, self.params.n_obs_max, 4), torch.float64, self.device, "c_eta_in", required=True)
         _check(bounds, (B, 4), torch.float64, self.device, "bounds")

@@ -202,8 +202,11 @@ int64_t lipmpc_warm_words(const lipmpc_params* p);     /* 1 + 2N + lipmpc_num_ro
  * N <= 8, for the flags that keep every row, and for batches larger than the workspace was sized for.  While it is set,
  * the order of lipmpc_set_schedule is not applied (the costs are still left).
  * `workspace`: device buffer of lipmpc_workspace_bytes(h, capacity) bytes, contents arbitrary, owned by the caller, alive
- * until unset (NULL) or the handle is destroyed.  The workspace, like the handle's side streams and events, is shared by
- * every launch of the handle: all step launches of a handle that has one must be stream-ordered. */
+ * until unset (NULL) or the handle is destroyed.  The workspace is shared by every launch made while it is registered: step
+ * launches on one workspace must be stream-ordered.  Once the handle's side streams exist (the first workspace makes them:
+ * not during a graph capture) this call only swaps a pointer, so a caller may register another workspace right before each
+ * launch -- one per stream, one per captured launch -- and launches on different workspaces may then overlap (the side
+ * streams and events they share only order them).  A graph keeps the pointer it was captured with. */
 int64_t lipmpc_workspace_bytes(const lipmpc_handle* h, int64_t capacity);
 int lipmpc_set_workspace(lipmpc_handle* h, void* workspace, int64_t capacity);
 
