@@ -7,6 +7,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblipmpc.so")
 
 
+class LipmpcRrtParamsC(C.Structure):
+    """struct lipmpc_rrt_params (include/lipmpc.h)"""
+    _fields_ = [("width", C.c_int32), ("n_samples", C.c_int32), ("r_rewire", C.c_int32), ("max_cells", C.c_int32),
+                ("margin", C.c_double)]
+
+
 class LipmpcParamsC(C.Structure):
     """struct lipmpc_params (include/lipmpc.h)"""
     _fields_ = [
@@ -23,6 +29,7 @@ class LipmpcParamsC(C.Structure):
 EXPORTS = ("lipmpc_default_params", "lipmpc_create", "lipmpc_destroy", "lipmpc_num_rows",
            "lipmpc_active_words", "lipmpc_plan_step_batch", "lipmpc_plan_step_batch_c_eta", "lipmpc_advance_batch", "lipmpc_fleet_update_batch", "lipmpc_rollout_batch", "lipmpc_lidar_sense_batch", "lipmpc_lidar_c_eta_batch", "lipmpc_lidar_schedule_words", "lipmpc_sense_plan_step_batch", "lipmpc_set_schedule", "lipmpc_schedule_words", "lipmpc_set_workspace", "lipmpc_workspace_bytes",
            "lipmpc_set_warm_start", "lipmpc_warm_words",
+           "lipmpc_rrt_default_params", "lipmpc_rrt_workspace_bytes", "lipmpc_rrt_plan_batch",
            "lipmpc_strerror", "lipmpc_version")
 
 ABI_VERSION = 5          # LIPMPC_ABI_VERSION of include/lipmpc.h this binding is written for
@@ -99,6 +106,13 @@ def load():
     lib.lipmpc_set_warm_start.restype = i32
     lib.lipmpc_warm_words.argtypes = [C.POINTER(LipmpcParamsC)]
     lib.lipmpc_warm_words.restype = i64
+    lib.lipmpc_rrt_default_params.argtypes = [C.POINTER(LipmpcRrtParamsC)]
+    lib.lipmpc_rrt_default_params.restype = i32
+    lib.lipmpc_rrt_workspace_bytes.argtypes = [C.POINTER(LipmpcRrtParamsC), i64]
+    lib.lipmpc_rrt_workspace_bytes.restype = i64
+    lib.lipmpc_rrt_plan_batch.argtypes = ([i32, C.POINTER(LipmpcRrtParamsC), i64, vp, vp, C.c_int32, C.c_int32]
+                                          + [vp] * 12 + [C.c_int32, vp])
+    lib.lipmpc_rrt_plan_batch.restype = i32
     lib.lipmpc_strerror.argtypes = [i32]
     lib.lipmpc_strerror.restype = C.c_char_p
     lib.lipmpc_version.argtypes = []

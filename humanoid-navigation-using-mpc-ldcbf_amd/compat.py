@@ -304,15 +304,15 @@ class HumanoidMPCCustomLCBF(HumanoidMPC):
 class HumanoidMPCWithRRT(HumanoidMPC):
     """Reach the goal through a sequence of sub-goals (HumanoidMPCVariants/HumanoidMPCWithRRT.py:15-183).
 
-    The reference obtains the sub-goals from ``rrtplanner.RRTStar`` on an occupancy grid (:98-138) — sequential,
-    CPU-side planning that is outside the accelerated path (and ``rrtplanner`` is not installed here).  What belongs
-    to the MPC path is the hand-off (:155-181), mirrored exactly: one fresh ``HumanoidMPC`` per sub-goal with the
-    parent's horizon / sample count / sampling time / first foot, started from the last state of the previous run,
-    X_pred / U_pred concatenated as they come (the hand-off state appears twice, as there).  Like the reference
+    The reference obtains the sub-goals from ``rrtplanner.RRTStar`` on an occupancy grid (:98-138); this library's
+    counterpart is ``RrtStarPlanner`` (planner.py: the same grid, distance transform and cost, its own sampler), passed
+    as ``planner=lipmpc.RrtStarPlanner()``.  The hand-off (:155-181) is mirrored exactly: one fresh ``HumanoidMPC`` per
+    sub-goal with the parent's horizon / sample count / sampling time / first foot, started from the last state of the
+    previous run, X_pred / U_pred concatenated as they come (the hand-off state appears twice, as there).  Like the reference
     (:155) the first run starts from (0, 0, 0, 0, 0) whatever ``init_state`` says unless ``honour_init_state=True``.
 
     Sub-goals come from ``sub_goals`` ([S,2], the last one normally the goal), or from ``planner(self) -> [S,2]``.
-    With neither, ``run_simulation`` raises ImportError: there is no built-in planner.
+    With neither, ``run_simulation`` raises ImportError: the planner is not chosen implicitly.
     """
 
     def __init__(self, goal, obstacles, N_horizon=3, N_mpc_timesteps=100, sampling_time=1e-3,
@@ -335,7 +335,7 @@ class HumanoidMPCWithRRT(HumanoidMPC):
             sub_goals = np.asarray(self.planner(self), float).reshape(-1, 2)
         else:
             raise ImportError("HumanoidMPCWithRRT: no planner available (rrtplanner is not part of this library); "
-                              "pass sub_goals=[[x, y], ...] or planner=callable")
+                              "pass sub_goals=[[x, y], ...] or planner=callable, e.g. planner=lipmpc.RrtStarPlanner()")
         X_glob, U_glob = None, None
         start_state = tuple(self.init_state) if self.honour_init_state else (0, 0, 0, 0, 0)
         animator = initial_animator

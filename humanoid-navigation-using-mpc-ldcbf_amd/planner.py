@@ -1,0 +1,147 @@
+"""Batched RRT* sub-goal planner on the device: the global planner of the reference's HumanoidMPCWithRRT
+(HumanoidMPCVariants/HumanoidMPCWithRRT.py:21-135) as ``lipmpc_rrt_plan_batch`` (include/lipmpc.h).
+
+``RrtStarPlanner.plan_batch`` plans B problems in one call and returns ``sub_goals [B,S_max,2]`` / ``n_sub [B]`` in the form
+``BatchedLipMpc.rollout_subgoals`` takes them; an instance is also the ``planner=`` of ``HumanoidMPCWithRRT``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .solver import pack_rings
+
+RRT_FOUND, RRT_NO_PATH, RRT_START_OCCUPIED, RRT_GOAL_OCCUPIED, RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, \
+    RRT_PATH_OVERFLOW = range(7)
+RRT_STATUS_NAMES = ("FOUND", "NO_PATH", "START_OCCUPIED", "GOAL_OCCUPIED", "GRID_TOO_LARGE", "NO_OBSTACLE_GRID",
+                    "PATH_OVERFLOW")
+
+
+def _ptr(t):
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+class RrtStarPlanner:
+    """RRT* on the occupancy grid of the obstacles, cost vcost[v] + C[x] |p_v - x| with C = exp(-distance to the nearest
+    obstacle) (HumanoidMPCWithRRT.py:98-135).  ``width_grid_size``, ``n`` and ``r_rewire`` are the reference's arguments
+    (250, 1500, 80); ``seed`` is the default seed of every problem.  The sampler is this library's (splitmix64, see
+    include/lipmpc.h): ``rrtplanner``'s own tree is not reproduced."""
+
+    def __init__(self, width_grid_size: int = 250, n: int = 1500, r_rewire: int = 80, seed: int = 1,
+                 device: int | None = None, *, margin: float = 3.0, max_cells: int | None = None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("lipmpc needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
+        self.lib = _lib.load()
+        p = _lib.LipmpcRrtParamsC()
+        _lib.check(self.lib.lipmpc_rrt_default_params(C.byref(p)), "lipmpc_rrt_default_params")
+        p.width, p.n_samples, p.r_rewire, p.margin = int(width_grid_size), int(n), int(r_rewire), float(margin)
+        if max_cells is not None:
+            p.max_cells = int(max_cells)
+        if self.lib.lipmpc_rrt_workspace_bytes(C.byref(p), 1) < 0:
+            raise ValueError(f"invalid RRT* parameters (width {p.width}, n {p.n_samples}, r_rewire {p.r_rewire}, "
+                             f"max_cells {p.max_cells}, margin {p.margin})")
+        self.params = p
+        self.seed = int(seed)
+        self.device_index = torch.cuda.current_device() if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index)
+        self._ws, self._ws_cap = None, 0
+        self.last = None            # outputs of the last plan_batch
+
+    @property
+    def max_cells(self):
+        return int(self.params.max_cells)
+
+    def _workspace(self, B):
+        if B > self._ws_cap:
+            nbytes = int(self.lib.lipmpc_rrt_workspace_bytes(C.byref(self.params), B))
+            self._ws, self._ws_cap = torch.empty((nbytes,), dtype=torch.uint8, device=self.device), B
+        return self._ws
+
+    def _dev(self, a, dt):
+        if a is None:
+            return None
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=dt).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=self.device)
+
+    def plan_batch(self, goal, obs_xy=None, obs_nv=None, start=None, seeds=None, S_max: int | None = None,
+                   with_tree: bool = False, with_grids: bool = False):
+        """Plan B problems.  goal [B,2]; obs_xy [B,n_obs_max,v_max,2] / obs_nv [B,n_obs_max] as ``pack_rings`` gives them;
+        start [B,2] or None (= the origin, as the reference); seeds [B] (int64 / uint64 bit patterns), one int for every
+        problem, or None (= the planner's seed).  S_max: sub-goal slots per problem (default n + 1, always enough).
+        Returns dict(sub_goals [B,S_max,2] (rows past n_sub are 0), n_sub [B], status [B] (RRT_*), path_cost [B]) as
+        device tensors; with_tree adds tree [B,n+2,4], with_grids grid_dims [B,2], occ_d2 [B,max_cells] (squared
+        distance, 0 = occupied) and cost_grid [B,max_cells] (layouts: lipmpc_rrt_plan_batch, include/lipmpc.h)."""
+        goal = self._dev(goal, torch.float64)
+        if goal is None or goal.dim() != 2 or goal.shape[1] != 2:
+            raise ValueError("goal must be [B,2]")
+        B = goal.shape[0]
+        xy, nv = self._dev(obs_xy, torch.float64), self._dev(obs_nv, torch.int32)
+        if (xy is None) != (nv is None):
+            raise ValueError("obs_xy and obs_nv go together")
+        n_obs, v_max = (0, 3) if xy is None else (int(xy.shape[1]), int(xy.shape[2]))
+        if xy is not None and (tuple(xy.shape) != (B, n_obs, v_max, 2) or tuple(nv.shape) != (B, n_obs)):
+            raise ValueError(f"obs_xy must be [B,n_obs_max,v_max,2] and obs_nv [B,n_obs_max] with B = {B}")
+        st = self._dev(start, torch.float64)
+        if st is not None and tuple(st.shape) != (B, 2):
+            raise ValueError("start must be [B,2] or None")
+        if seeds is None or np.isscalar(seeds):
+            sd = np.full(B, self.seed if seeds is None else int(seeds), dtype=np.uint64)
+        else:
+            if isinstance(seeds, torch.Tensor):
+                seeds = seeds.cpu().numpy()
+            vals = seeds.reshape(-1).tolist() if isinstance(seeds, np.ndarray) else list(seeds)   # (a list of Python
+            sd = np.asarray([int(s) & ((1 << 64) - 1) for s in vals], dtype=np.uint64)        # ints may not fit int64)
+            if sd.shape[0] != B:
+                raise ValueError("seeds must have B entries")
+        seeds_d = torch.as_tensor(sd.view(np.int64), device=self.device)
+        S_max = int(self.params.n_samples) + 1 if S_max is None else int(S_max)
+        dev = self.device
+        out = dict(sub_goals=torch.zeros((B, S_max, 2), dtype=torch.float64, device=dev),
+                   n_sub=torch.zeros((B,), dtype=torch.int32, device=dev),
+                   status=torch.zeros((B,), dtype=torch.int32, device=dev),
+                   path_cost=torch.zeros((B,), dtype=torch.float64, device=dev))
+        if with_grids:
+            out.update(grid_dims=torch.zeros((B, 2), dtype=torch.int32, device=dev),
+                       occ_d2=torch.zeros((B, self.max_cells), dtype=torch.int32, device=dev),
+                       cost_grid=torch.zeros((B, self.max_cells), dtype=torch.float64, device=dev))
+        if with_tree:
+            out["tree"] = torch.zeros((B, int(self.params.n_samples) + 2, 4), dtype=torch.float64, device=dev)
+        if B == 0:
+            return out
+        ws = self._workspace(B)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lipmpc_rrt_plan_batch(
+            self.device_index, C.byref(self.params), B, _ptr(xy), _ptr(nv), n_obs, v_max, _ptr(st), _ptr(goal),
+            _ptr(seeds_d), _ptr(ws), _ptr(out["sub_goals"]), _ptr(out["n_sub"]), _ptr(out["status"]),
+            _ptr(out["path_cost"]), _ptr(out.get("grid_dims")), _ptr(out.get("occ_d2")), _ptr(out.get("cost_grid")),
+            _ptr(out.get("tree")), S_max, C.c_void_p(stream))
+        _lib.check(rc, "lipmpc_rrt_plan_batch")
+        self.last = out
+        return out
+
+    def plan(self, goal, rings, start=None, seed=None, S_max=None, with_tree=False, with_grids=False):
+        """One problem from a list of (V,2) rings (any V >= 1)."""
+        v_max = max([3] + [len(r) for r in rings])
+        xy, nv = pack_rings([list(rings)], max(1, len(rings)), v_max)
+        return self.plan_batch(np.asarray(goal, float).reshape(1, 2), xy, nv,
+                               None if start is None else np.asarray(start, float).reshape(1, 2),
+                               None if seed is None else [seed], S_max, with_tree, with_grids)
+
+    def __call__(self, mpc):
+        """planner= of HumanoidMPCWithRRT: the sub-goals [S,2] from the controller's obstacles and goal, starting at the
+        origin as the reference does (:105, :155), or at init_state with honour_init_state=True.  Raises RuntimeError
+        unless a path is found."""
+        from .compat import _ring_of
+        rings = [_ring_of(o) for o in mpc.obstacles]
+        start = None
+        if getattr(mpc, "honour_init_state", False):
+            start = (float(mpc.init_state[0]), float(mpc.init_state[2]))
+        out = self.plan(mpc.goal, rings, start)
+        st, n = int(out["status"][0]), int(out["n_sub"][0])
+        if st != RRT_FOUND:
+            raise RuntimeError(f"RrtStarPlanner: no sub-goals ({RRT_STATUS_NAMES[st]})")
+        return out["sub_goals"][0, :n].cpu().numpy()

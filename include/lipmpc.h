@@ -33,7 +33,8 @@ extern "C" {
                                 * 5: `active` is the primal tight set of the returned point (LIPMPC_TIGHT_TOL), the finish's
                                 *    working set moves to the new optional output `working`, diag is [B,8],
                                 *    + lipmpc_set_workspace / lipmpc_workspace_bytes;
-                                *    backward-compatible additions since: + lipmpc_set_warm_start / lipmpc_warm_words */
+                                *    backward-compatible additions since: + lipmpc_set_warm_start / lipmpc_warm_words;
+                                *    + lipmpc_rrt_default_params / lipmpc_rrt_workspace_bytes / lipmpc_rrt_plan_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -337,6 +338,67 @@ int lipmpc_sense_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resolution
                                  double* U, double* X, double* theta, double* omega, double* obj, int32_t* status,
                                  int32_t* iters, uint64_t* active, uint64_t* working, double* diag, const double* bounds,
                                  void* hip_stream);
+
+/* RRT* SUB-GOAL PLANNER (backward-compatible addition): the global planner of HumanoidMPCWithRRT
+ * (HumanoidMPCVariants/HumanoidMPCWithRRT.py:21-135) for B independent problems, one workgroup per problem.  Per problem b:
+ *  - bounds: min / max over {start_x, goal_x, every ring vertex x} -/+ margin, the same for y (the reference's origin is
+ *    `start`, NULL = (0, 0) as there); H = ceil(W * ((max_y - min_y) / (max_x - min_x))), W = width.
+ *    world -> cell: rint(((x - min_x) / (max_x - min_x)) * W) (half to even, as np.round), H for y; cell -> world:
+ *    min_x + ((i * (max_x - min_x)) / W).  The grid is (W+1) x (H+1) cells, cell index i * (H+1) + j.
+ *  - occupancy: cell (i, j) is occupied if for some ring xmin <= i < xmax and ymin <= j < ymax over its ROUNDED vertices and
+ *    (i, j) lies in the closed convex hull of those rounded vertices (exact integer orientation tests).
+ *  - d2: exact squared Euclidean distance to the nearest occupied cell (0 on occupied cells); C = exp(-sqrt(d2)).
+ *  - draw k = 0, 1, ... of seed s: z = splitmix64 finaliser of (s + (k+1) * 0x9E3779B97F4A7C15), cell ((z >> 32) * ncells)
+ *    >> 32; a draw on an occupied, the start or the goal cell is skipped and is not a sample; at most 64 * n_samples draws.
+ *  - RRT* per sample x: v_near = nearest vertex (integer |p_v - x|^2, lowest index on ties); the sample is dropped (it still
+ *    counts) if that distance is 0 or the segment v_near -> x is blocked.  Near set = {v : |p_v - x|^2 <= r_rewire^2} +
+ *    v_near.  Parent = argmin over near vertices with a free segment of cost(v) + C[x] * sqrt(|p_v - x|^2) (lowest index on
+ *    ties).  Rewire, against the costs before this sample: every near u != parent with a free segment and
+ *    cost(x) + C[u] * len(x, u) < cost(u) takes x as parent; then the costs of x's subtree are recomputed top-down,
+ *    cost(v) = cost(parent(v)) + C[v] * len(parent(v), v).
+ *  - segment a -> b: endpoints in lexicographic order, m = max(|dx|, |dy|), cells a + floor((2 k d + m) / (2 m)), k = 0..m;
+ *    free if none is occupied.
+ *  - goal: its parent is the argmin of cost(v) + C[goal] * len over vertices within r_rewire with a free segment.
+ *  - output: the tree path without the root, ending with the goal CELL, in world coordinates.
+ * A problem's result depends only on its own inputs and seed.  Reproduced in numpy by tests/rrt_oracle.py. */
+#define LIPMPC_RRT_FOUND            0
+#define LIPMPC_RRT_NO_PATH          1  /* no vertex within r_rewire of the goal has a free segment to it */
+#define LIPMPC_RRT_START_OCCUPIED   2
+#define LIPMPC_RRT_GOAL_OCCUPIED    3
+#define LIPMPC_RRT_GRID_TOO_LARGE   4  /* (W+1)(H+1) > max_cells or H+1 > 4096 */
+#define LIPMPC_RRT_NO_OBSTACLE_GRID 5  /* no occupied cell: the distance transform is not defined */
+#define LIPMPC_RRT_PATH_OVERFLOW    6  /* the path has more than S_max sub-goals (path_cost is still written) */
+
+typedef struct lipmpc_rrt_params {
+  int32_t width;        /* W, grid cells across x minus one: 1..4095           (width_grid_size, :102) */
+  int32_t n_samples;    /* RRT* samples                                          (n=1500, :127) */
+  int32_t r_rewire;     /* near radius in cells, 1..8192                          (r_rewire=80, :127) */
+  int32_t max_cells;    /* cap on (W+1)(H+1): the tree kernel keeps the occupancy bitmap of this many cells in LDS */
+  double margin;        /* world margin around start, goal and obstacles          (3, :46-49) */
+} lipmpc_rrt_params;
+
+/* fills *p with 250, 1500, 80, 2^17 cells (16 KiB of bitmap, about 57 KiB of LDS per problem with the tree), 3.0 */
+int lipmpc_rrt_default_params(lipmpc_rrt_params* p);
+/* device workspace for B problems (contents arbitrary); < 0 if the parameters are invalid or the tree and bitmap do not
+ * fit the 160 KiB of LDS: 28 (n_samples + 1) + max_cells / 8 + 256 bytes */
+int64_t lipmpc_rrt_workspace_bytes(const lipmpc_rrt_params* p, int64_t B);
+/* All pointers are DEVICE pointers; asynchronous on hip_stream.
+ *  obs_xy [B,n_obs_max,v_max,2], obs_nv [B,n_obs_max]: as lipmpc_plan_step_batch (any ring of >= 1 vertex is an obstacle,
+ *         v_max <= 64); start [B,2] or NULL (= origin); goal [B,2]; seed [B] uint64
+ * outputs
+ *  sub_goals [B,S_max,2]: rows 0..n_sub[b]-1 written (FOUND only), the rest untouched; n_sub [B] (0 unless FOUND);
+ *  status [B] LIPMPC_RRT_*; path_cost [B] cost of the goal (NaN unless FOUND / PATH_OVERFLOW)
+ *  grid_dims [B,2] (W+1, H+1) or NULL
+ *  occ_d2 [B,max_cells] int32 or NULL: d2 of cell i*(H+1)+j for the first (W+1)(H+1) cells (0 = occupied; -1 everywhere on a
+ *         NO_OBSTACLE_GRID problem; untouched if GRID_TOO_LARGE)
+ *  cost_grid [B,max_cells] or NULL: C likewise (NaN on a NO_OBSTACLE_GRID problem)
+ *  tree [B,n_samples+2,4] or NULL: row 0 (vertex count V, goal's parent or -1, draws used, samples), row 1+v
+ *         (cell i, cell j, parent or -1, cost) for v < V; 0 for a problem whose status is decided before the tree. */
+int lipmpc_rrt_plan_batch(int device, const lipmpc_rrt_params* p, int64_t B, const double* obs_xy, const int32_t* obs_nv,
+                          int32_t n_obs_max, int32_t v_max, const double* start, const double* goal, const uint64_t* seed,
+                          void* workspace, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                          int32_t* grid_dims, int32_t* occ_d2, double* cost_grid, double* tree, int32_t S_max,
+                          void* hip_stream);
 
 const char* lipmpc_strerror(int code);
 int lipmpc_version(void);

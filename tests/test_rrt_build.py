@@ -1,0 +1,52 @@
+"""RRT* planner: C ABI and compiled resources (no GPU needed)."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import lipmpc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNELS = ("rrt_setup_kernel", "rrt_grid_kernel", "rrt_edt_col_kernel", "rrt_edt_row_kernel", "rrt_star_kernel")
+
+
+def test_rrt_exports_and_defaults():
+    lib = lipmpc._lib.load()
+    for name in ("lipmpc_rrt_default_params", "lipmpc_rrt_workspace_bytes", "lipmpc_rrt_plan_batch"):
+        assert name in lipmpc._lib.EXPORTS and hasattr(lib, name)
+    assert lib.lipmpc_version() == 5
+    p = lipmpc._lib.LipmpcRrtParamsC()
+    assert lib.lipmpc_rrt_default_params(C.byref(p)) == 0
+    assert (p.width, p.n_samples, p.r_rewire, p.margin) == (250, 1500, 80, 3.0)
+    # the largest grid of the reference's scenes (251 x 274 cells) fits the cap
+    assert p.max_cells >= 251 * 274
+    assert lib.lipmpc_rrt_workspace_bytes(C.byref(p), 0) == 0
+    one = lib.lipmpc_rrt_workspace_bytes(C.byref(p), 1)
+    assert one >= p.max_cells * 12 and lib.lipmpc_rrt_workspace_bytes(C.byref(p), 64) == 64 * one
+    # a tree and bitmap that do not fit the 160 KiB of LDS, and other invalid parameters, are refused
+    for field, bad in (("n_samples", 6000), ("max_cells", 1 << 21), ("width", 0), ("r_rewire", 0), ("margin", 0.0)):
+        q = lipmpc._lib.LipmpcRrtParamsC()
+        lib.lipmpc_rrt_default_params(C.byref(q))
+        setattr(q, field, bad)
+        assert lib.lipmpc_rrt_workspace_bytes(C.byref(q), 1) < 0, field
+    assert lib.lipmpc_rrt_default_params(None) < 0
+    assert lib.lipmpc_rrt_plan_batch(0, C.byref(p), 1, *([None] * 2), 0, 3, *([None] * 12), 8, None) < 0
+
+
+def test_rrt_kernel_resource_report():
+    """The five planner kernels compile without scratch (the tree kernel keeps tree and bitmap in LDS and every per-lane
+    walk in registers)."""
+    src = os.path.join(ROOT, "humanoid-navigation-using-mpc-ldcbf_amd", "csrc", "lipmpc_rrt.hip")
+    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-c", src,
+                        "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
+    found = set()
+    for b in blocks:
+        name = next((k for k in KERNELS if k in b.split()[0]), None)
+        if name is None:
+            continue
+        found.add(name)
+        scratch = int(re.search(r"ScratchSize[^:]*: (\d+)", b).group(1))
+        assert scratch == 0, (name, scratch)
+    assert found == set(KERNELS), found
