@@ -26,11 +26,56 @@ class LipmpcParamsC(C.Structure):
     ]
 
 
-EXPORTS = ("lipmpc_default_params", "lipmpc_create", "lipmpc_destroy", "lipmpc_num_rows",
-           "lipmpc_active_words", "lipmpc_plan_step_batch", "lipmpc_plan_step_batch_c_eta", "lipmpc_advance_batch", "lipmpc_fleet_update_batch", "lipmpc_rollout_batch", "lipmpc_lidar_sense_batch", "lipmpc_lidar_c_eta_batch", "lipmpc_lidar_schedule_words", "lipmpc_sense_plan_step_batch", "lipmpc_set_schedule", "lipmpc_schedule_words", "lipmpc_set_workspace", "lipmpc_workspace_bytes",
-           "lipmpc_set_warm_start", "lipmpc_warm_words",
-           "lipmpc_rrt_default_params", "lipmpc_rrt_workspace_bytes", "lipmpc_rrt_plan_batch",
-           "lipmpc_strerror", "lipmpc_version")
+_TYPES = {"ptr": C.c_void_p, "int": C.c_int, "i32": C.c_int32, "i64": C.c_int64, "f64": C.c_double,
+          "params": C.POINTER(LipmpcParamsC), "rrt_params": C.POINTER(LipmpcRrtParamsC), "handle_out": C.POINTER(C.c_void_p)}
+
+
+def _sig(restype, params):
+    """(restype, ((name, ctype), ...)) from 'name name:type ...' in the order of the prototype: a bare name is a pointer
+    (c_void_p: a handle, a device buffer, the stream), ':type' a key of _TYPES."""
+    return restype, tuple((n, _TYPES[t or "ptr"]) for n, _, t in (p.partition(":") for p in params.split()))
+
+
+_STEP_OUT = "U X theta omega obj status iters active working"
+_SCAN = "resolution:i32 n_env:i32 v_env:i32 env_shared:i32 lidar_range:f64 eps:f64 min_samples:i32"
+
+# Every export of include/lipmpc.h with the header's own parameter names: the ONE statement of each argument list on the
+# Python side.  load() binds restype / argtypes from it, call() takes its arguments by these names, and
+# tests/test_abi_and_c_oracle.py holds it to the prototypes (return type, count, names, order, type of every parameter).
+SIGNATURES = {
+    "lipmpc_default_params": _sig(C.c_int, "p:params"),
+    "lipmpc_create": _sig(C.c_int, "p:params device:int out:handle_out"),
+    "lipmpc_destroy": _sig(None, "h"),
+    "lipmpc_num_rows": _sig(C.c_int64, "p:params"),
+    "lipmpc_active_words": _sig(C.c_int64, "p:params"),
+    "lipmpc_plan_step_batch": _sig(C.c_int, f"h B:i64 state goal first_foot delta obs_xy obs_nv {_STEP_OUT} c_eta diag bounds hip_stream"),
+    "lipmpc_set_schedule": _sig(C.c_int, "h schedule capacity:i64"),
+    "lipmpc_schedule_words": _sig(C.c_int64, "B:i64"),
+    "lipmpc_set_warm_start": _sig(C.c_int, "h record capacity:i64"),
+    "lipmpc_warm_words": _sig(C.c_int64, "p:params"),
+    "lipmpc_workspace_bytes": _sig(C.c_int64, "h capacity:i64"),
+    "lipmpc_set_workspace": _sig(C.c_int, "h workspace capacity:i64"),
+    "lipmpc_plan_step_batch_c_eta": _sig(C.c_int, f"h B:i64 state goal first_foot delta c_eta_in overflow {_STEP_OUT} diag bounds hip_stream"),
+    "lipmpc_advance_batch": _sig(C.c_int, "h B:i64 state first_foot U theta status hip_stream"),
+    "lipmpc_fleet_update_batch": _sig(C.c_int, "h B:i64 k_max:i32 stop_obj:f64 state first_foot walking last_obj n_steps last_status n_overflow "
+                                               "sample X_pred U_pred U theta omega obj status overflow hip_stream"),
+    "lipmpc_rollout_batch": _sig(C.c_int, "h B:i64 k_max:i32 mpc_step:i32 stop_obj:f64 state0 goal first_foot delta obs_xy obs_nv "
+                                          "X_pred U_pred n_steps last_status total_iters bounds hip_stream"),
+    "lipmpc_lidar_sense_batch": _sig(C.c_int, f"device:int B:i64 {_SCAN} n_obs_max:i32 v_max:i32 state env_xy env_nv ray_table noise "
+                                              "obs_xy obs_nv n_inferred overflow hits labels hip_stream"),
+    "lipmpc_lidar_c_eta_batch": _sig(C.c_int, f"device:int B:i64 {_SCAN} n_obs_max:i32 v_max:i32 state env_xy env_nv ray_table noise "
+                                              "c_eta n_inferred overflow obs_xy obs_nv hits labels schedule hip_stream"),
+    "lipmpc_lidar_schedule_words": _sig(C.c_int64, "B:i64"),
+    "lipmpc_sense_plan_step_batch": _sig(C.c_int, f"h B:i64 {_SCAN} state goal first_foot delta env_xy env_nv ray_table noise "
+                                                  f"c_eta n_inferred overflow schedule {_STEP_OUT} diag bounds hip_stream"),
+    "lipmpc_rrt_default_params": _sig(C.c_int, "p:rrt_params"),
+    "lipmpc_rrt_workspace_bytes": _sig(C.c_int64, "p:rrt_params B:i64"),
+    "lipmpc_rrt_plan_batch": _sig(C.c_int, "device:int p:rrt_params B:i64 obs_xy obs_nv n_obs_max:i32 v_max:i32 start goal seed workspace "
+                                           "sub_goals n_sub status path_cost grid_dims occ_d2 cost_grid tree S_max:i32 hip_stream"),
+    "lipmpc_strerror": _sig(C.c_char_p, "code:int"),
+    "lipmpc_version": _sig(C.c_int, ""),
+}
+EXPORTS = tuple(SIGNATURES)
 
 ABI_VERSION = 5          # LIPMPC_ABI_VERSION of include/lipmpc.h this binding is written for
 VARIANT_BASE = 1000      # LIPMPC_VARIANT_BASE: instrumented development builds report ABI_VERSION + this
@@ -38,6 +83,8 @@ DIAG_WORDS = 8           # LIPMPC_DIAG_WORDS
 TIGHT_TOL = 1e-7         # LIPMPC_TIGHT_TOL
 
 _lib = None
+_bound = {}              # name -> (bound function, ((parameter name, is a c_void_p), ...)): what call() needs, resolved once by load()
+_ADDRESSES = {type(None), int, C.c_void_p}       # what call() hands to a c_void_p parameter as it is: NULL, the stream, the handle
 
 
 def load():
@@ -53,75 +100,43 @@ def load():
             f"{path} not found: build the HIP extension first "
             "(python -c 'import __graft_entry__ as g; g.build()' or make -C <package>/csrc)")
     lib = C.CDLL(path)
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-    # The argument lists bound below are those of ONE ABI version: a stale or historical build (LIPMPC_LIB) would take every
+    # SIGNATURES holds the argument lists of ONE ABI version: a stale or historical build (LIPMPC_LIB) would take every
     # pointer after an inserted argument shifted by one, and an instrumented variant (version >= LIPMPC_VARIANT_BASE) writes
     # other buffer shapes.  Refuse both here, before any pointer is handed over; tools that drive a variant on purpose set
     # LIPMPC_ALLOW_VARIANT=1 and hand in the buffers that variant expects.
-    lib.lipmpc_version.argtypes = []
-    lib.lipmpc_version.restype = i32
     ver = int(lib.lipmpc_version())
     if ver != ABI_VERSION and not (ver == ABI_VERSION + VARIANT_BASE and os.environ.get("LIPMPC_ALLOW_VARIANT") == "1"):
         raise RuntimeError(f"{path}: lipmpc_version() = {ver}, this binding is written for ABI {ABI_VERSION} "
                            f"(include/lipmpc.h); rebuild the library (make -C <package>/csrc)")
-    lib.lipmpc_default_params.argtypes = [C.POINTER(LipmpcParamsC)]
-    lib.lipmpc_default_params.restype = i32
-    lib.lipmpc_create.argtypes = [C.POINTER(LipmpcParamsC), i32, C.POINTER(vp)]
-    lib.lipmpc_create.restype = i32
-    lib.lipmpc_destroy.argtypes = [vp]
-    lib.lipmpc_destroy.restype = None
-    lib.lipmpc_num_rows.argtypes = [C.POINTER(LipmpcParamsC)]
-    lib.lipmpc_num_rows.restype = i64
-    lib.lipmpc_active_words.argtypes = [C.POINTER(LipmpcParamsC)]
-    lib.lipmpc_active_words.restype = i64
-    lib.lipmpc_plan_step_batch.argtypes = [vp, i64] + [vp] * 19
-    lib.lipmpc_plan_step_batch.restype = i32
-    lib.lipmpc_plan_step_batch_c_eta.argtypes = [vp, i64] + [vp] * 18
-    lib.lipmpc_plan_step_batch_c_eta.restype = i32
-    lib.lipmpc_advance_batch.argtypes = [vp, i64] + [vp] * 6
-    lib.lipmpc_advance_batch.restype = i32
-    lib.lipmpc_fleet_update_batch.argtypes = [vp, i64, C.c_int32, C.c_double] + [vp] * 17
-    lib.lipmpc_fleet_update_batch.restype = i32
-    lib.lipmpc_rollout_batch.argtypes = [vp, i64, C.c_int32, C.c_int32, C.c_double] + [vp] * 13
-    lib.lipmpc_rollout_batch.restype = i32
-    lib.lipmpc_lidar_sense_batch.argtypes = ([i32, i64] + [C.c_int32] * 4 + [C.c_double, C.c_double] + [C.c_int32] * 3
-                                             + [vp] * 12)
-    lib.lipmpc_lidar_sense_batch.restype = i32
-    lib.lipmpc_lidar_c_eta_batch.argtypes = ([i32, i64] + [C.c_int32] * 4 + [C.c_double, C.c_double] + [C.c_int32] * 3
-                                             + [vp] * 14)
-    lib.lipmpc_lidar_c_eta_batch.restype = i32
-    lib.lipmpc_lidar_schedule_words.argtypes = [i64]
-    lib.lipmpc_lidar_schedule_words.restype = i64
-    lib.lipmpc_sense_plan_step_batch.argtypes = ([vp, i64] + [C.c_int32] * 4 + [C.c_double, C.c_double, C.c_int32] + [vp] * 24)
-    lib.lipmpc_sense_plan_step_batch.restype = i32
-    lib.lipmpc_set_schedule.argtypes = [vp, vp, i64]
-    lib.lipmpc_set_schedule.restype = i32
-    lib.lipmpc_schedule_words.argtypes = [i64]
-    lib.lipmpc_schedule_words.restype = i64
-    lib.lipmpc_set_workspace.argtypes = [vp, vp, i64]
-    lib.lipmpc_set_workspace.restype = i32
-    lib.lipmpc_workspace_bytes.argtypes = [vp, i64]
-    lib.lipmpc_workspace_bytes.restype = i64
-    lib.lipmpc_set_warm_start.argtypes = [vp, vp, i64]
-    lib.lipmpc_set_warm_start.restype = i32
-    lib.lipmpc_warm_words.argtypes = [C.POINTER(LipmpcParamsC)]
-    lib.lipmpc_warm_words.restype = i64
-    lib.lipmpc_rrt_default_params.argtypes = [C.POINTER(LipmpcRrtParamsC)]
-    lib.lipmpc_rrt_default_params.restype = i32
-    lib.lipmpc_rrt_workspace_bytes.argtypes = [C.POINTER(LipmpcRrtParamsC), i64]
-    lib.lipmpc_rrt_workspace_bytes.restype = i64
-    lib.lipmpc_rrt_plan_batch.argtypes = ([i32, C.POINTER(LipmpcRrtParamsC), i64, vp, vp, C.c_int32, C.c_int32]
-                                          + [vp] * 12 + [C.c_int32, vp])
-    lib.lipmpc_rrt_plan_batch.restype = i32
-    lib.lipmpc_strerror.argtypes = [i32]
-    lib.lipmpc_strerror.restype = C.c_char_p
-    lib.lipmpc_version.argtypes = []
-    lib.lipmpc_version.restype = i32
+    for name, (restype, params) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, [t for _, t in params]
+        _bound[name] = fn, tuple((n, t is C.c_void_p) for n, t in params)
     _lib = lib
     return lib
 
 
 def check(code, what):
     if code != 0:
-        msg = load().lipmpc_strerror(code).decode()
-        raise RuntimeError(f"{what} failed: {msg} ({code})")
+        err = RuntimeError(f"{what} failed: {load().lipmpc_strerror(code).decode()} ({code})")
+        err.code = code
+        raise err
+
+
+def call(name, **args):
+    """Call an entry point that returns a status, every argument given by the header's parameter name (SIGNATURES), exactly
+    once: a missing or an unknown name is a TypeError before anything is enqueued.  Pointer parameters take a tensor (its
+    data_ptr()), None (NULL) or an address (the handle, the stream); the others go through their ctype.  A non-zero status raises
+    check()'s RuntimeError, the code in its ``code`` attribute."""
+    if _lib is None:
+        load()
+    fn, params = _bound[name]
+    try:
+        argv = [v.data_ptr() if is_ptr and v.__class__ not in _ADDRESSES else v for n, is_ptr in params for v in (args[n],)]
+    except KeyError as e:
+        raise TypeError(f"{name}: argument {e.args[0]!r} missing") from None
+    if len(args) != len(argv):
+        raise TypeError(f"{name}: no such argument {sorted(set(args) - {n for n, _ in params})}")
+    rc = fn(*argv)
+    if rc != 0:
+        check(rc, name)

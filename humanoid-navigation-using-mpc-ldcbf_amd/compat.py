@@ -167,9 +167,7 @@ class HumanoidMPC:
             if self._ce_solver is None or n_slots != have:
                 self._ce_solver = self._make_solver(n_slots, 3)
         elif self._ce_solver is None or self._ce_solver.params.n_obs_max != n_obs:
-            p = LipMpcParams(N=self.N_horizon, n_obs_max=n_obs, v_max=3, sampling_time=self.sampling_time,
-                             flags=0 if self._exact else FLAG_INTERIOR, tol_interior=self._interior_tol)
-            self._ce_solver = BatchedLipMpc(p, self._device)
+            self._ce_solver = self._make_solver(n_obs, 3)
         sv = self._ce_solver
         n_slots = sv.params.n_obs_max
         dev = sv.device

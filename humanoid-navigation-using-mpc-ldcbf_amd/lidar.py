@@ -3,7 +3,6 @@ lipmpc_lidar_sense_batch and the drop-in HumanoidMPCUnknownEnvironment class
 (HumanoidNavigation/MPC/HumanoidMPCVariants/HumanoidMPCUnknownEnvironment.py:13-68)."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
@@ -11,7 +10,7 @@ import torch
 
 from . import _lib
 from .compat import HumanoidMPC, _ring_of
-from .solver import _check, _ptr, _step_out_ptrs
+from .solver import _STEP_OUTPUTS_GIVEN_C_ETA, _alloc, _check, _check_table, _named, fleet_state
 
 NOISE_STD = 0.01           # range_finder_wth_polygons_dbscan.py:163
 DBSCAN_EPS = 0.3           # :100
@@ -22,6 +21,19 @@ def ray_table(resolution=360):
     """(cos, sin) of i * 2 pi / resolution through math.cos / math.sin, as the reference computes its rays (:28-36)."""
     step = 2 * math.pi / resolution
     return np.array([[math.cos(i * step), math.sin(i * step)] for i in range(resolution)])
+
+
+def sensor_outputs(B, n_obs_max, v_max, resolution):
+    """Outputs of a scan, in the order LidarSensor.alloc_outputs returns them; which of the optional ones a call needs is the
+    call's to say."""
+    f64, i32 = torch.float64, torch.int32
+    return {"n_inferred": (i32, (B,), True), "overflow": (i32, (B,), True), "obs_xy": (f64, (B, n_obs_max, v_max, 2), False),
+            "obs_nv": (i32, (B, n_obs_max), False), "c_eta": (f64, (B, n_obs_max, 4), False),
+            "hits": (f64, (B, resolution, 2), False), "labels": (i32, (B, resolution), False)}
+
+
+SENSOR_OUTPUTS = tuple(sensor_outputs(0, 0, 0, 0))                           # the names
+_RING_SCAN_OUTPUTS = tuple(k for k in SENSOR_OUTPUTS if k != "c_eta")       # lipmpc_lidar_sense_batch has no c_eta
 
 
 class LidarSensor:
@@ -44,20 +56,15 @@ class LidarSensor:
         self.env_xy = torch.as_tensor(xy, device=self.device)
         self.env_nv = torch.as_tensor(nv, device=self.device)
         self.table = torch.as_tensor(ray_table(self.resolution), device=self.device)
+        self._auto_sched = {}      # (batch size, stream) -> order buffer of sense(schedule="auto")
 
     def alloc_outputs(self, B, with_debug=False, rings=True, c_eta=False):
         """Output buffers of ``sense``: rings (obs_xy, obs_nv) and / or the assembled half-spaces c_eta [B,n_obs_max,4]."""
-        dev = self.device
-        out = dict(n_inferred=torch.zeros((B,), dtype=torch.int32, device=dev),
-                   overflow=torch.zeros((B,), dtype=torch.int32, device=dev))
-        if rings:
-            out["obs_xy"] = torch.zeros((B, self.n_obs_max, self.v_max, 2), dtype=torch.float64, device=dev)
-            out["obs_nv"] = torch.zeros((B, self.n_obs_max), dtype=torch.int32, device=dev)
-        if c_eta:
-            out["c_eta"] = torch.zeros((B, self.n_obs_max, 4), dtype=torch.float64, device=dev)
+        table = sensor_outputs(B, self.n_obs_max, self.v_max, self.resolution)
+        names = ("n_inferred", "overflow") + (("obs_xy", "obs_nv") if rings else ()) + (("c_eta",) if c_eta else ())
+        out = _alloc(table, names, self.device, torch.zeros)
         if with_debug:
-            out["hits"] = torch.empty((B, self.resolution, 2), dtype=torch.float64, device=dev)
-            out["labels"] = torch.empty((B, self.resolution), dtype=torch.int32, device=dev)
+            out.update(_alloc(table, ("hits", "labels"), self.device))
         return out
 
     def make_schedule(self, B):
@@ -85,11 +92,7 @@ class LidarSensor:
         if out is None:
             out = self.alloc_outputs(B, with_debug, rings=rings or not c_eta, c_eta=c_eta)
         want_ce = "c_eta" in out
-        for name, shape, dt in (("obs_xy", (B, self.n_obs_max, self.v_max, 2), torch.float64), ("obs_nv", (B, self.n_obs_max), torch.int32),
-                                ("c_eta", (B, self.n_obs_max, 4), torch.float64), ("n_inferred", (B,), torch.int32),
-                                ("overflow", (B,), torch.int32), ("hits", (B, self.resolution, 2), torch.float64),
-                                ("labels", (B, self.resolution), torch.int32)):
-            _check(out.get(name), shape, dt, dev, f"out['{name}']")
+        _check_table(sensor_outputs(B, self.n_obs_max, self.v_max, self.resolution), out, dev, "out")
         _check(state, (B, 5), torch.float64, dev, "state", required=True)
         _check(noise, (B, self.resolution, 2), torch.float64, dev, "noise")
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -101,8 +104,6 @@ class LidarSensor:
                     or env_xy.device != dev or env_nv.device != dev):
                 raise ValueError("per-robot maps: env_xy [B,n_env,v_env,2] float64, env_nv [B,n_env] int32, contiguous, on the sensor's device")
             n_env, v_env, shared, exy, env = int(env_xy.shape[1]), int(env_xy.shape[2]), 0, env_xy, env_nv
-        head = (self.device_index, B, self.resolution, n_env, v_env, shared, self.lidar_range, DBSCAN_EPS,
-                DBSCAN_MIN_SAMPLES, self.n_obs_max, self.v_max, _ptr(state), _ptr(exy), _ptr(env), _ptr(self.table), _ptr(noise))
         if isinstance(schedule, str):
             if schedule != "auto":
                 raise ValueError('schedule: a make_schedule(B) buffer, None or "auto"')
@@ -110,26 +111,21 @@ class LidarSensor:
             if want_ce and B > 2048:                         # beyond one round of waves (two per SIMD) the start order matters
                 # one buffer per (batch size, stream): scans sharing a schedule must be ordered on one stream -- the order
                 # kernel of one launch rewrites what the next one reads
-                cache = self.__dict__.setdefault("_auto_sched", {})
                 key = (B, stream)
-                if key not in cache:
-                    cache[key] = self.make_schedule(B)
-                schedule = cache[key]
+                if key not in self._auto_sched:
+                    self._auto_sched[key] = self.make_schedule(B)
+                schedule = self._auto_sched[key]
         if schedule is not None and (not want_ce or schedule.dtype != torch.int32 or schedule.device != dev or not schedule.is_contiguous()
                                      or schedule.numel() != int(self.lib.lipmpc_lidar_schedule_words(B))):
             raise ValueError("schedule: a buffer of make_schedule(B) for this B, with c_eta=True")
         if want_ce:
-            rc = self.lib.lipmpc_lidar_c_eta_batch(*head, _ptr(out["c_eta"]), _ptr(out["n_inferred"]), _ptr(out["overflow"]),
-                                                   _ptr(out.get("obs_xy")), _ptr(out.get("obs_nv")), _ptr(out.get("hits")),
-                                                   _ptr(out.get("labels")), _ptr(schedule), C.c_void_p(stream))
-            _lib.check(rc, "lipmpc_lidar_c_eta_batch")
+            entry, outputs = "lipmpc_lidar_c_eta_batch", dict(_named(out, SENSOR_OUTPUTS), schedule=schedule)
         else:
-            rc = self.lib.lipmpc_lidar_sense_batch(*head, _ptr(out["obs_xy"]), _ptr(out["obs_nv"]), _ptr(out["n_inferred"]),
-                                                   _ptr(out["overflow"]), _ptr(out.get("hits")), _ptr(out.get("labels")),
-                                                   C.c_void_p(stream))
-            _lib.check(rc, "lipmpc_lidar_sense_batch")
+            entry, outputs = "lipmpc_lidar_sense_batch", _named(out, _RING_SCAN_OUTPUTS)
+        _lib.call(entry, device=self.device_index, B=B, resolution=self.resolution, n_env=n_env, v_env=v_env, env_shared=shared,
+                  lidar_range=self.lidar_range, eps=DBSCAN_EPS, min_samples=DBSCAN_MIN_SAMPLES, n_obs_max=self.n_obs_max,
+                  v_max=self.v_max, state=state, env_xy=exy, env_nv=env, ray_table=self.table, noise=noise, **outputs, hip_stream=stream)
         return out
-
 
     def sense_plan_step(self, solver, state, goal, first_foot, noise=None, delta=None, sen=None, out=None, schedule=None,
                         bounds=None):
@@ -152,20 +148,19 @@ class LidarSensor:
             out = solver.alloc_outputs(B)
         else:
             solver._check_outputs(out, B)
-        for name, shape, dt in (("c_eta", (B, self.n_obs_max, 4), torch.float64), ("n_inferred", (B,), torch.int32), ("overflow", (B,), torch.int32)):
-            _check(sen.get(name), shape, dt, self.device, f"sen['{name}']", required=True)
+        table, handed_over = sensor_outputs(B, self.n_obs_max, self.v_max, self.resolution), ("c_eta", "n_inferred", "overflow")
+        for k in handed_over:
+            _check(sen.get(k), table[k][1], table[k][0], self.device, f"sen['{k}']", required=True)
         _check(noise, (B, self.resolution, 2), torch.float64, self.device, "noise")
         if schedule is not None and (schedule.dtype != torch.int32 or schedule.device != self.device or not schedule.is_contiguous()
                                      or schedule.numel() != int(self.lib.lipmpc_lidar_schedule_words(B))):
             raise ValueError("schedule: a buffer of make_schedule(B) for this B")
         solver._ensure_workspace(B)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.lipmpc_sense_plan_step_batch(
-            solver._h, B, self.resolution, self.n_env, self.v_env, 1, self.lidar_range, DBSCAN_EPS, DBSCAN_MIN_SAMPLES,
-            _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(self.env_xy), _ptr(self.env_nv), _ptr(self.table),
-            _ptr(noise), _ptr(sen["c_eta"]), _ptr(sen["n_inferred"]), _ptr(sen["overflow"]), _ptr(schedule),
-            *_step_out_ptrs(out), _ptr(bounds), C.c_void_p(stream))
-        _lib.check(rc, "lipmpc_sense_plan_step_batch")
+        _lib.call("lipmpc_sense_plan_step_batch", h=solver._h, B=B, resolution=self.resolution, n_env=self.n_env, v_env=self.v_env,
+                  env_shared=1, lidar_range=self.lidar_range, eps=DBSCAN_EPS, min_samples=DBSCAN_MIN_SAMPLES, state=state, goal=goal,
+                  first_foot=first_foot, delta=delta, env_xy=self.env_xy, env_nv=self.env_nv, ray_table=self.table, noise=noise,
+                  **_named(sen, handed_over), schedule=schedule, **_named(out, _STEP_OUTPUTS_GIVEN_C_ETA), bounds=bounds,
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         return sen, out
 
 
@@ -263,13 +258,10 @@ class UnknownEnvFleet:
         if self.warm_start and not sv.set_warm_start(B):      # (outside any capture; grow-only)
             raise ValueError("warm_start: the warm-start record needs N >= 2 and at most 14 obstacle slots")
         f64 = dict(dtype=torch.float64, device=dev)
-        fl = dict(state=torch.zeros((B, 5), **f64), first_foot=torch.ones((B,), dtype=torch.int8, device=dev),
-                  walking=torch.ones((B,), dtype=torch.int8, device=dev), last_obj=torch.zeros((B,), **f64),
-                  n_steps=torch.zeros((B,), dtype=torch.int32, device=dev),
-                  last_status=torch.zeros((B,), dtype=torch.int32, device=dev),
-                  n_overflow=torch.zeros((B,), dtype=torch.int32, device=dev),
-                  sample=torch.zeros((1,), dtype=torch.int32, device=dev),
-                  X_pred=torch.zeros((B, k_max + 1, 5), **f64), U_pred=torch.zeros((B, k_max, 3), **f64))
+        table = fleet_state(B, k_max)
+        fl = _alloc(table, table, dev, torch.zeros)
+        fl["first_foot"].fill_(1)
+        fl["walking"].fill_(1)
         pl = dict(key=key, fl=fl, goal=torch.zeros((B, 2), **f64), delta=torch.zeros((B,), **f64) if have_delta else None,
                   sen=sn.alloc_outputs(B, rings=False, c_eta=True),      # hulls stay in the scan kernel: only (c, eta) rows reach HBM
                   out=sv.alloc_outputs(B), nbuf=None if noise_mode == "none" else torch.zeros((B, sn.resolution, 2), **f64),

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .solver import pack_rings
+from .solver import _alloc, _named, pack_rings
 
 RRT_FOUND, RRT_NO_PATH, RRT_START_OCCUPIED, RRT_GOAL_OCCUPIED, RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, \
     RRT_PATH_OVERFLOW = range(7)
@@ -20,8 +20,12 @@ RRT_STATUS_NAMES = ("FOUND", "NO_PATH", "START_OCCUPIED", "GOAL_OCCUPIED", "GRID
                     "PATH_OVERFLOW")
 
 
-def _ptr(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
+def plan_outputs(B, S_max, max_cells, n_samples):
+    """Outputs of a plan, in the order RrtStarPlanner.plan_batch returns them."""
+    f64, i32 = torch.float64, torch.int32
+    return {"sub_goals": (f64, (B, S_max, 2), True), "n_sub": (i32, (B,), True), "status": (i32, (B,), True), "path_cost": (f64, (B,), True),
+            "grid_dims": (i32, (B, 2), False), "occ_d2": (i32, (B, max_cells), False), "cost_grid": (f64, (B, max_cells), False),
+            "tree": (f64, (B, n_samples + 2, 4), False)}
 
 
 class RrtStarPlanner:
@@ -99,27 +103,14 @@ class RrtStarPlanner:
                 raise ValueError("seeds must have B entries")
         seeds_d = torch.as_tensor(sd.view(np.int64), device=self.device)
         S_max = int(self.params.n_samples) + 1 if S_max is None else int(S_max)
-        dev = self.device
-        out = dict(sub_goals=torch.zeros((B, S_max, 2), dtype=torch.float64, device=dev),
-                   n_sub=torch.zeros((B,), dtype=torch.int32, device=dev),
-                   status=torch.zeros((B,), dtype=torch.int32, device=dev),
-                   path_cost=torch.zeros((B,), dtype=torch.float64, device=dev))
-        if with_grids:
-            out.update(grid_dims=torch.zeros((B, 2), dtype=torch.int32, device=dev),
-                       occ_d2=torch.zeros((B, self.max_cells), dtype=torch.int32, device=dev),
-                       cost_grid=torch.zeros((B, self.max_cells), dtype=torch.float64, device=dev))
-        if with_tree:
-            out["tree"] = torch.zeros((B, int(self.params.n_samples) + 2, 4), dtype=torch.float64, device=dev)
+        want = dict(grid_dims=with_grids, occ_d2=with_grids, cost_grid=with_grids, tree=with_tree)
+        table = plan_outputs(B, S_max, self.max_cells, int(self.params.n_samples))
+        out = _alloc(table, [k for k, (_, _, required) in table.items() if required or want[k]], self.device, torch.zeros)
         if B == 0:
             return out
-        ws = self._workspace(B)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lipmpc_rrt_plan_batch(
-            self.device_index, C.byref(self.params), B, _ptr(xy), _ptr(nv), n_obs, v_max, _ptr(st), _ptr(goal),
-            _ptr(seeds_d), _ptr(ws), _ptr(out["sub_goals"]), _ptr(out["n_sub"]), _ptr(out["status"]),
-            _ptr(out["path_cost"]), _ptr(out.get("grid_dims")), _ptr(out.get("occ_d2")), _ptr(out.get("cost_grid")),
-            _ptr(out.get("tree")), S_max, C.c_void_p(stream))
-        _lib.check(rc, "lipmpc_rrt_plan_batch")
+        _lib.call("lipmpc_rrt_plan_batch", device=self.device_index, p=C.byref(self.params), B=B, obs_xy=xy, obs_nv=nv, n_obs_max=n_obs,
+                  v_max=v_max, start=st, goal=goal, seed=seeds_d, workspace=self._workspace(B), **_named(out, table),
+                  S_max=S_max, hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         self.last = out
         return out
 

@@ -64,10 +64,6 @@ class LipMpcParams:
         return (self.num_rows + 63) // 64
 
 
-def _ptr(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
 def _check(t, shape, dtype, device, name, required=False):
     """A buffer whose raw pointer goes to a kernel: a contiguous ``dtype`` tensor of ``shape`` on ``device``, or None when
     not ``required``; anything else is a ValueError naming it."""
@@ -75,15 +71,59 @@ def _check(t, shape, dtype, device, name, required=False):
         if required:
             raise ValueError(f"{name} is required")
         return
-    if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+    if t.shape != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
         raise ValueError(f"{name}: expected contiguous {dtype} {shape} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
-def _step_out_ptrs(out, c_eta_slot=False):
-    """The output pointers of a step in the order of the C ABI: U .. working[, c_eta when the entry point has that slot],
-    diag (absent optional outputs: NULL)."""
-    names = ("U", "X", "theta", "omega", "obj", "status", "iters", "active", "working") + (("c_eta",) if c_eta_slot else ()) + ("diag",)
-    return [_ptr(out.get(k)) for k in names]
+# A buffer family is one shape table next to the class that owns it -- a function of B and the owner's sizes that returns
+# name (the C ABI's parameter name) -> (dtype, shape, required) -- which allocation and checking both read.
+def _alloc(table, names, device, new=torch.empty):
+    return {k: new(table[k][1], dtype=table[k][0], device=device) for k in names}
+
+
+def _check_table(table, bufs, device, what):
+    """Caller-supplied buffers of a family: every required one present, every one given as ``_check`` wants it (whose test is
+    repeated here: this runs per buffer on every launch, and only a failure needs the call and the buffer's name)."""
+    for k, (dtype, shape, required) in table.items():
+        t = bufs.get(k)
+        if t is None:
+            if required and k not in bufs:
+                raise ValueError(f"{what}['{k}'] missing")
+        elif t.shape != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+            _check(t, shape, dtype, device, f"{what}['{k}']")
+
+
+def _named(bufs, names):
+    """``bufs``' entries under ``names`` as keyword arguments of _lib.call (an optional buffer that is absent: None = NULL)."""
+    return {k: bufs.get(k) for k in names}
+
+
+def step_outputs(B, P):
+    """Outputs of a step of a handle with the LipMpcParams ``P``, in the order alloc_outputs returns them."""
+    f64, i32, i64, words = torch.float64, torch.int32, torch.int64, P.active_words
+    return {"U": (f64, (B, P.N, 2), True), "X": (f64, (B, P.N + 1, 4), True), "theta": (f64, (B, P.N + 1), True),
+            "omega": (f64, (B, P.N), True), "obj": (f64, (B,), True), "status": (i32, (B,), True), "iters": (i32, (B,), True),
+            "active": (i64, (B, words), True), "c_eta": (f64, (B, P.n_obs_max, 4), False),
+            "diag": (f64, (B, _lib.DIAG_WORDS), False), "working": (i64, (B, words), False)}
+
+
+def fleet_state(B, k_max):
+    """State of a host-driven fleet loop of at most ``k_max`` samples (fleet_update)."""
+    f64, i32, i8 = torch.float64, torch.int32, torch.int8
+    return {"state": (f64, (B, 5), True), "first_foot": (i8, (B,), True), "walking": (i8, (B,), True), "last_obj": (f64, (B,), True),
+            "n_steps": (i32, (B,), True), "last_status": (i32, (B,), True), "n_overflow": (i32, (B,), True), "sample": (i32, (1,), True),
+            "X_pred": (f64, (B, k_max + 1, 5), True), "U_pred": (f64, (B, k_max, 3), True)}
+
+
+def rollout_outputs(B, k_max):
+    """Outputs of the on-device closed loop of at most ``k_max`` samples (rollout)."""
+    f64, i32 = torch.float64, torch.int32
+    return {"X_pred": (f64, (B, k_max + 1, 5), True), "U_pred": (f64, (B, k_max, 3), True), "n_steps": (i32, (B,), True),
+            "last_status": (i32, (B,), True), "total_iters": (i32, (B,), True)}
+
+
+STEP_OUTPUTS, FLEET_STATE = tuple(step_outputs(0, LipMpcParams())), tuple(fleet_state(0, 0))             # the names
+_STEP_OUTPUTS_GIVEN_C_ETA = tuple(k for k in STEP_OUTPUTS if k != "c_eta")      # the entry points that take the half-spaces as input
 
 
 class BatchedLipMpc:
@@ -104,11 +144,18 @@ class BatchedLipMpc:
         self.auto_workspace = True
         self._ws, self._ws_cap = None, 0           # the workspace registered last
         self._ws_by_stream = {}                    # stream -> (workspace, capacity) of the eager launches on it: grow-only
-        self._kept = []                            # every buffer ever registered with the library (a captured graph may hold it)
+        self._kept = {}                            # address -> every buffer ever registered with the library (_register)
+        self._sched = None
         self._side_streams = False                 # the library made its side streams / events (first workspace registered)
         self._split_capable = int(self.lib.lipmpc_workspace_bytes(self._h, 1)) > 0
         self._warm, self._warm_cap = None, 0
         self.warm_words = int(self.lib.lipmpc_warm_words(C.byref(cp)))
+
+    def _register(self, setter, capacity, **buffer):
+        """Hand a buffer, under the setter's parameter name, to lipmpc_set_schedule / _set_workspace / _set_warm_start.  Whatever
+        the library has accepted the handle keeps for as long as it lives: a captured graph may hold the pointer."""
+        _lib.call(setter, h=self._h, capacity=capacity, **buffer)
+        self._kept.update((b.data_ptr(), b) for b in buffer.values() if b is not None)
 
     def set_warm_start(self, capacity):
         """Warm-start records for this handle's step launches (lipmpc_set_warm_start): allocates a zeroed
@@ -126,10 +173,12 @@ class BatchedLipMpc:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("set_warm_start: cannot grow the warm-start record while a graph is being captured")
         rec = torch.zeros((capacity, self.warm_words), dtype=torch.float64, device=self.device)
-        rc = self.lib.lipmpc_set_warm_start(self._h, _ptr(rec), capacity)
-        if rc == _LIPMPC_E_UNSUPPORTED:
+        try:
+            self._register("lipmpc_set_warm_start", capacity, record=rec)
+        except RuntimeError as e:
+            if getattr(e, "code", None) != _LIPMPC_E_UNSUPPORTED:
+                raise
             return False
-        _lib.check(rc, "lipmpc_set_warm_start")
         self._warm, self._warm_cap = rec, capacity
         return True
 
@@ -174,20 +223,18 @@ class BatchedLipMpc:
         self._register_workspace(ws, capacity)
 
     def _new_workspace(self, capacity):
-        """A workspace buffer of ``capacity`` problems that the handle keeps for its lifetime, or None (not split-capable)."""
+        """A workspace buffer of ``capacity`` problems, or None (not split-capable)."""
         nbytes = int(self.lib.lipmpc_workspace_bytes(self._h, capacity)) if capacity > 0 else 0
         if nbytes <= 0:
             return None
         if not self._side_streams and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("the first split launch (workspace) of a handle makes its side streams and events, which cannot "
                                "happen during a graph capture: run one step of the handle, or set_workspace, before capturing")
-        ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=self.device)
-        self._kept.append(ws)
-        return ws
+        return torch.empty((nbytes // 4,), dtype=torch.int32, device=self.device)
 
     def _register_workspace(self, ws, capacity):
         cap = capacity if ws is not None else 0
-        _lib.check(self.lib.lipmpc_set_workspace(self._h, _ptr(ws), cap), "lipmpc_set_workspace")
+        self._register("lipmpc_set_workspace", cap, workspace=ws)
         self._ws, self._ws_cap = ws, cap
         self._side_streams = self._side_streams or ws is not None
 
@@ -217,9 +264,7 @@ class BatchedLipMpc:
         capacity = int(capacity)
         self._sched = (torch.zeros((int(self.lib.lipmpc_schedule_words(capacity)),), dtype=torch.int32, device=self.device)
                        if capacity > 0 else None)
-        if self._sched is not None:
-            self._kept.append(self._sched)
-        _lib.check(self.lib.lipmpc_set_schedule(self._h, _ptr(self._sched), capacity), "lipmpc_set_schedule")
+        self._register("lipmpc_set_schedule", capacity, schedule=self._sched)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -229,23 +274,8 @@ class BatchedLipMpc:
 
     # ---- buffers --------------------------------------------------------------------------------
     def alloc_outputs(self, B, with_c_eta=False, with_diag=False, with_working=False):
-        P, dev = self.params, self.device
-        f64 = dict(dtype=torch.float64, device=dev)
-        out = dict(
-            U=torch.empty((B, P.N, 2), **f64), X=torch.empty((B, P.N + 1, 4), **f64),
-            theta=torch.empty((B, P.N + 1), **f64), omega=torch.empty((B, P.N), **f64),
-            obj=torch.empty((B,), **f64),
-            status=torch.empty((B,), dtype=torch.int32, device=dev),
-            iters=torch.empty((B,), dtype=torch.int32, device=dev),
-            active=torch.empty((B, P.active_words), dtype=torch.int64, device=dev),
-        )
-        if with_c_eta:
-            out["c_eta"] = torch.empty((B, P.n_obs_max, 4), **f64)
-        if with_diag:
-            out["diag"] = torch.empty((B, _lib.DIAG_WORDS), **f64)
-        if with_working:
-            out["working"] = torch.empty((B, P.active_words), dtype=torch.int64, device=dev)
-        return out
+        table, want = step_outputs(B, self.params), dict(c_eta=with_c_eta, diag=with_diag, working=with_working)
+        return _alloc(table, [k for k, (_, _, required) in table.items() if required or want[k]], self.device)
 
     def _check_inputs(self, state, goal, first_foot, obs_xy, obs_nv, delta, need_obstacles=True):
         P, dev = self.params, self.device
@@ -282,11 +312,9 @@ class BatchedLipMpc:
             self._check_outputs(out, B)
         self._ensure_workspace(B)
         self._check_warm(B)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.lipmpc_plan_step_batch(
-            self._h, B, _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(obs_xy), _ptr(obs_nv),
-            *_step_out_ptrs(out, c_eta_slot=True), _ptr(bounds), C.c_void_p(stream))
-        _lib.check(rc, "lipmpc_plan_step_batch")
+        _lib.call("lipmpc_plan_step_batch", h=self._h, B=B, state=state, goal=goal, first_foot=first_foot, delta=delta,
+                  obs_xy=obs_xy, obs_nv=obs_nv, **_named(out, STEP_OUTPUTS), bounds=bounds,
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         return out
 
     def plan_step_batch_c_eta(self, state, goal, first_foot, c_eta_in, delta=None, out=None, with_diag=False, bounds=None,
@@ -307,27 +335,14 @@ class BatchedLipMpc:
             self._check_outputs(out, B)
         self._ensure_workspace(B)
         self._check_warm(B)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.lipmpc_plan_step_batch_c_eta(
-            self._h, B, _ptr(state), _ptr(goal), _ptr(first_foot), _ptr(delta), _ptr(c_eta_in), _ptr(overflow),
-            *_step_out_ptrs(out), _ptr(bounds), C.c_void_p(stream))
-        _lib.check(rc, "lipmpc_plan_step_batch_c_eta")
+        _lib.call("lipmpc_plan_step_batch_c_eta", h=self._h, B=B, state=state, goal=goal, first_foot=first_foot, delta=delta,
+                  c_eta_in=c_eta_in, overflow=overflow, **_named(out, _STEP_OUTPUTS_GIVEN_C_ETA), bounds=bounds,
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         return out
 
     def _check_outputs(self, out, B):
         """caller-supplied output buffers must have the shapes alloc_outputs gives (raw pointers go to the kernel)"""
-        P, dev = self.params, self.device
-        ref = {"U": ((B, P.N, 2), torch.float64), "X": ((B, P.N + 1, 4), torch.float64),
-               "theta": ((B, P.N + 1), torch.float64), "omega": ((B, P.N), torch.float64),
-               "obj": ((B,), torch.float64), "status": ((B,), torch.int32), "iters": ((B,), torch.int32),
-               "active": ((B, P.active_words), torch.int64)}
-        for k, (shape, dt) in ref.items():
-            if k not in out:
-                raise ValueError(f"out['{k}'] missing")
-            _check(out[k], shape, dt, dev, f"out['{k}']")
-        _check(out.get("c_eta"), (B, P.n_obs_max, 4), torch.float64, dev, "out['c_eta']")
-        _check(out.get("diag"), (B, _lib.DIAG_WORDS), torch.float64, dev, "out['diag']")
-        _check(out.get("working"), (B, P.active_words), torch.int64, dev, "out['working']")
+        _check_table(step_outputs(B, self.params), out, self.device, "out")
 
     def advance(self, state, first_foot, out):
         """In place: state <- (A_l x + B_l U[:,0], theta[:,1]), first_foot <- -first_foot for the
@@ -336,11 +351,8 @@ class BatchedLipMpc:
         _check(state, (B, 5), torch.float64, self.device, "state")
         _check(first_foot, (B,), torch.int8, self.device, "first_foot")
         self._check_outputs(out, B)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.lipmpc_advance_batch(self._h, B, _ptr(state), _ptr(first_foot), _ptr(out["U"]),
-                                           _ptr(out["theta"]), _ptr(out["status"]), C.c_void_p(stream))
-        _lib.check(rc, "lipmpc_advance_batch")
-
+        _lib.call("lipmpc_advance_batch", h=self._h, B=B, state=state, first_foot=first_foot, **_named(out, ("U", "theta", "status")),
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
     def fleet_update(self, fleet, out, overflow=None, stop_obj=0.05):
         """One sample of a host-driven fleet loop after ``plan_step_batch(..., out=out)`` on the same stream:
@@ -349,22 +361,12 @@ class BatchedLipMpc:
         n_overflow, sample int32[1], X_pred [B,k_max+1,5], U_pred [B,k_max,3]); the device-side sample counter
         advances by one per call."""
         B, k_max = fleet["state"].shape[0], fleet["U_pred"].shape[1]
-        for name, shape, dt in (("state", (B, 5), torch.float64), ("first_foot", (B,), torch.int8), ("walking", (B,), torch.int8),
-                                ("last_obj", (B,), torch.float64), ("n_steps", (B,), torch.int32), ("last_status", (B,), torch.int32),
-                                ("n_overflow", (B,), torch.int32), ("sample", (1,), torch.int32),
-                                ("X_pred", (B, k_max + 1, 5), torch.float64), ("U_pred", (B, k_max, 3), torch.float64)):
-            if name not in fleet:
-                raise ValueError(f"fleet['{name}'] missing")
-            _check(fleet[name], shape, dt, self.device, f"fleet['{name}']")
+        _check_table(fleet_state(B, k_max), fleet, self.device, "fleet")
         self._check_outputs(out, B)
         _check(overflow, (B,), torch.int32, self.device, "overflow")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.lipmpc_fleet_update_batch(
-            self._h, B, int(k_max), float(stop_obj), _ptr(fleet["state"]), _ptr(fleet["first_foot"]), _ptr(fleet["walking"]),
-            _ptr(fleet["last_obj"]), _ptr(fleet["n_steps"]), _ptr(fleet["last_status"]), _ptr(fleet["n_overflow"]),
-            _ptr(fleet["sample"]), _ptr(fleet["X_pred"]), _ptr(fleet["U_pred"]), _ptr(out["U"]), _ptr(out["theta"]),
-            _ptr(out["omega"]), _ptr(out["obj"]), _ptr(out["status"]), _ptr(overflow), C.c_void_p(stream))
-        _lib.check(rc, "lipmpc_fleet_update_batch")
+        _lib.call("lipmpc_fleet_update_batch", h=self._h, B=B, k_max=int(k_max), stop_obj=float(stop_obj), **_named(fleet, FLEET_STATE),
+                  **_named(out, ("U", "theta", "omega", "obj", "status")), overflow=overflow,
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
     def rollout(self, state0, goal, first_foot, obs_xy=None, obs_nv=None, delta=None, k_max=100, mpc_step=1,
                 stop_obj=0.05, bounds=None):
@@ -374,18 +376,11 @@ class BatchedLipMpc:
         _check(bounds, (B, 4), torch.float64, self.device, "bounds")
         if int(k_max) < 1 or int(mpc_step) < 1:
             raise ValueError("k_max and mpc_step must be positive")
-        dev = self.device
-        out = dict(X_pred=torch.empty((B, k_max + 1, 5), dtype=torch.float64, device=dev),
-                   U_pred=torch.empty((B, k_max, 3), dtype=torch.float64, device=dev),
-                   n_steps=torch.empty((B,), dtype=torch.int32, device=dev),
-                   last_status=torch.empty((B,), dtype=torch.int32, device=dev),
-                   total_iters=torch.empty((B,), dtype=torch.int32, device=dev))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lipmpc_rollout_batch(self._h, B, int(k_max), int(mpc_step), float(stop_obj), _ptr(state0), _ptr(goal),
-                                           _ptr(first_foot), _ptr(delta), _ptr(obs_xy), _ptr(obs_nv), _ptr(out["X_pred"]),
-                                           _ptr(out["U_pred"]), _ptr(out["n_steps"]), _ptr(out["last_status"]),
-                                           _ptr(out["total_iters"]), _ptr(bounds), C.c_void_p(stream))
-        _lib.check(rc, "lipmpc_rollout_batch")
+        table = rollout_outputs(B, k_max)
+        out = _alloc(table, table, self.device)
+        _lib.call("lipmpc_rollout_batch", h=self._h, B=B, k_max=int(k_max), mpc_step=int(mpc_step), stop_obj=float(stop_obj),
+                  state0=state0, goal=goal, first_foot=first_foot, delta=delta, obs_xy=obs_xy, obs_nv=obs_nv, **out, bounds=bounds,
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         return out
 
     def rollout_subgoals(self, state0, sub_goals, n_sub, first_foot, obs_xy=None, obs_nv=None, delta=None, k_max=100,

@@ -1,4 +1,5 @@
 """Shared test helpers (CPU side)."""
+import ctypes as C
 import dataclasses
 import math
 
@@ -519,3 +520,14 @@ def oracle_unknown_env_run(golden_dir, noise_seed, run="Simulation4UnkEnv", k_ma
         st = np.concatenate([A @ st[:4] + B @ r["U"][0], [r["theta"][1]]])
         X.append(st.copy())
     return np.array(X).T, np.array(U).T
+
+
+def raw_call(name, **given):
+    """The raw ctypes call of an entry point, past every check of the Python wrapper, its status returned: the arguments
+    named here, NULL for every pointer that is not, in the order of the binding's signature table."""
+    import lipmpc
+    lib = lipmpc._lib.load()
+    params = lipmpc._lib.SIGNATURES[name][1]
+    assert set(given) <= {n for n, _ in params}, set(given) - {n for n, _ in params}
+    is_pointer = lambda t: t is C.c_void_p or issubclass(t, C._Pointer)
+    return getattr(lib, name)(*[given.get(n) if is_pointer(t) else given[n] for n, t in params])

@@ -12,7 +12,7 @@ import pytest
 import lipmpc
 import lipmpc_oracle as O
 import c_oracle
-from helpers import closed_loop_problems
+from helpers import closed_loop_problems, raw_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,7 +23,57 @@ def _declared_functions():
     return sorted(set(re.findall(r"\b(lipmpc_[a-z_]+)\s*\(", txt)))
 
 
+def _prototypes(path=os.path.join(ROOT, "include", "lipmpc.h")):
+    """{function: (return type, [(C type, parameter name), ...])} of every prototype of the header, C types without
+    ``const`` and with their stars attached (``double*``).  Every prototype there is ``ret name(args);``."""
+    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    protos = {}
+    for ret, name, args in re.findall(r"^[ \t]*([\w \t\*]+?)[ \t]*\b(lipmpc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt, flags=re.M):
+        params = []
+        for a in ([] if args.strip() == "void" else args.split(",")):
+            m = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\**)\s*(\w+)\s*", a)
+            assert m, f"{name}: cannot read the parameter {a.strip()!r}"
+            params.append((m.group(1) + m.group(2), m.group(3)))
+        assert name not in protos, name
+        protos[name] = (re.sub(r"\bconst\s+", "", ret).replace(" ", ""), params)
+    return protos
+
+
+_SCALARS = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int32, C.c_int), "int64_t": (C.c_int64,), "double": (C.c_double,)}
+_STRUCTS = {"lipmpc_params*": lipmpc._lib.LipmpcParamsC, "lipmpc_rrt_params*": lipmpc._lib.LipmpcRrtParamsC}
+
+
+def _fits(ctype, c_type):
+    """The binding's ctype for a C parameter type: the scalar of the same width and kind; for a pointer c_void_p, or a
+    POINTER whose target is the struct of that name (a handle's address: a void pointer)."""
+    if not c_type.endswith("*"):
+        return ctype in _SCALARS.get(c_type, ())
+    if ctype is C.c_void_p:
+        return True
+    return issubclass(ctype, C._Pointer) and ctype._type_ is _STRUCTS.get(c_type, C.c_void_p if c_type.endswith("**") else None)
+
+
+def _signature_mismatches(protos, table):
+    """What the binding's table gets wrong about the header, one line per function."""
+    bad = [f"{n}: in the header, not in the table" for n in protos.keys() - table.keys()]
+    bad += [f"{n}: in the table, not in the header" for n in table.keys() - protos.keys()]
+    for name in protos.keys() & table.keys():
+        (ret, params), (restype, bound) = protos[name], table[name]
+        want_ret = {"void": (None,), "char*": (C.c_char_p,)}.get(ret) or _SCALARS.get(ret, ())
+        if restype not in want_ret:
+            bad.append(f"{name}: returns {ret}, bound as {restype}")
+        if [n for _, n in params] != [n for n, _ in bound]:
+            bad.append(f"{name}: header ({len(params)}) {[n for _, n in params]} != table ({len(bound)}) {[n for n, _ in bound]}")
+            continue
+        bad += [f"{name}: {c_type} {n} bound as {ctype.__name__}" for (c_type, n), (_, ctype) in zip(params, bound)
+                if not _fits(ctype, c_type)]
+    return bad
+
+
 def test_library_exports_every_declared_symbol():
+    """... and the binding states every argument list as the header does: lipmpc._lib.SIGNATURES against the prototypes, per
+    function the return type, the number of parameters, their names in order, and a ctype that fits each C type.  A
+    prototype the parser cannot read fails (every declared name must come out of it)."""
     lib = lipmpc._lib.load()
     names = _declared_functions()
     assert len(names) >= 9
@@ -32,6 +82,33 @@ def test_library_exports_every_declared_symbol():
     assert set(names) == set(lipmpc._lib.EXPORTS)
     assert lib.lipmpc_version() == lipmpc._lib.ABI_VERSION == 5
     assert b"ok" == lib.lipmpc_strerror(0)
+    protos = _prototypes()
+    assert sorted(protos) == names, set(names) ^ set(protos)
+    bad = _signature_mismatches(protos, lipmpc._lib.SIGNATURES)
+    assert not bad, "\n".join(bad)
+    for name, (restype, bound) in lipmpc._lib.SIGNATURES.items():          # load() bound what the table says
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == [t for _, t in bound], name
+
+
+def test_call_names_every_argument_once():
+    """_lib.call refuses before it calls -- a missing or an unknown keyword is a TypeError naming it -- and raises a status
+    with exactly the code the raw ctypes call returns (null arguments: no device is reached)."""
+    call = lipmpc._lib.call
+    with pytest.raises(TypeError, match="'capacity' missing"):
+        call("lipmpc_set_workspace", h=None, workspace=None)
+    with pytest.raises(TypeError, match="no such argument.*'stream'"):
+        call("lipmpc_set_workspace", h=None, workspace=None, capacity=0, stream=None)
+    for name, scalars in (("lipmpc_set_workspace", dict(capacity=0)), ("lipmpc_set_warm_start", dict(capacity=0)),
+                          ("lipmpc_fleet_update_batch", dict(B=1, k_max=4, stop_obj=0.05)),
+                          ("lipmpc_lidar_sense_batch", dict(device=0, B=1, resolution=400, n_env=0, v_env=1, env_shared=1, lidar_range=1.5,
+                                                            eps=0.3, min_samples=3, n_obs_max=12, v_max=32))):
+        nulls = {n: None for n, t in lipmpc._lib.SIGNATURES[name][1] if n not in scalars}
+        rc = raw_call(name, **scalars)
+        assert rc < 0, name
+        with pytest.raises(RuntimeError, match=re.escape(lipmpc._lib.load().lipmpc_strerror(rc).decode())) as e:
+            call(name, **scalars, **nulls)
+        assert e.value.code == rc, (name, e.value.code, rc)
 
 
 def test_loader_refuses_another_abi(tmp_path):
@@ -89,11 +166,12 @@ def test_default_params_are_the_reference_config():
     # split-launch workspace: argument errors without a handle
     assert lib.lipmpc_workspace_bytes(C.c_void_p(0), 4096) < 0 and lib.lipmpc_set_workspace(C.c_void_p(0), C.c_void_p(0), 0) == -1
     # argument errors of the LiDAR entry points never reach a device (no GPU needed)
-    z = C.c_void_p(0)
-    assert lib.lipmpc_lidar_c_eta_batch(0, 1, 360, 0, 1, 1, C.c_double(1.5), C.c_double(0.3), 3, 12, 32, *([z] * 14)) == -1   # no c_eta
-    assert lib.lipmpc_sense_plan_step_batch(z, 1, 360, 0, 1, 1, C.c_double(1.5), C.c_double(0.3), 3, *([z] * 24)) == -1       # no handle
-    one = C.c_void_p(8)                                                                                                        # (never dereferenced)
-    assert lib.lipmpc_lidar_c_eta_batch(0, 1, 360, 70000, 5, 1, C.c_double(1.5), C.c_double(0.3), 3, 12, 32, *([one] * 14)) == -2  # obstacle indices are 16 bits in LDS
+    scan = dict(B=1, resolution=360, n_env=0, v_env=1, env_shared=1, lidar_range=1.5, eps=0.3, min_samples=3)
+    assert raw_call("lipmpc_lidar_c_eta_batch", device=0, n_obs_max=12, v_max=32, **scan) == -1                      # no c_eta
+    assert raw_call("lipmpc_sense_plan_step_batch", **scan) == -1                                                    # no handle
+    one = C.c_void_p(8)                                                                                               # (never dereferenced)
+    pointers = {n: one for n, t in lipmpc._lib.SIGNATURES["lipmpc_lidar_c_eta_batch"][1] if t is C.c_void_p}
+    assert raw_call("lipmpc_lidar_c_eta_batch", device=0, n_obs_max=12, v_max=32, **dict(scan, n_env=70000, v_env=5), **pointers) == -2  # obstacle indices are 16 bits in LDS
 
 
 def test_create_without_gpu_fails_cleanly():

@@ -349,8 +349,8 @@ def test_gpu_per_robot_maps_and_input_limits(golden_dir):
     gives it on its own map; more than 384 obstacles in range, or a ring longer than v_env, is flagged as overflow and
     never read past the kernel's candidate list; bad arguments are refused before any launch."""
     torch = pytest.importorskip("torch")
-    import ctypes as C
     import lipmpc
+    from helpers import raw_call
     d = np.load(os.path.join(golden_dir, "lidar_golden.npz"))
     lr = float(d["lidar_range"][0])
     cases = [i for i in range(len(d["pos"])) if float(d["lidar_range"][i]) == lr][:6]
@@ -405,10 +405,9 @@ def test_gpu_per_robot_maps_and_input_limits(golden_dir):
     torch.cuda.synchronize()
     assert int(o["overflow"][0]) == 1
     # argument errors never reach the device
-    lib = lipmpc._lib.load()
-    z = C.c_void_p(0)
-    assert lib.lipmpc_lidar_sense_batch(0, 1, 400, 0, 1, 1, C.c_double(1.5), C.c_double(0.3), 3, 12, 32, z, z, z, z, z, z, z, z, z, z, z, z) == -1
-    assert lib.lipmpc_lidar_sense_batch(0, 1, 360, 0, 1, 1, C.c_double(1.5), C.c_double(0.3), 3, 12, 99, z, z, z, z, z, z, z, z, z, z, z, z) == -1
+    scan = dict(device=0, B=1, n_env=0, v_env=1, env_shared=1, lidar_range=1.5, eps=0.3, min_samples=3, n_obs_max=12)
+    assert raw_call("lipmpc_lidar_sense_batch", resolution=400, v_max=32, **scan) == -1
+    assert raw_call("lipmpc_lidar_sense_batch", resolution=360, v_max=99, **scan) == -1
 
 
 @pytest.mark.gpu

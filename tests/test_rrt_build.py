@@ -5,6 +5,7 @@ import re
 import subprocess
 
 import lipmpc
+from helpers import raw_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ("rrt_setup_kernel", "rrt_grid_kernel", "rrt_edt_col_kernel", "rrt_edt_row_kernel", "rrt_star_kernel")
@@ -30,7 +31,7 @@ def test_rrt_exports_and_defaults():
         setattr(q, field, bad)
         assert lib.lipmpc_rrt_workspace_bytes(C.byref(q), 1) < 0, field
     assert lib.lipmpc_rrt_default_params(None) < 0
-    assert lib.lipmpc_rrt_plan_batch(0, C.byref(p), 1, *([None] * 2), 0, 3, *([None] * 12), 8, None) < 0
+    assert raw_call("lipmpc_rrt_plan_batch", device=0, p=C.byref(p), B=1, n_obs_max=0, v_max=3, S_max=8) < 0
 
 
 def test_rrt_kernel_resource_report():

@@ -217,6 +217,50 @@ def test_captured_step_survives_growth_and_reregistration(after):
     _assert_same(got_other, ref_other, "eager launch beside a replay")
 
 
+def test_captured_warm_step_survives_record_growth():
+    """T2 for the warm-start record: a warm step captured with a record of B1 = 600 problems keeps its record after
+    set_warm_start grew it to B2 -- the handle keeps every buffer it registered, the record as the workspace and the
+    schedule.  The replay reads and writes the record it was captured with and nothing else (canaries of that record's size
+    stay untouched, the grown record stays zero), and equals, bit for bit, the same two steps run eagerly on a second handle
+    whose record never grew."""
+    N, n_obs, B1, B2 = 8, 10, 600, 1500
+    P = lipmpc.LipMpcParams(N=N, n_obs_max=n_obs, v_max=5, flags=lipmpc.FLAG_WARM_START)
+    sv, never_grew = lipmpc.BatchedLipMpc(P), lipmpc.BatchedLipMpc(P)
+    assert sv.set_warm_start(B1) and never_grew.set_warm_start(B1)
+    args = _batch(N, n_obs, B1, seed=97)
+    st2 = args[0].clone()
+    st2[:, 0] += 0.03
+    st2[:, 2] -= 0.02                                   # the states of the second step
+    kw = dict(with_c_eta=True, with_diag=True, with_working=True)
+    never_grew.plan_step_batch(*args, **kw)
+    ref = never_grew.plan_step_batch(st2, *args[1:], **kw)
+    out = sv.alloc_outputs(B1, **kw)
+    sv.plan_step_batch(*args, out=out)                  # the first step, outside the capture: its result is in the record
+    torch.cuda.synchronize()
+    assert int(np.isin(ref["status"].cpu().numpy(), (0, 4)).sum()) > B1 // 3
+    assert int((sv.warm_record[:, 0] == 1.0).sum()) > B1 // 3          # the second step starts warm
+    old_bytes = 8 * B1 * sv.warm_words
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(g, stream=side):
+            sv.plan_step_batch(*args, out=out)
+    torch.cuda.current_stream().wait_stream(side)
+    assert sv.set_warm_start(B2)
+    torch.cuda.synchronize()
+    canaries = _canaries(old_bytes)
+    args[0].copy_(st2)
+    for k in ("U", "X", "status", "iters", "active"):
+        out[k].zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    _assert_same(out, ref, "warm replay after the record grew")
+    for i, c in enumerate(canaries):
+        assert bool((c == CANARY).all()), f"canary {i} of {len(canaries)} written by the warm replay after the record grew"
+    assert tuple(sv.warm_record.shape) == (B2, sv.warm_words) and not bool(sv.warm_record.any())
+
+
 def test_first_split_launch_inside_a_capture_is_refused():
     """T4: the first split launch of a handle makes its side streams and events, which a capture must not see: it raises a
     RuntimeError before anything is enqueued, and the handle works normally afterwards -- eagerly and captured."""

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import lipmpc  # noqa: E402
 import lipmpc_oracle as O  # noqa: E402
-from helpers import closed_loop_problems  # noqa: E402
+from helpers import closed_loop_problems, raw_call  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 E_ARG, E_UNSUPPORTED = -1, -2
@@ -257,9 +257,9 @@ def test_refusals_and_no_record_unchanged():
         sv.plan_step_batch(*args)
     out = sv.alloc_outputs(B)
     p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    rc = lib.lipmpc_plan_step_batch(sv._h, B, *[p(a) for a in args[:2]], p(args[2]), p(args[5]), p(args[3]), p(args[4]),
-                                    *[p(out[k]) for k in ("U", "X", "theta", "omega", "obj", "status", "iters", "active")],
-                                    None, None, None, None, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = raw_call("lipmpc_plan_step_batch", h=sv._h, B=B, **{k: p(a) for k, a in zip(("state", "goal", "first_foot", "obs_xy", "obs_nv", "delta"), args)},
+                  **{k: p(out[k]) for k in ("U", "X", "theta", "omega", "obj", "status", "iters", "active")},
+                  hip_stream=C.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == E_ARG
     # FLAG_WARM_START without a record: the plain step, bit-identical to the NO_PRESOLVE handle
     res = {}

@@ -4,7 +4,6 @@ LIPMPC_LIB=variants/phase.so LIPMPC_ALLOW_VARIANT=1 python tools/phase_cycles.py
 Every wave books constant-clock time per section in LDS, once per wave pass, whatever subset of its groups is still running
 (lipmpc_kernel.hpp: ph_mark), plus the part of each section spent with ONE group alive -- the tail inside the wave.  Printed:
 mean per wave, per iteration / round, the share of the launch's wave-time that is single-group time, and the slowest waves."""
-import ctypes as C
 import os
 import sys
 
@@ -17,8 +16,6 @@ os.environ.setdefault("LIPMPC_ALLOW_VARIANT", "1")
 import lipmpc  # noqa: E402
 from importlib import import_module  # noqa: E402
 synth = import_module("humanoid-navigation-using-mpc-ldcbf_amd.synth")
-solver_mod = import_module("humanoid-navigation-using-mpc-ldcbf_amd.solver")
-_ptr = solver_mod._ptr
 NAMES = ["iteration head", "reciprocals + K", "factorisation", "predictor rhs + solve", "predictor rows/ratio", "corrector rhs + solve",
          "corrector rows/update", "finish K + factor", "finish equality solve", "finish ratio/exchange", "front end", "outputs"]
 dev = torch.device("cuda", 0)
@@ -36,11 +33,8 @@ def run(tag, N, n_obs, state, goal, foot, obs_xy, obs_nv, delta, flags=0, max_it
     stream = torch.cuda.current_stream(dev).cuda_stream
     for _ in range(2):
         ph.zero_()
-        rc = sv.lib.lipmpc_plan_step_batch(sv._h, B, _ptr(state), _ptr(goal), _ptr(foot), _ptr(delta), _ptr(obs_xy), _ptr(obs_nv),
-                                           _ptr(out["U"]), _ptr(out["X"]), _ptr(out["theta"]), _ptr(out["omega"]), _ptr(out["obj"]),
-                                           _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["active"]), None, None, _ptr(ph), None,
-                                           C.c_void_p(stream))
-        assert rc == 0
+        lipmpc._lib.call("lipmpc_plan_step_batch", h=sv._h, B=B, state=state, goal=goal, first_foot=foot, delta=delta, obs_xy=obs_xy,
+                         obs_nv=obs_nv, **out, working=None, c_eta=None, diag=ph, bounds=None, hip_stream=stream)
     torch.cuda.synchronize()
     p = ph.cpu().numpy()
     w = p[p[:, 28] == 1.0]                              # one record per wave, at the wave's first problem
