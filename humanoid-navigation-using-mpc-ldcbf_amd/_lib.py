@@ -37,6 +37,7 @@ def _sig(restype, params):
 
 
 _STEP_OUT = "U X theta omega obj status iters active working"
+_GRID_SCAN = "resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 eps:f64 min_samples:i32"
 _SCAN = "resolution:i32 n_env:i32 v_env:i32 env_shared:i32 lidar_range:f64 eps:f64 min_samples:i32"
 
 # Every export of include/lipmpc.h with the header's own parameter names: the ONE statement of each argument list on the
@@ -68,6 +69,10 @@ SIGNATURES = {
     "lipmpc_lidar_schedule_words": _sig(C.c_int64, "B:i64"),
     "lipmpc_sense_plan_step_batch": _sig(C.c_int, f"h B:i64 {_SCAN} state goal first_foot delta env_xy env_nv ray_table noise "
                                                   f"c_eta n_inferred overflow schedule {_STEP_OUT} diag bounds hip_stream"),
+    "lipmpc_lidar_grid_c_eta_batch": _sig(C.c_int, f"device:int B:i64 {_GRID_SCAN} n_obs_max:i32 v_max:i32 state occ ray_table noise "
+                                                   "c_eta n_inferred overflow obs_xy obs_nv hits labels hip_stream"),
+    "lipmpc_sense_grid_plan_step_batch": _sig(C.c_int, f"h B:i64 {_GRID_SCAN} state goal first_foot delta occ ray_table noise "
+                                                       f"c_eta n_inferred overflow {_STEP_OUT} diag bounds hip_stream"),
     "lipmpc_rrt_default_params": _sig(C.c_int, "p:rrt_params"),
     "lipmpc_rrt_workspace_bytes": _sig(C.c_int64, "p:rrt_params B:i64"),
     "lipmpc_rrt_plan_batch": _sig(C.c_int, "device:int p:rrt_params B:i64 obs_xy obs_nv n_obs_max:i32 v_max:i32 start goal seed workspace "

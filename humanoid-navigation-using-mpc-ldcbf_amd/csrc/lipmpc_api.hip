@@ -429,6 +429,27 @@ int lipmpc_sense_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resolution
                                       active, working, diag, bounds, hip_stream);
 }
 
+int lipmpc_sense_grid_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                                      const double* origin, const double* cell, double lidar_range, double eps,
+                                      int32_t min_samples, const double* state, const double* goal, const int8_t* first_foot,
+                                      const double* delta, const uint8_t* occ, const double* ray_table, const double* noise,
+                                      double* c_eta, int32_t* n_inferred, int32_t* overflow,
+                                      double* U, double* X, double* theta, double* omega, double* obj, int32_t* status,
+                                      int32_t* iters, uint64_t* active, uint64_t* working, double* diag, const double* bounds,
+                                      void* hip_stream) {
+  if (!h || B < 0) return LIPMPC_E_ARG;
+  if (h->p.n_obs_max < 1) return LIPMPC_E_UNSUPPORTED;        // a handle without obstacle slots has nothing to sense into
+  if (!c_eta || !goal || !first_foot || !U || !X || !theta || !omega || !obj || !status || !iters || !active) return LIPMPC_E_ARG;
+  if (h->warm && B > h->warm_cap) return LIPMPC_E_ARG;       // (refused before the scan is enqueued)
+  const int rc = lipmpc_lidar_grid_c_eta_batch(h->device, B, resolution, W, H, grid_shared, origin, cell, lidar_range, eps, min_samples,
+                                               h->p.n_obs_max, h->p.v_max, state, occ, ray_table, noise, c_eta, n_inferred, overflow,
+                                               nullptr, nullptr, nullptr, nullptr, hip_stream);
+  if (rc != LIPMPC_OK) return rc;
+  // overflow: the clusters did not fit the obstacle slots, or the robot stands in a solid cell -- no plan either way
+  return lipmpc_plan_step_batch_c_eta(h, B, state, goal, first_foot, delta, c_eta, overflow, U, X, theta, omega, obj, status, iters,
+                                      active, working, diag, bounds, hip_stream);
+}
+
 int lipmpc_advance_batch(lipmpc_handle* h, int64_t B, double* state, int8_t* first_foot, const double* U,
                          const double* theta, const int32_t* status, void* hip_stream) {
   if (!h || B < 0) return LIPMPC_E_ARG;

@@ -50,6 +50,18 @@ constexpr int NRUN = RMAX / 16;      // runs of 16 consecutive readings
 constexpr int ECAP = 152;           // edges staged per chunk of the ray phase (5 doubles each, where the points go afterwards)
 static_assert(ECAP * 5 <= 2 * RMAX && ECAP % 2 == 0, "the staged edges live in the point array");
 static_assert(ECAP <= 65535 && RMAX <= 65535, "16-bit edge offsets and point indices");
+constexpr int GRID_WINDOW_CELLS = 2 * RMAX * 8 * 8;      // grid maps: the window of cells around the robot, one bit each, where the edges are staged
+constexpr int GRID_RAYS = 3;         // grid maps: rays a lane marches at once
+constexpr int GRID_STAGE = 8;        // grid maps: window cells a lane fetches per trip of the staging loop
+
+// The occupancy grid of a grid scan (lipmpc_lidar_grid_c_eta_batch)
+struct GridArg {
+  int W, H;                          // cells; cell (i, j) at occ[i * H + j]
+  long stride;                       // W * H for a map per robot, 0 for a shared one
+  double ox, oy, dx, dy;             // origin and cell size
+  int nx, ny;                        // half-width of the staged window in cells: floor(range / cell) + 2
+  const unsigned char* occ;
+};
 
 struct Cand { double x, y; int idx; };
 #ifdef LIPMPC_LIDAR_PHASES
@@ -121,6 +133,8 @@ __device__ __forceinline__ EdgeCp edge_closest(double pvx, double pvy, double ax
   return r;
 }
 
+// The two sense kernels share one body (lipmpc_lidar_body.inc), which differs in section 1 only: the rays are cast against vertex rings
+// (lidar_sense_kernel) or marched through an occupancy grid (lidar_grid_scan_kernel).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void lidar_sense_kernel(
     long B, int R, int n_env, int v_env, long env_stride, double lidar_range, double eps, int min_samples,
     int n_obs_max, int v_max, const double* __restrict__ state, const double* __restrict__ env_xy,
@@ -128,138 +142,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     double* __restrict__ obs_xy, int32_t* __restrict__ obs_nv, double* __restrict__ c_eta, int32_t* __restrict__ n_inferred,
     int32_t* __restrict__ overflow, double* __restrict__ hits_out, int32_t* __restrict__ labels_out,
     int32_t* __restrict__ sched, int dbg_stop) {
-  // LDS: 10.1 KB per wave = 16 waves per CU (the 160 KB of a CU are what caps this kernel's occupancy, not its registers:
-  // the scan is latency-bound, and went from 8 to 16 resident waves per CU with this layout).  One array of points, everything
-  // a lane owns of its own points (coordinates, cluster root) in registers, and the three small tables of the three phases on
-  // one another.
-  __shared__ __attribute__((aligned(16))) double pint_[2 * RMAX];   // ray phase: staged edges; then the readings (x, y), compacted in ray order
-  double* const edge_ = pint_;                   // [ECAP][4]: g = b - a and f = robot - a of every staged edge ...
-  double* const nua_ = pint_ + 4 * ECAP;         // [ECAP]:    ... and g x f, the ray-independent numerator of compute_intersection
-  __shared__ __attribute__((aligned(16))) int comp_[RMAX];          // -1 = no reading; core: component root; else NO_ROOT; hull stage: cluster offsets
-  __shared__ unsigned short cand_[RMAX];         // obstacles that can be hit from here, list order; then the ray of every reading; then member lists
-  __shared__ unsigned short eoff_[66];           // first staged edge of the chunk's candidates
-  __shared__ __attribute__((aligned(16))) double small_[NCC * 3];   // one phase's small table at a time:
-  double (*const candc_)[3] = reinterpret_cast<double (*)[3]>(small_);            // rays: bounding circle (centre, radius) of the first NCC candidates
-  double (*const bb16_)[4] = reinterpret_cast<double (*)[4]>(small_);             // neighbour rows: bounding box (x0, x1, y0, y1) of each run of 16 points
-  int* const roots_ = reinterpret_cast<int*>(small_);                             // components on: cluster roots, ascending [64]
-  unsigned short* const stagei_ = reinterpret_cast<unsigned short*>(small_ + 32); // hulls: [4][VSTAGE] vertices of the rings being marched, as point indices
-  static_assert(NRUN * 4 * 8 <= NCC * 3 * 8 && 32 * 8 + 4 * VSTAGE * 2 <= NCC * 3 * 8, "the small tables share one area");
+#define LIDAR_GRID 0
+#include "lipmpc_lidar_body.inc"
+#undef LIDAR_GRID
+}
 
-  const int lane = threadIdx.x;
-  if ((long)blockIdx.x >= B) return;
-  // Which robot this wave scans: the block index, or -- with an order buffer (include/lipmpc.h) -- the robot the order
-  // kernel of THIS call put at this position: ranked by an estimate of its reading count (lidar_weight_kernel) and dealt out so
-  // that the robots sharing a SIMD are a heavy one with light ones (lidar_order_kernel).  A scan's length varies 3x with the
-  // number of readings, and with the whole batch resident the launch lasts as long as its most loaded SIMD: 94 us as the robots
-  // come, 74 us ranked by the true counts, 85 us ranked by the estimate, ranking included (tools/lidar_order.py).  Any order
-  // gives the same results.
-  long b = blockIdx.x;
-  if (sched && sched[SCHED_VALID] == (int)B) {
-    const long r = sched[SCHED_ORDER + blockIdx.x];
-    if (r >= 0 && r < B) b = r;
-    // the robots of a SIMD come one from each round of `period` launch positions, the heaviest from the first: that one goes
-    // first when the SIMD picks an instruction (the launch lasts as long as its longest scan)
-    const int period = sched[SCHED_PERIOD];
-    if (period > 0) {
-      const long round = blockIdx.x / period;
-      if (round == 0) __builtin_amdgcn_s_setprio(3);
-      else if (round == 1) __builtin_amdgcn_s_setprio(1);
-    }
-  }
-#ifdef LIPMPC_LIDAR_PHASES
-  const unsigned long long t_enter = wall_clock64();
-  if (dbg_stop == 8) {            // placement probe (tools/lidar_placement.py): where the dispatcher put launch position blockIdx.x
-    if (lane == 0) {
-      n_inferred[blockIdx.x] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_REG_HW_ID
-      overflow[blockIdx.x] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 20);       // HW_REG_XCC_ID
-    }
-    for (int i = 0; i < 16; ++i) __builtin_amdgcn_s_sleep(127);                     // stay resident while the grid is placed
-    return;
-  }
-#endif
-  const double x0 = state[b * 5 + 0], y0 = state[b * 5 + 2];
-  const double* exy = env_xy + b * env_stride * (long)n_env * v_env * 2;
-  const int32_t* env = env_nv + b * env_stride * (long)n_env;
-  int n_cand = 0;
-  int in_ovf = 0;                 // inputs beyond what this kernel holds: more than RMAX obstacles in range, rings longer than v_env
-
-  // 1. ray casting -> n_pts readings (hit + noise) compacted in ray order in pint_, the ray of reading k in cand_[k]
-#include "lipmpc_lidar_rays.inc"
-
-  LIDAR_PHASE_END(1);
-  // ---- 2. DBSCAN ------------------------------------------------------------------------------------
-  // The launch lasts as long as its longest scan, and a scan with many readings (quadratically more pair tests, the longest hull)
-  // shares its SIMD with three others: from here on it goes first when the SIMD picks an instruction.
-  if (n_pts > 256) __builtin_amdgcn_s_setprio(3);
-  else if (n_pts > 160) __builtin_amdgcn_s_setprio(2);
-  else if (n_pts > 112) __builtin_amdgcn_s_setprio(1);
-  else __builtin_amdgcn_s_setprio(0);
-  const int NW = (n_pts + 63) >> 6;                      // words / passes actually in use (wave-uniform)
-  const int npad = NW << 6;
-  if (labels_out) for (int i = lane; i < R; i += 64) labels_out[b * R + i] = -2;      // -2 = no reading
-  const double eps2 = eps * eps;
-  unsigned long long vmask[WORDS];                  // which points exist
-#pragma unroll
-  for (int w = 0; w < WORDS; ++w) {
-    const int left = n_pts - w * 64;
-    vmask[w] = left >= 64 ? ~0ull : (left <= 0 ? 0ull : ((1ull << left) - 1ull));
-  }
-  int touch[WORDS];                                  // smallest tree root point lane + 64 k touches (NO_ROOT: none)
-#pragma unroll
-  for (int w = 0; w < WORDS; ++w) touch[w] = NO_ROOT;
-  // 2a. clustering by chains of consecutive readings, where that is provably DBSCAN's answer -> chains, comp_, touch
-#include "lipmpc_lidar_chains.inc"
-  if (chains) __syncthreads();
-  if (!chains) {
-  // 2. the general route: neighbour rows, core flags, connected components -> comp_, touch
-#include "lipmpc_lidar_rows.inc"
-  }      // (!chains)
-  LIDAR_PHASE_END(4);
-  // cluster root of every reading (of this lane's point of every word: nobody else asks for it): own component for cores,
-  // smallest neighbouring core component for the rest
-  int rootr[WORDS];
-#pragma unroll
-  for (int k = 0; k < WORDS; ++k) {
-    const int ci = (k < NW) ? comp_[k * 64 + lane] : -1;
-    rootr[k] = (ci < 0) ? NO_ROOT : ((ci != NO_ROOT) ? ci : touch[k]);
-  }
-  LIDAR_PHASE_END(5);
-  // roots in ascending order = cluster labels 0, 1, ...
-  int n_clusters = 0;
-  for (int w = 0; w < NW; ++w) {
-    const int i = w * 64 + lane;
-    const bool is_root = comp_[i] == i;
-    const unsigned long long ball = __ballot(is_root);
-    if (is_root) {
-      const int k = n_clusters + __popcll(ball & ((1ull << lane) - 1ull));
-      if (k < 64) roots_[k] = i;
-    }
-    n_clusters += __popcll(ball);
-  }
-  __syncthreads();
-  if (labels_out) {
-#pragma unroll
-    for (int w = 0; w < WORDS; ++w) {
-      const int i = w * 64 + lane;
-      if (i >= n_pts) continue;
-      int lab = -1;                                           // -1 noise
-      const int r = rootr[w];
-      if (r != NO_ROOT) for (int k = 0; k < n_clusters && k < 64; ++k) if (roots_[k] == r) lab = k;
-      labels_out[b * R + cand_[i]] = lab;
-    }
-  }
-
-  LIDAR_PHASE_END(3);
-  // 3 + 4. hull per cluster, constraint assembly -> obs_xy / obs_nv / c_eta, n_out, ovf
-#include "lipmpc_lidar_hulls.inc"
-  if (lane == 0) { n_inferred[b] = n_out; overflow[b] = ovf; }
-#ifdef LIPMPC_LIDAR_PHASES
-  if (dbg_stop == 10 && lane == 0) n_inferred[b] = chains ? 1 : 0;      // which route clustered this scan (tools/lidar_wave_times.py)
-  if (dbg_stop == 9 && lane == 0) {      // wave timing (tools/lidar_wave_times.py): start and end on the 100 MHz wall clock, by robot
-    n_inferred[b] = (int)(t_enter & 0x7fffffff);
-    overflow[b] = (int)(wall_clock64() & 0x7fffffff);
-  }
-#endif
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void lidar_grid_scan_kernel(
+    long B, int R, double lidar_range, double eps, int min_samples, int n_obs_max, int v_max, const double* __restrict__ state,
+    const double* __restrict__ ray_table, const double* __restrict__ noise, double* __restrict__ obs_xy,
+    int32_t* __restrict__ obs_nv, double* __restrict__ c_eta, int32_t* __restrict__ n_inferred, int32_t* __restrict__ overflow,
+    double* __restrict__ hits_out, int32_t* __restrict__ labels_out, int dbg_stop, GridArg gm) {
+#define LIDAR_GRID 1
+#include "lipmpc_lidar_body.inc"
+#undef LIDAR_GRID
 }
 
 // Weight of every robot for the launch order of its scan: an ESTIMATE of its reading count -- every ray, if the robot stands
@@ -380,6 +275,18 @@ static int simd_count(int device) {
   return cached[device];
 }
 
+static int lidar_dbg_stop() {
+#ifdef LIPMPC_LIDAR_PHASES
+  // profiling build only (make CXXFLAGS+=-DLIPMPC_LIDAR_PHASES, tools/lidar_phases.py): LIPMPC_LIDAR_STOP=1..7 ends the
+  // kernel after that phase (the grid scan: 6 = window staged, 1 = rays marched); outputs are then undefined.  The shipped
+  // library has no such knob.
+  static const int dbg_stop = getenv("LIPMPC_LIDAR_STOP") ? atoi(getenv("LIPMPC_LIDAR_STOP")) : 0;
+  return dbg_stop;
+#else
+  return 0;
+#endif
+}
+
 static int lidar_launch(int device, int64_t B, int32_t resolution, int32_t n_env, int32_t v_env, int32_t env_shared,
                         double lidar_range, double eps, int32_t min_samples, int32_t n_obs_max, int32_t v_max,
                         const double* state, const double* env_xy, const int32_t* env_nv, const double* ray_table,
@@ -392,13 +299,7 @@ static int lidar_launch(int device, int64_t B, int32_t resolution, int32_t n_env
       (!obs_xy && !c_eta))
     return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-#ifdef LIPMPC_LIDAR_PHASES
-  // profiling build only (make CXXFLAGS+=-DLIPMPC_LIDAR_PHASES, tools/lidar_phases.py): LIPMPC_LIDAR_STOP=1..7 ends the
-  // kernel after that phase; outputs are then undefined.  The shipped library has no such knob.
-  static const int dbg_stop = getenv("LIPMPC_LIDAR_STOP") ? atoi(getenv("LIPMPC_LIDAR_STOP")) : 0;
-#else
-  const int dbg_stop = 0;
-#endif
+  const int dbg_stop = lidar_dbg_stop();
   if (schedule && n_env > 0) {
     // rank the robots first: estimate of the reading counts -> launch positions, a heavy robot with light ones on every SIMD
     hipLaunchKernelGGL(lidar_weight_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)hip_stream, (long)B, resolution, n_env, v_env,
@@ -435,6 +336,32 @@ extern "C" int lipmpc_lidar_c_eta_batch(int device, int64_t B, int32_t resolutio
   if (schedule && B > 0x3fffffff) return LIPMPC_E_UNSUPPORTED;
   return lidar_launch(device, B, resolution, n_env, v_env, env_shared, lidar_range, eps, min_samples, n_obs_max, v_max, state,
                       env_xy, env_nv, ray_table, noise, obs_xy, obs_nv, c_eta, n_inferred, overflow, hits, labels, schedule, hip_stream);
+}
+
+extern "C" int lipmpc_lidar_grid_c_eta_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                                             const double* origin, const double* cell, double lidar_range, double eps,
+                                             int32_t min_samples, int32_t n_obs_max, int32_t v_max, const double* state,
+                                             const uint8_t* occ, const double* ray_table, const double* noise, double* c_eta,
+                                             int32_t* n_inferred, int32_t* overflow, double* obs_xy, int32_t* obs_nv, double* hits,
+                                             int32_t* labels, void* hip_stream) {
+  if (B < 0 || resolution < 1 || resolution > RMAX || W < 1 || H < 1 || n_obs_max < 1 || v_max < 3 || v_max > VSTAGE || !origin ||
+      !cell || !c_eta)
+    return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY) ||
+      !(lidar_range >= 0.0) || !(lidar_range < INFINITY))
+    return LIPMPC_E_ARG;
+  // the window of cells within range of a robot is staged as a bitmap in LDS: (range, cell) pairs whose window does not fit are refused
+  const double nx = floor(lidar_range / dx) + 2.0, ny = floor(lidar_range / dy) + 2.0;
+  if ((2.0 * nx + 1.0) * (2.0 * ny + 1.0) > (double)GRID_WINDOW_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (B == 0) return LIPMPC_OK;
+  if (!state || !occ || !ray_table || !n_inferred || !overflow || (!obs_xy != !obs_nv)) return LIPMPC_E_ARG;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  const GridArg gm{W, H, grid_shared ? 0L : (long)W * H, ox, oy, dx, dy, (int)nx, (int)ny, occ};
+  hipLaunchKernelGGL(lidar_grid_scan_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)hip_stream, (long)B, resolution, lidar_range, eps,
+                     min_samples, n_obs_max, v_max, state, ray_table, noise, obs_xy, obs_nv, c_eta, n_inferred, overflow, hits, labels,
+                     lidar_dbg_stop(), gm);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
 extern "C" int64_t lipmpc_lidar_schedule_words(int64_t B) { return B < 0 ? LIPMPC_E_ARG : SCHED_ORDER + 2L * B; }

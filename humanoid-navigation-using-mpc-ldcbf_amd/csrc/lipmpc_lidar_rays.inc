@@ -165,7 +165,7 @@
   // return one): clustering and hulls then sweep n points instead of RMAX slots.  Order is preserved, so "smallest core index"
   // numbering, border-point assignment and every index tie-break are those of the uncompacted scan.  (The staged edges are
   // dead: the ray loop ends on a barrier.)
-  int n_pts = 0;
+  n_pts = 0;
 #pragma unroll
   for (int p = 0; p < WORDS; ++p) {
 #pragma clang fp contract(off)

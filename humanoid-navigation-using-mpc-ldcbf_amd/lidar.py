@@ -1,8 +1,10 @@
 """LiDAR front end of the unknown-environment variant (BASELINE config 5) — host wrapper of
 lipmpc_lidar_sense_batch and the drop-in HumanoidMPCUnknownEnvironment class
-(HumanoidNavigation/MPC/HumanoidMPCVariants/HumanoidMPCUnknownEnvironment.py:13-68)."""
+(HumanoidNavigation/MPC/HumanoidMPCVariants/HumanoidMPCUnknownEnvironment.py:13-68).  The true map is a list of convex vertex
+rings, as in the reference, or an occupancy grid (GridMap, lipmpc_lidar_grid_c_eta_batch)."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import numpy as np
@@ -36,9 +38,78 @@ SENSOR_OUTPUTS = tuple(sensor_outputs(0, 0, 0, 0))                           # t
 _RING_SCAN_OUTPUTS = tuple(k for k in SENSOR_OUTPUTS if k != "c_eta")       # lipmpc_lidar_sense_batch has no c_eta
 
 
+class GridMap:
+    """An occupancy grid as the true map of a scan (include/lipmpc.h, lipmpc_lidar_grid_c_eta_batch): ``occ`` [W,H] (one map for
+    every robot) or [B,W,H] (one per robot), a tensor or an array, cell (i, j) solid where ``occ[..., i, j]`` is nonzero;
+    cell (i, j) is the rectangle [ox + i dx, ox + (i+1) dx) x [oy + j dy, oy + (j+1) dy) with ``origin`` = (ox, oy) and
+    ``cell`` = (dx, dy) or one size for both.  Everything outside the grid is free."""
+
+    def __init__(self, occ, origin, cell):
+        if isinstance(occ, torch.Tensor):
+            occ = (occ != 0).to(torch.uint8).contiguous()
+        else:
+            occ = np.ascontiguousarray(np.asarray(occ) != 0, dtype=np.uint8)
+        if occ.ndim not in (2, 3) or min(occ.shape) < 1:
+            raise ValueError("occ must be [W,H] or [B,W,H] with at least one cell")
+        self.occ = occ
+        self.origin = (float(origin[0]), float(origin[1]))
+        self.cell = (float(cell), float(cell)) if np.isscalar(cell) else (float(cell[0]), float(cell[1]))
+        if not (0.0 < self.cell[0] < math.inf and 0.0 < self.cell[1] < math.inf):
+            raise ValueError("cell sizes must be positive and finite")
+        self._origin_c, self._cell_c = (C.c_double * 2)(*self.origin), (C.c_double * 2)(*self.cell)      # read by the C call
+
+    shared = property(lambda self: self.occ.ndim == 2)
+    W = property(lambda self: int(self.occ.shape[-2]))
+    H = property(lambda self: int(self.occ.shape[-1]))
+
+    def _on(self, device):
+        """Is ``occ`` a tensor on ``device``?  ("cuda" names the current device: the same place as its "cuda:i".)"""
+        index = lambda d: torch.cuda.current_device() if d.type == "cuda" and d.index is None else d.index
+        device = torch.device(device)
+        return isinstance(self.occ, torch.Tensor) and self.occ.device.type == device.type and index(self.occ.device) == index(device)
+
+    def to(self, device):
+        """The same map with ``occ`` as a tensor on ``device``."""
+        if self._on(device):
+            return self
+        return GridMap(torch.as_tensor(self.occ, device=device), self.origin, self.cell)
+
+    @classmethod
+    def from_planner(cls, out, b):
+        """The grid problem ``b`` of ``RrtStarPlanner.plan_batch(..., with_grids=True)`` was planned on (``out``: that call's
+        dict, with grid_dims, occ_d2 and grid_bounds).  The planner's cell (i, j) is the POINT min + (i * (max - min)) / W
+        (include/lipmpc.h): here it is the centre of a cell of size (max - min) / W, so origin = min - cell / 2; the cells with
+        occ_d2 = 0 are the solid ones."""
+        W1, H1 = (int(v) for v in out["grid_dims"][b].cpu())
+        min_x, max_x, min_y, max_y = (float(v) for v in out["grid_bounds"][b].cpu())
+        cell = ((max_x - min_x) / (W1 - 1), (max_y - min_y) / (H1 - 1))
+        occ = (out["occ_d2"][b, : W1 * H1] == 0).reshape(W1, H1)
+        return cls(occ, (min_x - cell[0] / 2, min_y - cell[1] / 2), cell)
+
+    def _args(self, B, device):
+        """The map's arguments of the C calls, for a batch of B robots."""
+        occ = self.occ
+        if not self._on(device) or (not self.shared and occ.shape[0] != B):
+            raise ValueError(f"grid: occ must be a tensor on {device}, [W,H] or [B,W,H] with B = {B} (GridMap.to)")
+        return dict(W=self.W, H=self.H, grid_shared=int(self.shared), origin=C.addressof(self._origin_c),
+                    cell=C.addressof(self._cell_c), occ=occ)
+
+
 class LidarSensor:
     """Batched range_finder(): scan -> noise -> DBSCAN -> hulls, one wavefront per robot, rings in the layout
-    BatchedLipMpc.plan_step_batch consumes."""
+    BatchedLipMpc.plan_step_batch consumes.  ``LidarSensor.from_grid``: the same sensor over an occupancy grid."""
+
+    @classmethod
+    def from_grid(cls, grid, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32, device=None):
+        """A sensor whose true map is the GridMap ``grid`` (shared, or one map per robot of the batches it will scan): ``sense``
+        (with ``c_eta=True``), ``sense_plan_step`` and ``alloc_outputs`` as for rings, same return dicts.  The robots are scanned
+        in index order (no ``schedule``).  A robot standing in a solid cell gets no scan: n_inferred = 0, overflow = 1.  A
+        (range, cell) pair whose window of cells within range exceeds 49152 cells is refused (RuntimeError, code -2)."""
+        sn = cls([], lidar_range, resolution, n_obs_max, v_max, device)
+        sn.grid = grid.to(sn.device)
+        return sn
+
+    grid = None                # the GridMap of a sensor made by from_grid
 
     def __init__(self, env_rings, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32, device=None):
         if not torch.cuda.is_available():
@@ -74,7 +145,7 @@ class LidarSensor:
         return torch.zeros((int(self.lib.lipmpc_lidar_schedule_words(B)),), dtype=torch.int32, device=self.device)
 
     def sense(self, state, noise=None, with_debug=False, out=None, env_xy=None, env_nv=None, c_eta=False, rings=True,
-              schedule="auto"):
+              schedule="auto", grid=None):
         """state [B,5] device tensor; noise [B,resolution,2] or None -> dict(n_inferred, overflow[, obs_xy, obs_nv][, c_eta]
         [, hits, labels]).  ``c_eta=True``: the constraint assembly runs in the same launch (lipmpc_lidar_c_eta_batch) and
         the dict carries c_eta [B,n_obs_max,4] = (c, eta) of every inferred hull at the robot's CoM -- what
@@ -87,7 +158,9 @@ class LidarSensor:
         of ``make_schedule`` handed to launches on two streams, or to two graphs replayed concurrently, is a caller's bug.
         Vertex slots beyond obs_nv keep whatever an earlier call left there when ``out`` is reused.
         ``env_xy`` [B,n_env,v_env,2] / ``env_nv`` [B,n_env] (device tensors): one true map PER ROBOT instead of the
-        sensor's shared map (env_shared = 0 of the C ABI)."""
+        sensor's shared map (env_shared = 0 of the C ABI).
+        A sensor over a grid (``from_grid``) scans through lipmpc_lidar_grid_c_eta_batch: ``c_eta=True`` is required, ``grid``
+        (a GridMap on the sensor's device) replaces the sensor's map for this call, ``schedule`` must be "auto" or None."""
         B, dev = state.shape[0], self.device
         if out is None:
             out = self.alloc_outputs(B, with_debug, rings=rings or not c_eta, c_eta=c_eta)
@@ -96,6 +169,14 @@ class LidarSensor:
         _check(state, (B, 5), torch.float64, dev, "state", required=True)
         _check(noise, (B, self.resolution, 2), torch.float64, dev, "noise")
         stream = torch.cuda.current_stream(dev).cuda_stream
+        grid = self.grid if grid is None else grid
+        if grid is not None:
+            if not want_ce or env_xy is not None or not (schedule is None or schedule == "auto"):
+                raise ValueError("a grid scan assembles the half-spaces (c_eta=True), takes no rings as its map and no schedule")
+            _lib.call("lipmpc_lidar_grid_c_eta_batch", device=self.device_index, B=B, resolution=self.resolution, **grid._args(B, dev),
+                      lidar_range=self.lidar_range, eps=DBSCAN_EPS, min_samples=DBSCAN_MIN_SAMPLES, n_obs_max=self.n_obs_max,
+                      v_max=self.v_max, state=state, ray_table=self.table, noise=noise, **_named(out, SENSOR_OUTPUTS), hip_stream=stream)
+            return out
         n_env, v_env, shared, exy, env = self.n_env, self.v_env, 1, self.env_xy, self.env_nv
         if env_xy is not None:
             if (env_xy.dim() != 4 or env_xy.shape[0] != B or env_xy.shape[3] != 2 or env_nv is None
@@ -156,6 +237,15 @@ class LidarSensor:
                                      or schedule.numel() != int(self.lib.lipmpc_lidar_schedule_words(B))):
             raise ValueError("schedule: a buffer of make_schedule(B) for this B")
         solver._ensure_workspace(B)
+        if self.grid is not None:
+            if schedule is not None:
+                raise ValueError("a grid scan takes no schedule")
+            _lib.call("lipmpc_sense_grid_plan_step_batch", h=solver._h, B=B, resolution=self.resolution, **self.grid._args(B, self.device),
+                      lidar_range=self.lidar_range, eps=DBSCAN_EPS, min_samples=DBSCAN_MIN_SAMPLES, state=state, goal=goal,
+                      first_foot=first_foot, delta=delta, ray_table=self.table, noise=noise, **_named(sen, handed_over),
+                      **_named(out, _STEP_OUTPUTS_GIVEN_C_ETA), bounds=bounds,
+                      hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+            return sen, out
         _lib.call("lipmpc_sense_plan_step_batch", h=solver._h, B=B, resolution=self.resolution, n_env=self.n_env, v_env=self.v_env,
                   env_shared=1, lidar_range=self.lidar_range, eps=DBSCAN_EPS, min_samples=DBSCAN_MIN_SAMPLES, state=state, goal=goal,
                   first_foot=first_foot, delta=delta, env_xy=self.env_xy, env_nv=self.env_nv, ray_table=self.table, noise=noise,
@@ -234,12 +324,18 @@ class UnknownEnvFleet:
     replayed.  One MPC solve per sample (sampling_time = DELTA_T), the reference's stop rule (previous objective <
     0.05) and stop-on-failed-solve per robot.  ``warm_start=True``: every solve starts from the robot's previous step,
     shifted by one stage (the reference's seeding, HumanoidMpc.py:448-455), through a warm-start record per robot that each
-    run zeroes before its first sample (N >= 2, at most 14 obstacle slots)."""
+    run zeroes before its first sample (N >= 2, at most 14 obstacle slots).  ``grid=GridMap`` instead of ``env_rings``: the same
+    loop over an occupancy grid (a robot that walks into a solid cell stops with STATUS_SENSOR_OVERFLOW)."""
 
-    def __init__(self, env_rings, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
-                 exact=False, interior_tol=1e-6, device=None, warm_start=False):
+    def __init__(self, env_rings=None, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
+                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None):
         from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR, FLAG_WARM_START
-        self.sensor = LidarSensor(env_rings, lidar_range, resolution, n_obs_max, v_max, device)
+        if (env_rings is None) == (grid is None):
+            raise ValueError("the true map: env_rings or grid")
+        if grid is not None:
+            self.sensor = LidarSensor.from_grid(grid, lidar_range, resolution, n_obs_max, v_max, device)
+        else:
+            self.sensor = LidarSensor(env_rings, lidar_range, resolution, n_obs_max, v_max, device)
         self.warm_start = bool(warm_start)
         self.solver = BatchedLipMpc(LipMpcParams(N=N_horizon, n_obs_max=n_obs_max, v_max=v_max,
                                                  flags=(0 if exact else FLAG_INTERIOR) | (FLAG_WARM_START if warm_start else 0),
@@ -266,7 +362,8 @@ class UnknownEnvFleet:
                   sen=sn.alloc_outputs(B, rings=False, c_eta=True),      # hulls stay in the scan kernel: only (c, eta) rows reach HBM
                   out=sv.alloc_outputs(B), nbuf=None if noise_mode == "none" else torch.zeros((B, sn.resolution, 2), **f64),
                   gen=torch.Generator(device=dev) if noise_mode == "seeded" else None, graph=None,
-                  sched=sn.make_schedule(B))                 # order buffer: every scan ranks its robots before it starts them
+                  # order buffer: every scan of rings ranks its robots before it starts them (a grid is scanned in index order)
+                  sched=sn.make_schedule(B) if sn.grid is None else None)
         self._plan = pl
         return pl
 
@@ -275,7 +372,8 @@ class UnknownEnvFleet:
         """state0 [B,5], goal [B,2], first_foot [B] int8.  noise: "seeded" (N(0, 0.01) per reading from a generator
         seeded with noise_seed), None (noiseless) or a tensor [k_max,B,resolution,2].  Returns dict(X_pred
         [B,k_max+1,5], U_pred [B,k_max,3], n_steps [B] solved samples, last_status [B] (STATUS_SENSOR_OVERFLOW = 5: the
-        robot was stopped because a scan's clusters did not fit the obstacle slots), overflow [B] number of such scans).
+        robot was stopped because a scan's clusters did not fit the obstacle slots, or -- on a grid -- because it stands in a solid
+        cell), overflow [B] number of such scans).
         One sample = noise draw (seeded mode), scan + constraint assembly, step solve, fleet update; with ``use_graph``
         it is captured once per run shape in a HIP graph (kept by the object) and replayed k_max times back to back.
         The returned tensors are the object's buffers: the next ``run`` of the same shape overwrites them."""

@@ -78,7 +78,8 @@ class RrtStarPlanner:
         problem, or None (= the planner's seed).  S_max: sub-goal slots per problem (default n + 1, always enough).
         Returns dict(sub_goals [B,S_max,2] (rows past n_sub are 0), n_sub [B], status [B] (RRT_*), path_cost [B]) as
         device tensors; with_tree adds tree [B,n+2,4], with_grids grid_dims [B,2], occ_d2 [B,max_cells] (squared
-        distance, 0 = occupied) and cost_grid [B,max_cells] (layouts: lipmpc_rrt_plan_batch, include/lipmpc.h)."""
+        distance, 0 = occupied) and cost_grid [B,max_cells] (layouts: lipmpc_rrt_plan_batch, include/lipmpc.h), and grid_bounds
+        [B,4] = (min_x, max_x, min_y, max_y), the world box of every grid (what ``GridMap.from_planner`` places the cells by)."""
         goal = self._dev(goal, torch.float64)
         if goal is None or goal.dim() != 2 or goal.shape[1] != 2:
             raise ValueError("goal must be [B,2]")
@@ -106,6 +107,8 @@ class RrtStarPlanner:
         want = dict(grid_dims=with_grids, occ_d2=with_grids, cost_grid=with_grids, tree=with_tree)
         table = plan_outputs(B, S_max, self.max_cells, int(self.params.n_samples))
         out = _alloc(table, [k for k, (_, _, required) in table.items() if required or want[k]], self.device, torch.zeros)
+        if with_grids:
+            out["grid_bounds"] = self._grid_bounds(goal, xy, nv, st)
         if B == 0:
             return out
         _lib.call("lipmpc_rrt_plan_batch", device=self.device_index, p=C.byref(self.params), B=B, obs_xy=xy, obs_nv=nv, n_obs_max=n_obs,
@@ -113,6 +116,24 @@ class RrtStarPlanner:
                   S_max=S_max, hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         self.last = out
         return out
+
+    def _grid_bounds(self, goal, xy, nv, st):
+        """[B,4] (min_x, max_x, min_y, max_y) of every problem's grid, by the rule of lipmpc_rrt_plan_batch (include/lipmpc.h):
+        min / max over the start (None = the origin), the goal and every ring vertex, -/+ the margin.  min, max and one
+        subtraction / addition: the same doubles as the kernel's (tests/test_lidar_grid_gpu.py holds the world coordinates of
+        the device's sub-goals to them bit for bit)."""
+        B = goal.shape[0]
+        pts = torch.stack([torch.zeros_like(goal) if st is None else st, goal], 1)                     # [B,2,2]
+        if xy is not None and xy.shape[1] > 0:
+            valid = (torch.arange(xy.shape[2], device=self.device)[None, None, :] < nv[:, :, None]).reshape(B, -1, 1)
+            v = xy.reshape(B, -1, 2)
+            inf = torch.full_like(v, float("inf"))
+            lo = torch.cat([pts, torch.where(valid, v, inf)], 1).amin(1)
+            hi = torch.cat([pts, torch.where(valid, v, -inf)], 1).amax(1)
+        else:
+            lo, hi = pts.amin(1), pts.amax(1)
+        m = float(self.params.margin)
+        return torch.stack([lo[:, 0] - m, hi[:, 0] + m, lo[:, 1] - m, hi[:, 1] + m], 1)
 
     def plan(self, goal, rings, start=None, seed=None, S_max=None, with_tree=False, with_grids=False):
         """One problem from a list of (V,2) rings (any V >= 1)."""

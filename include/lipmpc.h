@@ -339,6 +339,56 @@ int lipmpc_sense_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resolution
                                  int32_t* iters, uint64_t* active, uint64_t* working, double* diag, const double* bounds,
                                  void* hip_stream);
 
+/* The unknown-environment front end on an OCCUPANCY GRID (backward-compatible addition): lipmpc_lidar_c_eta_batch with the true
+ * map given as cells instead of vertex rings.  Only the ray casting differs; the readings then go through the same clustering,
+ * hulls and constraint assembly in the same launch, and every output means what it means there.  (Convex hulls of clusters
+ * over-cover concave walls, as they do on adjoining polygons.)
+ *  occ    uint8, [W,H] if grid_shared else [B,W,H], DEVICE: cell (i, j) at occ[i * H + j], solid if nonzero
+ *  origin (ox, oy), cell (dx, dy): two doubles each, HOST pointers read during the call; dx, dy > 0.  Cell (i, j) is the
+ *         rectangle [ox + i dx, ox + (i+1) dx) x [oy + j dy, oy + (j+1) dy); everything outside the grid is free (a robot
+ *         outside the grid sees into it)
+ *  the rest as lipmpc_lidar_c_eta_batch; the robots are scanned in index order (no schedule).
+ * THE SCAN, in IEEE double, no contraction, division and square root correctly rounded, every expression evaluated as written:
+ *  - robot cell: ci = floor((x0 - ox) / dx), cj = floor((y0 - oy) / dy).  Unless |ci|, |cj| < 2^30 (NaN included) the robot
+ *    has no reading.  If (ci, cj) is a solid cell of the grid NO SCAN IS MADE: n_inferred = 0, no reading, overflow = 1
+ *    (lipmpc_sense_grid_plan_step_batch then gives LIPMPC_STATUS_SENSOR_OVERFLOW and NaN outputs: the scan is unusable).
+ *  - ray i, as the polygon scan: e = (x0 + range * cos_i, y0 + range * sin_i), d = (e_x - x0, e_y - y0), points x0 + t d.
+ *  - boundary crossings: with inv_x = 1 / d_x, the crossing of the x boundary of index a is t = ((ox + a * dx) - x0) * inv_x
+ *    (a converted to double; y likewise with oy, dy, y0, inv_y).  The ray starts in (ci, cj) with t_x the crossing of
+ *    a = ci + 1 if d_x > 0, of a = ci if d_x < 0, and +inf if d_x = 0; t_y likewise.
+ *  - step: if t_x <= t_y (a tie goes to x) then t = t_x, ci += sign(d_x), t_x = the crossing of the next boundary that way
+ *    (a = ci + 1 if d_x > 0 else ci, with the new ci); else the same in y.  The ray is now in cell (ci, cj), entered at t.
+ *  - stop, without a reading: unless t <= 1 (NaN included), or when the cell is more than floor(range / dx) + 2 columns or
+ *    floor(range / dy) + 2 rows from the robot's cell (no reading can lie there).
+ *  - hit: the first solid cell of the grid so entered ends the ray.  Its reading q lies ON the boundary that was crossed:
+ *    entered in x through the boundary of index a, q = (ox + a * dx, y0 + t * d_y); entered in y, q = (x0 + t * d_x,
+ *    oy + a * dy) -- readings on one face of a wall are exactly collinear, as the polygon scan's are on an axis-parallel
+ *    edge.  It is kept only if sqrt((q_x - x0)^2 + (q_y - y0)^2) < range, strictly, as in the polygon scan.  Noise is added
+ *    to kept readings.
+ * Reproduced bit for bit in numpy by tests/grid_lidar_oracle.py.
+ * The window of cells a ray can reach, (2 floor(range / dx) + 5) x (2 floor(range / dy) + 5), is staged per robot as a
+ * bitmap in the kernel's LDS: a (range, cell) pair whose window exceeds 49152 cells is refused with LIPMPC_E_UNSUPPORTED
+ * before anything is enqueued.  Other refusals (LIPMPC_E_ARG): resolution outside 1..384, W or H < 1, a cell size that is
+ * not positive and finite, a range that is negative or not finite, a null origin / cell / c_eta. */
+int lipmpc_lidar_grid_c_eta_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                                  const double* origin, const double* cell, double lidar_range, double eps,
+                                  int32_t min_samples, int32_t n_obs_max, int32_t v_max, const double* state,
+                                  const uint8_t* occ, const double* ray_table, const double* noise, double* c_eta,
+                                  int32_t* n_inferred, int32_t* overflow, double* obs_xy, int32_t* obs_nv, double* hits,
+                                  int32_t* labels, void* hip_stream);
+
+/* lipmpc_sense_plan_step_batch on an occupancy grid: lipmpc_lidar_grid_c_eta_batch (n_obs_max / v_max from the handle), then on
+ * the same stream lipmpc_plan_step_batch_c_eta against those half-spaces and the scan's overflow flags -- a robot whose
+ * clusters did not fit, or that stands in a solid cell, gets LIPMPC_STATUS_SENSOR_OVERFLOW and NaN outputs. */
+int lipmpc_sense_grid_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                                      const double* origin, const double* cell, double lidar_range, double eps,
+                                      int32_t min_samples, const double* state, const double* goal, const int8_t* first_foot,
+                                      const double* delta, const uint8_t* occ, const double* ray_table, const double* noise,
+                                      double* c_eta, int32_t* n_inferred, int32_t* overflow,
+                                      double* U, double* X, double* theta, double* omega, double* obj, int32_t* status,
+                                      int32_t* iters, uint64_t* active, uint64_t* working, double* diag, const double* bounds,
+                                      void* hip_stream);
+
 /* RRT* SUB-GOAL PLANNER (backward-compatible addition): the global planner of HumanoidMPCWithRRT
  * (HumanoidMPCVariants/HumanoidMPCWithRRT.py:21-135) for B independent problems, one workgroup per problem.  Per problem b:
  *  - bounds: min / max over {start_x, goal_x, every ring vertex x} -/+ margin, the same for y (the reference's origin is
