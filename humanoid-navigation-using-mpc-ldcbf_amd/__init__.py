@@ -5,5 +5,6 @@ from .solver import (BatchedLipMpc, LipMpcParams, pack_rings, unpack_active, FLA
                      STATUS_SENSOR_OVERFLOW)
 from .compat import HumanoidMPC, HumanoidMPCCustomLCBF, HumanoidMPCWithRRT  # noqa: F401
 from .lidar import GridMap, LidarSensor, HumanoidMPCUnknownEnvironment, UnknownEnvFleet, ray_table  # noqa: F401
+from .neighbours import NeighbourRows  # noqa: F401
 from .planner import (RrtStarPlanner, RRT_FOUND, RRT_NO_PATH, RRT_START_OCCUPIED, RRT_GOAL_OCCUPIED,  # noqa: F401
                       RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, RRT_PATH_OVERFLOW, RRT_STATUS_NAMES)

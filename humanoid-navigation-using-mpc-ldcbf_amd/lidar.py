@@ -325,10 +325,13 @@ class UnknownEnvFleet:
     0.05) and stop-on-failed-solve per robot.  ``warm_start=True``: every solve starts from the robot's previous step,
     shifted by one stage (the reference's seeding, HumanoidMpc.py:448-455), through a warm-start record per robot that each
     run zeroes before its first sample (N >= 2, at most 14 obstacle slots).  ``grid=GridMap`` instead of ``env_rings``: the same
-    loop over an occupancy grid (a robot that walks into a solid cell stops with STATUS_SENSOR_OVERFLOW)."""
+    loop over an occupancy grid (a robot that walks into a solid cell stops with STATUS_SENSOR_OVERFLOW).
+    ``avoid=NeighbourRows(...)``: the robots keep apart -- every sample each robot's nearest neighbours in the batch are
+    appended to its scan's half-spaces as LDCBF rows (lipmpc_neighbour_c_eta_batch) before the solve; a stopped robot stays
+    where it is and stays an obstacle."""
 
     def __init__(self, env_rings=None, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
-                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None):
+                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None):
         from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR, FLAG_WARM_START
         if (env_rings is None) == (grid is None):
             raise ValueError("the true map: env_rings or grid")
@@ -342,6 +345,9 @@ class UnknownEnvFleet:
                                                  tol_interior=interior_tol),
                                     self.sensor.device_index)
         self.device = self.sensor.device
+        if avoid is not None and avoid.device != self.device:
+            raise ValueError("avoid: a NeighbourRows on the fleet's device")
+        self.avoid = avoid
 
     def _plan_for(self, B, k_max, noise_mode, have_delta, stop_obj, use_graph):
         """Buffers (and, once captured, the HIP graph of one sample) of a run shape; kept across ``run`` calls, so a
@@ -364,6 +370,9 @@ class UnknownEnvFleet:
                   gen=torch.Generator(device=dev) if noise_mode == "seeded" else None, graph=None,
                   # order buffer: every scan of rings ranks its robots before it starts them (a grid is scanned in index order)
                   sched=sn.make_schedule(B) if sn.grid is None else None)
+        if self.avoid is not None:
+            pl.update(nbr=self.avoid.alloc_outputs(B), n_crowded=torch.zeros((B,), dtype=torch.int32, device=dev),
+                      crowded=torch.zeros((B,), dtype=torch.bool, device=dev))
         self._plan = pl
         return pl
 
@@ -373,11 +382,12 @@ class UnknownEnvFleet:
         seeded with noise_seed), None (noiseless) or a tensor [k_max,B,resolution,2].  Returns dict(X_pred
         [B,k_max+1,5], U_pred [B,k_max,3], n_steps [B] solved samples, last_status [B] (STATUS_SENSOR_OVERFLOW = 5: the
         robot was stopped because a scan's clusters did not fit the obstacle slots, or -- on a grid -- because it stands in a solid
-        cell), overflow [B] number of such scans).
+        cell), overflow [B] number of such scans).  With ``avoid`` also n_crowded [B]: the number of samples in which a
+        neighbour in range of the robot got no row (n_near > n_rows: more neighbours than k_rows or than free slots).
         One sample = noise draw (seeded mode), scan + constraint assembly, step solve, fleet update; with ``use_graph``
         it is captured once per run shape in a HIP graph (kept by the object) and replayed k_max times back to back.
         The returned tensors are the object's buffers: the next ``run`` of the same shape overwrites them."""
-        dev, sv, sn = self.device, self.solver, self.sensor
+        dev, sv, sn, avoid = self.device, self.solver, self.sensor, self.avoid
         B = state0.shape[0]
         mode = "none" if noise is None else ("seeded" if isinstance(noise, str) else "given")
         pl = self._plan_for(B, int(k_max), mode, delta is not None, stop_obj, use_graph)
@@ -392,6 +402,8 @@ class UnknownEnvFleet:
             for n in ("n_steps", "last_status", "n_overflow", "sample"):
                 fl[n].zero_()
             fl["X_pred"].zero_(); fl["U_pred"].zero_(); fl["X_pred"][:, 0] = state0
+            if avoid is not None:
+                pl["n_crowded"].zero_()
             sv.reset_warm_start()                            # every run starts cold (no-op without a record)
             if gen is not None:
                 gen.manual_seed(int(noise_seed))
@@ -401,7 +413,16 @@ class UnknownEnvFleet:
             # and the trajectory row: one bookkeeping launch (lipmpc_fleet_update_batch)
             if gen is not None:
                 nbuf.normal_(0.0, NOISE_STD, generator=gen)
-            sn.sense_plan_step(sv, fl["state"], pl["goal"], fl["first_foot"], nbuf, pl["delta"], sen=sen, out=out, schedule=pl["sched"])
+            if avoid is None:
+                sn.sense_plan_step(sv, fl["state"], pl["goal"], fl["first_foot"], nbuf, pl["delta"], sen=sen, out=out, schedule=pl["sched"])
+            else:
+                # scan -> neighbour rows behind the scan's -> solve, back to back on the one stream
+                sn.sense(fl["state"], nbuf, out=sen, c_eta=True, rings=False, schedule=pl["sched"])
+                nbr = avoid.append(fl["state"], sen["c_eta"], first_slot=sen["n_inferred"], out=pl["nbr"])
+                torch.gt(nbr["n_near"], nbr["n_rows"], out=pl["crowded"])
+                pl["n_crowded"].add_(pl["crowded"])
+                sv.plan_step_batch_c_eta(fl["state"], pl["goal"], fl["first_foot"], sen["c_eta"], pl["delta"], out=out,
+                                         overflow=sen["overflow"])
             sv.fleet_update(fl, out, overflow=sen["overflow"], stop_obj=stop_obj)
 
         if use_graph and pl["graph"] is None:
@@ -427,5 +448,8 @@ class UnknownEnvFleet:
                 pl["graph"].replay()
             else:
                 sample()
-        return dict(X_pred=fl["X_pred"], U_pred=fl["U_pred"], n_steps=fl["n_steps"], last_status=fl["last_status"],
-                    overflow=fl["n_overflow"])
+        res = dict(X_pred=fl["X_pred"], U_pred=fl["U_pred"], n_steps=fl["n_steps"], last_status=fl["last_status"],
+                   overflow=fl["n_overflow"])
+        if avoid is not None:
+            res["n_crowded"] = pl["n_crowded"]
+        return res

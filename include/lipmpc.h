@@ -34,7 +34,8 @@ extern "C" {
                                 *    working set moves to the new optional output `working`, diag is [B,8],
                                 *    + lipmpc_set_workspace / lipmpc_workspace_bytes;
                                 *    backward-compatible additions since: + lipmpc_set_warm_start / lipmpc_warm_words;
-                                *    + lipmpc_rrt_default_params / lipmpc_rrt_workspace_bytes / lipmpc_rrt_plan_batch */
+                                *    + lipmpc_rrt_default_params / lipmpc_rrt_workspace_bytes / lipmpc_rrt_plan_batch;
+                                *    + lipmpc_neighbour_workspace_bytes / lipmpc_neighbour_c_eta_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -449,6 +450,50 @@ int lipmpc_rrt_plan_batch(int device, const lipmpc_rrt_params* p, int64_t B, con
                           void* workspace, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                           int32_t* grid_dims, int32_t* occ_d2, double* cost_grid, double* tree, int32_t S_max,
                           void* hip_stream);
+
+/* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
+ * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
+ * c_eta, in the form lipmpc_plan_step_batch_c_eta solves against -- after the rows of a scan (first_slot = the scan's
+ * n_inferred), or on their own.  All pointers are DEVICE pointers; asynchronous on hip_stream; no host synchronisation and no
+ * allocation, so the call can be captured in a graph.  Evaluated in IEEE double, no contraction, division and square root
+ * correctly rounded, every expression as written.
+ *  state      [B,5]  only (p_x, p_y) are read
+ *  radius     [B]    body radius of each robot
+ *  group      [B] int32 or NULL (= one world): only robots of equal group see each other
+ *  first_slot [B] int32 or NULL (= 0): first free slot of robot b's c_eta; values outside 0..n_obs_max are taken as the
+ *             nearer end of that range
+ *  workspace  lipmpc_neighbour_workspace_bytes(B) bytes, contents arbitrary on entry; calls sharing one must be stream-ordered
+ * ABSENT: a robot with group < 0, a non-finite coordinate, or a negative or non-finite radius.  It neither sees nor is seen:
+ *  n_rows = n_near = 0 (its slots from first_slot on are zeroed like everybody's).
+ * RANGE AND ORDER: for present i != j of one group, dx = x_i - x_j, dy = y_i - y_j, d2 = dx*dx + dy*dy, dist = sqrt(d2);
+ *  j is in range iff dist < sense_range (strictly, as the LiDAR's readings).  n_near[i] = the number in range.  Robot i's
+ *  neighbours are the in-range j in ascending (d2, j) order; n_rows[i] = min(k_rows, n_obs_max - first_slot[i], n_near[i]).
+ * ROW r of robot i, for its r-th neighbour j, at slot first_slot[i] + r:
+ *    rs = r_i + r_j;  offset = rs + share * (dist - rs);  eta = (dx / dist, dy / dist);
+ *    c = (x_j + offset * eta_x, y_j + offset * eta_y);  stored (c_x, c_y, eta_x, eta_y).
+ *  share = 0.5 is the RECIPROCAL model (buffered Voronoi cell, Zhou et al. 2017): each robot of a pair may use its half of
+ *  the free space between the two discs.  There eta.(p_i - c) = (dist - rs) / 2 at k = 0, which is >= 0 whenever the discs
+ *  do not overlap -- the constant row cannot fail because the OTHER robot moved -- and the two half-spaces of a pair are
+ *  disjoint and rs apart, so if both solves succeed the discs do not overlap at the next sample either.  share = 0 is the
+ *  static disc, c = p_j + rs * eta, for neighbours known not to move (a neighbour that steps toward the robot violates that
+ *  row).  dist == 0 gives eta = NaN: the step reports LIPMPC_STATUS_DEGENERATE, as for every producer's degenerate geometry.
+ *  There is no inside flip: overlapping discs make the constant row negative and the step reports LIPMPC_STATUS_INFEASIBLE.
+ * WRITTEN: slots below first_slot[i] are not touched; slots first_slot[i] + n_rows[i] .. n_obs_max - 1 are zeroed (in a
+ *  replayed loop no row of the previous sample survives); n_rows [B], n_near [B]; neighbours [B,k_rows] int32 or NULL: j per
+ *  row, -1 beyond n_rows.  n_near[i] > n_rows[i]: a neighbour in range got no row.
+ * A robot's outputs are a function of the inputs alone -- not of the launch order, nor of how the races of the sort fell:
+ *  two calls give identical bits.  Reproduced in numpy by tests/neighbour_oracle.py.
+ * The search is a uniform grid of cells a hair wider than sense_range, hashed into a bucket table sized from B (counting
+ *  sort: count, scan, scatter; then one lane per robot walks its 3 x 3 cells): linear in B at a given density.
+ * LIPMPC_E_ARG: B outside 0..2^22, k_rows outside 1..16, n_obs_max outside 1..50, sense_range not positive and finite, share
+ *  outside [0, 1], a null state, radius, workspace, c_eta, n_rows or n_near. */
+int64_t lipmpc_neighbour_workspace_bytes(int64_t B);          /* < 0: B out of range */
+int lipmpc_neighbour_c_eta_batch(int device, int64_t B, int32_t n_obs_max, int32_t k_rows,
+                                 double sense_range, double share,
+                                 const double* state, const double* radius, const int32_t* group,
+                                 const int32_t* first_slot, void* workspace,
+                                 double* c_eta, int32_t* n_rows, int32_t* n_near, int32_t* neighbours,
+                                 void* hip_stream);
 
 const char* lipmpc_strerror(int code);
 int lipmpc_version(void);
