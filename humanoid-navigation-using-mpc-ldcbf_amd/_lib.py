@@ -77,6 +77,10 @@ SIGNATURES = {
     "lipmpc_rrt_workspace_bytes": _sig(C.c_int64, "p:rrt_params B:i64"),
     "lipmpc_rrt_plan_batch": _sig(C.c_int, "device:int p:rrt_params B:i64 obs_xy obs_nv n_obs_max:i32 v_max:i32 start goal seed workspace "
                                            "sub_goals n_sub status path_cost grid_dims occ_d2 cost_grid tree S_max:i32 hip_stream"),
+    "lipmpc_rrt_plan_grid_batch": _sig(C.c_int, "device:int p:rrt_params B:i64 W:i32 H:i32 grid_shared:i32 origin cell occ start goal seed workspace "
+                                                "sub_goals n_sub status path_cost grid_dims occ_d2 cost_grid tree S_max:i32 hip_stream"),
+    "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
+                                             "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),
     "lipmpc_neighbour_c_eta_batch": _sig(C.c_int, "device:int B:i64 n_obs_max:i32 k_rows:i32 sense_range:f64 share:f64 state radius group "
                                                   "first_slot workspace c_eta n_rows n_near neighbours hip_stream"),

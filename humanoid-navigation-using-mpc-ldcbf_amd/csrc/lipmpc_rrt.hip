@@ -10,6 +10,8 @@
 //                      C = exp(-sqrt(d2)) (:107-112)
 //   rrt_star_kernel    one workgroup per problem: RRT* (:116-128) with the tree and the occupancy bitmap in LDS, then the
 //                      tree path as world sub-goals (:129-135)
+// lipmpc_rrt_plan_grid_batch plans on a GIVEN occupancy grid: rrt_setup_grid_kernel and rrt_pack_grid_kernel (bounds from the
+// grid's geometry, occupancy bytes -> bitmap words) stand in for the first two launches, the other three run unchanged.
 // The contract (sampler, ties, rewiring, segment rasterisation) is spelled out at lipmpc_rrt_plan_batch in lipmpc.h and
 // restated in numpy by tests/rrt_oracle.py.  Every comparison the tree makes is between exactly computed values (integers,
 // correctly rounded sqrt, separate multiply and add), so given C the tree is the oracle's bit for bit.
@@ -193,6 +195,69 @@ __global__ void __launch_bounds__(GRID_THREADS) rrt_grid_kernel(const double* __
     }
   }
   const uint64_t mask = __ballot(occ);
+  if ((threadIdx.x & 63) == 0 && c < ncells) {
+    uint32_t* bm = (uint32_t*)(ws + b * slot_bytes + off_bitmap);
+    const int w = c >> 5;                                     // c is a multiple of 64
+    bm[w] = (uint32_t)mask;
+    bm[w + 1] = (uint32_t)(mask >> 32);
+    if (mask) atomicOr(&h->any_occ, 1);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Planning on a GIVEN occupancy grid (lipmpc_rrt_plan_grid_batch): the two kernels that stand in for rrt_setup_kernel and
+// rrt_grid_kernel; the distance transform and the tree run behind them unchanged.
+// The planner's cells are the CENTRES of the grid's W x H cells: bounds min = origin + cell / 2, max = origin + (W - 1/2) cell,
+// W_p = W - 1, H_p = H - 1 -- the inverse of GridMap.from_planner.  One thread per problem.
+__global__ void rrt_setup_grid_kernel(int64_t B, lipmpc_rrt_params p, int W, int H, double ox, double oy, double cdx, double cdy,
+                                      const double* __restrict__ start, const double* __restrict__ goal, char* ws,
+                                      int64_t slot_bytes, int32_t* grid_dims) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double sx = start ? start[2 * b] : 0.0, sy = start ? start[2 * b + 1] : 0.0;
+  const double gx = goal[2 * b], gy = goal[2 * b + 1];
+  RrtHdr* h = (RrtHdr*)(ws + b * slot_bytes);
+  h->min_x = ox + cdx / 2.0; h->max_x = ox + ((double)W - 0.5) * cdx;
+  h->min_y = oy + cdy / 2.0; h->max_y = oy + ((double)H - 0.5) * cdy;
+  const bool too_large = W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > (int64_t)p.max_cells;
+  h->W = W - 1;
+  h->H = too_large ? 0 : H - 1;
+  h->ncells = too_large ? 0 : W * H;
+  h->any_occ = 0;
+  h->start_cell = 0; h->goal_cell = 0;
+  int st = too_large ? LIPMPC_RRT_GRID_TOO_LARGE : LIPMPC_RRT_FOUND;
+  if (!too_large) {
+    // the rounded cells as doubles first: a start or goal that rounds outside the grid (NaN included) has no cell
+    const double si = rint(((sx - h->min_x) / (h->max_x - h->min_x)) * (double)(W - 1));
+    const double sj = rint(((sy - h->min_y) / (h->max_y - h->min_y)) * (double)(H - 1));
+    const double gi = rint(((gx - h->min_x) / (h->max_x - h->min_x)) * (double)(W - 1));
+    const double gj = rint(((gy - h->min_y) / (h->max_y - h->min_y)) * (double)(H - 1));
+    const bool inside = (si >= 0.0) & (si <= (double)(W - 1)) & (sj >= 0.0) & (sj <= (double)(H - 1)) &
+                        (gi >= 0.0) & (gi <= (double)(W - 1)) & (gj >= 0.0) & (gj <= (double)(H - 1));
+    if (inside) {
+      h->start_cell = (int)si * H + (int)sj;
+      h->goal_cell = (int)gi * H + (int)gj;
+    } else {
+      st = LIPMPC_RRT_OUTSIDE_GRID;
+    }
+  }
+  h->status = st;
+  if (grid_dims) { grid_dims[2 * b] = W; grid_dims[2 * b + 1] = H; }
+}
+
+// Occupancy bytes -> bitmap words.  blockIdx.x = problem, blockIdx.y = chunk of GRID_THREADS cells; the grid's own layout
+// (cell (i, j) at i * H + j) is the planner's, so a wave's ballot over 64 consecutive bytes is the word pair.
+__global__ void __launch_bounds__(GRID_THREADS) rrt_pack_grid_kernel(const uint8_t* __restrict__ occ, int64_t occ_stride, char* ws,
+                                                                     int64_t slot_bytes, int64_t off_bitmap) {
+  const int64_t b = blockIdx.x;
+  RrtHdr* h = (RrtHdr*)(ws + b * slot_bytes);
+  if (h->status != LIPMPC_RRT_FOUND) return;
+  const int ncells = h->ncells;
+  const int c0 = blockIdx.y * GRID_THREADS;
+  if (c0 >= ncells) return;
+  const int c = c0 + threadIdx.x;
+  const bool o = c < ncells && occ[b * occ_stride + c] != 0;
+  const uint64_t mask = __ballot(o);
   if ((threadIdx.x & 63) == 0 && c < ncells) {
     uint32_t* bm = (uint32_t*)(ws + b * slot_bytes + off_bitmap);
     const int w = c >> 5;                                     // c is a multiple of 64
@@ -554,6 +619,12 @@ bool params_ok(const lipmpc_rrt_params* p) {
          rrt_lds_bytes(p->n_samples, p->max_cells) <= LDS_LIMIT;
 }
 
+// the parameters the tree and the distance transform read (a given grid has no width and no margin)
+bool tree_params_ok(const lipmpc_rrt_params* p) {
+  return p && p->n_samples >= 1 && p->r_rewire >= 1 && p->r_rewire <= 8192 && p->max_cells >= 1 && p->max_cells <= (1 << 22) &&
+         rrt_lds_bytes(p->n_samples, p->max_cells) <= LDS_LIMIT;
+}
+
 }  // namespace
 
 extern "C" int lipmpc_rrt_default_params(lipmpc_rrt_params* p) {
@@ -604,5 +675,41 @@ extern "C" int lipmpc_rrt_plan_batch(int device, const lipmpc_rrt_params* p, int
     return LIPMPC_E_HIP;
   hipLaunchKernelGGL(rrt_star_kernel, dim3((unsigned)B), dim3(RRT_THREADS), lds_tree, s, *p, seed, ws, sl.bytes, sl,
                      S_max, sub_goals, n_sub, status, path_cost, tree);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_rrt_plan_grid_batch(int device, const lipmpc_rrt_params* p, int64_t B, int32_t W, int32_t H,
+                                          int32_t grid_shared, const double* origin, const double* cell, const uint8_t* occ,
+                                          const double* start, const double* goal, const uint64_t* seed, void* workspace,
+                                          double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                          int32_t* grid_dims, int32_t* occ_d2, double* cost_grid, double* tree, int32_t S_max,
+                                          void* hip_stream) {
+  if (!tree_params_ok(p) || B < 0 || B > 0x7fffffff || W < 2 || H < 2 || S_max < 1 || !origin || !cell) return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
+    return LIPMPC_E_ARG;
+  if (B == 0) return LIPMPC_OK;
+  if (!occ || !goal || !seed || !workspace || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const Slot sl = slot_layout(p->max_cells);
+  char* ws = (char*)workspace;
+  // a grid beyond the caps is refused per problem by the setup kernel (GRID_TOO_LARGE); the launches behind it then find nothing to do
+  const bool fits = W <= MAX_SIDE && H <= MAX_SIDE && (int64_t)W * H <= (int64_t)p->max_cells;
+  const int64_t ncells = fits ? (int64_t)W * H : 1;
+  const int w1 = fits ? W : 1, h1 = fits ? H : 1;
+  hipLaunchKernelGGL(rrt_setup_grid_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, B, *p, W, H, ox, oy, dx, dy, start,
+                     goal, ws, sl.bytes, grid_dims);
+  hipLaunchKernelGGL(rrt_pack_grid_kernel, dim3((unsigned)B, (unsigned)((ncells + GRID_THREADS - 1) / GRID_THREADS)),
+                     dim3(GRID_THREADS), 0, s, occ, grid_shared ? (int64_t)0 : (int64_t)W * H, ws, sl.bytes, sl.bitmap);
+  hipLaunchKernelGGL(rrt_edt_col_kernel, dim3((unsigned)B, (unsigned)((w1 + 63) / 64)), dim3(64), 0, s, ws, sl.bytes, sl);
+  hipLaunchKernelGGL(rrt_edt_row_kernel, dim3((unsigned)B, (unsigned)((h1 + 63) / 64)), dim3(64), 0, s, ws, sl.bytes, sl,
+                     (int64_t)p->max_cells, occ_d2, cost_grid);
+  const size_t lds_tree = (size_t)rrt_lds_bytes(p->n_samples, p->max_cells);
+  if (lds_tree > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)rrt_star_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tree) != hipSuccess)
+    return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(rrt_star_kernel, dim3((unsigned)B), dim3(RRT_THREADS), lds_tree, s, *p, seed, ws, sl.bytes, sl, S_max,
+                     sub_goals, n_sub, status, path_cost, tree);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

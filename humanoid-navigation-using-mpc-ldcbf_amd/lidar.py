@@ -328,10 +328,14 @@ class UnknownEnvFleet:
     loop over an occupancy grid (a robot that walks into a solid cell stops with STATUS_SENSOR_OVERFLOW).
     ``avoid=NeighbourRows(...)``: the robots keep apart -- every sample each robot's nearest neighbours in the batch are
     appended to its scan's half-spaces as LDCBF rows (lipmpc_neighbour_c_eta_batch) before the solve; a stopped robot stays
-    where it is and stays an obstacle."""
+    where it is and stays an obstacle.
+    ``mapper=OccupancyMapper(...)``: the robots map what they see -- every sample the scan's readings of the walking robots are
+    integrated into the mapper's evidence grid (lipmpc_map_update_batch) between the scan and the solve, inside the captured
+    graph; the loop itself is not disturbed (same X_pred / U_pred, bit for bit).  A run adds to the evidence the mapper holds
+    (``mapper.reset()`` forgets it).  ``run_replanning`` plans on that map."""
 
     def __init__(self, env_rings=None, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
-                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None):
+                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None, mapper=None):
         from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR, FLAG_WARM_START
         if (env_rings is None) == (grid is None):
             raise ValueError("the true map: env_rings or grid")
@@ -348,6 +352,10 @@ class UnknownEnvFleet:
         if avoid is not None and avoid.device != self.device:
             raise ValueError("avoid: a NeighbourRows on the fleet's device")
         self.avoid = avoid
+        if mapper is not None and (mapper.device != self.device or mapper.resolution != self.sensor.resolution
+                                   or mapper.lidar_range != self.sensor.lidar_range):
+            raise ValueError("mapper: an OccupancyMapper on the fleet's device, for the fleet's resolution and lidar_range")
+        self.mapper = mapper
 
     def _plan_for(self, B, k_max, noise_mode, have_delta, stop_obj, use_graph):
         """Buffers (and, once captured, the HIP graph of one sample) of a run shape; kept across ``run`` calls, so a
@@ -373,6 +381,10 @@ class UnknownEnvFleet:
         if self.avoid is not None:
             pl.update(nbr=self.avoid.alloc_outputs(B), n_crowded=torch.zeros((B,), dtype=torch.int32, device=dev),
                       crowded=torch.zeros((B,), dtype=torch.bool, device=dev))
+        if self.mapper is not None:
+            # the scan hands its readings over, and `walking` (int8) goes to the update as the int32 mask the C call takes
+            pl["sen"].update(_alloc(sensor_outputs(B, sn.n_obs_max, sn.v_max, sn.resolution), ("hits",), dev, torch.zeros))
+            pl["mask"] = torch.zeros((B,), dtype=torch.int32, device=dev)
         self._plan = pl
         return pl
 
@@ -387,7 +399,11 @@ class UnknownEnvFleet:
         One sample = noise draw (seeded mode), scan + constraint assembly, step solve, fleet update; with ``use_graph``
         it is captured once per run shape in a HIP graph (kept by the object) and replayed k_max times back to back.
         The returned tensors are the object's buffers: the next ``run`` of the same shape overwrites them."""
-        dev, sv, sn, avoid = self.device, self.solver, self.sensor, self.avoid
+        return self._run(state0, goal, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph)
+
+    def _run(self, state0, goal, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=None):
+        """``run``; ``before_sample(k, pl)``: called on the host before sample k is enqueued (run_replanning's hook)."""
+        dev, sv, sn, avoid, mapper = self.device, self.solver, self.sensor, self.avoid, self.mapper
         B = state0.shape[0]
         mode = "none" if noise is None else ("seeded" if isinstance(noise, str) else "given")
         pl = self._plan_for(B, int(k_max), mode, delta is not None, stop_obj, use_graph)
@@ -413,14 +429,18 @@ class UnknownEnvFleet:
             # and the trajectory row: one bookkeeping launch (lipmpc_fleet_update_batch)
             if gen is not None:
                 nbuf.normal_(0.0, NOISE_STD, generator=gen)
-            if avoid is None:
+            if avoid is None and mapper is None:
                 sn.sense_plan_step(sv, fl["state"], pl["goal"], fl["first_foot"], nbuf, pl["delta"], sen=sen, out=out, schedule=pl["sched"])
             else:
-                # scan -> neighbour rows behind the scan's -> solve, back to back on the one stream
+                # scan -> [neighbour rows behind the scan's] -> [the readings into the map] -> solve, back to back on the one stream
                 sn.sense(fl["state"], nbuf, out=sen, c_eta=True, rings=False, schedule=pl["sched"])
-                nbr = avoid.append(fl["state"], sen["c_eta"], first_slot=sen["n_inferred"], out=pl["nbr"])
-                torch.gt(nbr["n_near"], nbr["n_rows"], out=pl["crowded"])
-                pl["n_crowded"].add_(pl["crowded"])
+                if avoid is not None:
+                    nbr = avoid.append(fl["state"], sen["c_eta"], first_slot=sen["n_inferred"], out=pl["nbr"])
+                    torch.gt(nbr["n_near"], nbr["n_rows"], out=pl["crowded"])
+                    pl["n_crowded"].add_(pl["crowded"])
+                if mapper is not None:
+                    pl["mask"].copy_(fl["walking"])
+                    mapper.update(fl["state"], sen["hits"], mask=pl["mask"])
                 sv.plan_step_batch_c_eta(fl["state"], pl["goal"], fl["first_foot"], sen["c_eta"], pl["delta"], out=out,
                                          overflow=sen["overflow"])
             sv.fleet_update(fl, out, overflow=sen["overflow"], stop_obj=stop_obj)
@@ -432,7 +452,10 @@ class UnknownEnvFleet:
             side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
+                kept = None if mapper is None else mapper.evidence.clone()
                 sample()                                     # warm-up outside capture (lazy initialisation)
+                if kept is not None:
+                    mapper.evidence.copy_(kept)              # the warm-up's scan is no part of the run
             torch.cuda.current_stream(dev).wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             if gen is not None:
@@ -442,6 +465,8 @@ class UnknownEnvFleet:
             pl["graph"] = graph
         reset()
         for k in range(k_max):
+            if before_sample is not None:
+                before_sample(k, pl)
             if mode == "given":
                 nbuf.copy_(noise[k])
             if use_graph:
@@ -453,3 +478,63 @@ class UnknownEnvFleet:
         if avoid is not None:
             res["n_crowded"] = pl["n_crowded"]
         return res
+
+    def run_replanning(self, state0, goal, first_foot, k_max, planner, replan_every, lookahead, noise="seeded", noise_seed=0,
+                       delta=None, stop_obj=0.05, use_graph=True, seeds=None, S_max=None, min_evidence=None):
+        """``run`` with a global planner on the map the fleet builds (``mapper`` is required): a robot that the reactive loop
+        leaves in a dead end re-plans on what it has seen and walks out.  The loop is driven from the host, all per-robot work
+        runs on the device, nothing is copied device -> host per sample.  Every ``replan_every`` samples (sample 0 included):
+          - all B robots are planned in one ``planner.plan_grid_batch`` call, from their current positions to their final goals,
+            on ``mapper.grid_map(min_evidence)`` (unknown cells count as free); ``seeds`` / ``S_max`` as ``plan_grid_batch``;
+          - a robot that the stop rule stopped at a working goal that was not its final goal walks again (a robot that stopped
+            at its final goal, or on a failed solve, stays stopped);
+          - each robot's working goal becomes the first sub-goal of its path that is at least ``lookahead`` from the robot, or
+            the final goal when none is or when the plan's status is anything other than RRT_FOUND (RRT_NO_OBSTACLE_GRID
+            included: the map is empty, the robot heads straight for the goal).
+        Returns what ``run`` returns, plus n_replans (int), rrt_status [B] of the last plan, working_goal [B,2] and walking [B]
+        (int8) as the last sample left them: a robot ARRIVED if it is not walking, its last_status is SOLVED or UNCERTIFIED
+        (the stop rule stopped it, not a failed solve) and its working goal is its final goal."""
+        from .planner import RRT_FOUND
+        from .solver import STATUS_SOLVED, STATUS_UNCERTIFIED
+        if self.mapper is None:
+            raise ValueError("run_replanning plans on the fleet's map: UnknownEnvFleet(..., mapper=OccupancyMapper(...))")
+        replan_every, lookahead = int(replan_every), float(lookahead)
+        if replan_every < 1 or not lookahead >= 0.0:
+            raise ValueError("replan_every >= 1 and lookahead >= 0")
+        if isinstance(seeds, torch.Tensor):
+            seeds = seeds.cpu().numpy()                      # once, before the loop
+        final = goal.to(device=self.device, dtype=torch.float64).contiguous()
+        info = dict(n_replans=0, rrt_status=None)
+
+        def replan(k, pl):
+            if k % replan_every:
+                return
+            fl, working = pl["fl"], pl["goal"]
+            pos = fl["state"][:, (0, 2)].contiguous()
+            plan = planner.plan_grid_batch(final, self.mapper.grid_map(min_evidence), pos, seeds=seeds, S_max=S_max)
+            # stopped by the stop rule (not by a failed solve: that leaves its status), at a goal that was not the final one
+            solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
+            resume = (fl["walking"] == 0) & solved & (fl["last_obj"] < stop_obj) & (working != final).any(1)
+            fl["walking"].masked_fill_(resume, 1)
+            fl["last_obj"].masked_fill_(resume, float("inf"))          # the objective of the goal it has reached says nothing about the next
+            working.copy_(select_working_goals(pos, final, plan["sub_goals"], plan["n_sub"], plan["status"], lookahead, RRT_FOUND))
+            info["n_replans"] += 1
+            info["rrt_status"] = plan["status"]
+
+        res = self._run(state0, final, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=replan)
+        res.update(info, working_goal=self._plan["goal"], walking=self._plan["fl"]["walking"])
+        return res
+
+
+def select_working_goals(position, goal, sub_goals, n_sub, status, lookahead, found=0):
+    """The goal-selection rule of ``UnknownEnvFleet.run_replanning`` on the device: per robot the first of its n_sub sub-goals
+    with sqrt(dx * dx + dy * dy) >= lookahead from ``position``, else (or when status != found) its ``goal``.  position, goal
+    [B,2]; sub_goals [B,S,2]; n_sub, status [B].  Restated in numpy by tests/map_oracle.py (select_goals)."""
+    S = sub_goals.shape[1]
+    dx, dy = sub_goals[:, :, 0] - position[:, None, 0], sub_goals[:, :, 1] - position[:, None, 1]
+    dist = torch.sqrt(dx * dx + dy * dy)
+    slot = torch.arange(S, device=sub_goals.device)[None, :]
+    ok = (dist >= lookahead) & (slot < n_sub[:, None]) & (status == found)[:, None]
+    first = torch.where(ok, slot, S).amin(1)
+    pick = sub_goals[torch.arange(sub_goals.shape[0], device=sub_goals.device), first.clamp(max=S - 1)]
+    return torch.where((first < S)[:, None], pick, goal)

@@ -15,9 +15,9 @@ from . import _lib
 from .solver import _alloc, _named, pack_rings
 
 RRT_FOUND, RRT_NO_PATH, RRT_START_OCCUPIED, RRT_GOAL_OCCUPIED, RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, \
-    RRT_PATH_OVERFLOW = range(7)
+    RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID = range(8)
 RRT_STATUS_NAMES = ("FOUND", "NO_PATH", "START_OCCUPIED", "GOAL_OCCUPIED", "GRID_TOO_LARGE", "NO_OBSTACLE_GRID",
-                    "PATH_OVERFLOW")
+                    "PATH_OVERFLOW", "OUTSIDE_GRID")
 
 
 def plan_outputs(B, S_max, max_cells, n_samples):
@@ -93,6 +93,20 @@ class RrtStarPlanner:
         st = self._dev(start, torch.float64)
         if st is not None and tuple(st.shape) != (B, 2):
             raise ValueError("start must be [B,2] or None")
+        seeds_d = self._seeds(seeds, B)
+        S_max, table, out = self._outputs(B, S_max, with_tree, with_grids)
+        if with_grids:
+            out["grid_bounds"] = self._grid_bounds(goal, xy, nv, st)
+        if B == 0:
+            return out
+        _lib.call("lipmpc_rrt_plan_batch", device=self.device_index, p=C.byref(self.params), B=B, obs_xy=xy, obs_nv=nv, n_obs_max=n_obs,
+                  v_max=v_max, start=st, goal=goal, seed=seeds_d, workspace=self._workspace(B), **_named(out, table),
+                  S_max=S_max, hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self.last = out
+        return out
+
+    def _seeds(self, seeds, B):
+        """[B] device tensor of seed bit patterns from ``seeds`` as plan_batch takes them."""
         if seeds is None or np.isscalar(seeds):
             sd = np.full(B, self.seed if seeds is None else int(seeds), dtype=np.uint64)
         else:
@@ -102,18 +116,43 @@ class RrtStarPlanner:
             sd = np.asarray([int(s) & ((1 << 64) - 1) for s in vals], dtype=np.uint64)        # ints may not fit int64)
             if sd.shape[0] != B:
                 raise ValueError("seeds must have B entries")
-        seeds_d = torch.as_tensor(sd.view(np.int64), device=self.device)
+        return torch.as_tensor(sd.view(np.int64), device=self.device)
+
+    def _outputs(self, B, S_max, with_tree, with_grids):
+        """(S_max, the shape table, zeroed output tensors) of a plan."""
         S_max = int(self.params.n_samples) + 1 if S_max is None else int(S_max)
         want = dict(grid_dims=with_grids, occ_d2=with_grids, cost_grid=with_grids, tree=with_tree)
         table = plan_outputs(B, S_max, self.max_cells, int(self.params.n_samples))
-        out = _alloc(table, [k for k, (_, _, required) in table.items() if required or want[k]], self.device, torch.zeros)
+        return S_max, table, _alloc(table, [k for k, (_, _, required) in table.items() if required or want[k]], self.device, torch.zeros)
+
+    def plan_grid_batch(self, goal, grid, start, seeds=None, S_max: int | None = None, with_tree: bool = False,
+                        with_grids: bool = False):
+        """Plan B problems on a GIVEN occupancy grid (lipmpc_rrt_plan_grid_batch): ``grid`` a GridMap -- shared, or one map per
+        problem -- e.g. ``OccupancyMapper.grid_map()`` or ``GridMap.from_planner``; goal, start [B,2] (start None = the
+        origin).  The planner's cells are the centres of the grid's cells; ``width_grid_size`` and ``margin`` play no part.
+        Returns the dict of ``plan_batch``: status RRT_OUTSIDE_GRID where the start or the goal rounds to no cell of the grid,
+        grid_dims = (W, H), grid_bounds = (origin + cell / 2, origin + (W - 1/2) cell) per axis."""
+        goal = self._dev(goal, torch.float64)
+        if goal is None or goal.dim() != 2 or goal.shape[1] != 2:
+            raise ValueError("goal must be [B,2]")
+        B = goal.shape[0]
+        st = self._dev(start, torch.float64)
+        if st is not None and tuple(st.shape) != (B, 2):
+            raise ValueError("start must be [B,2] or None")
+        if grid.W < 2 or grid.H < 2:
+            raise ValueError("grid: at least 2 x 2 cells")
+        grid = grid.to(self.device)
+        seeds_d = self._seeds(seeds, B)
+        S_max, table, out = self._outputs(B, S_max, with_tree, with_grids)
         if with_grids:
-            out["grid_bounds"] = self._grid_bounds(goal, xy, nv, st)
+            (ox, oy), (dx, dy) = grid.origin, grid.cell
+            gb = [ox + dx / 2.0, ox + (grid.W - 0.5) * dx, oy + dy / 2.0, oy + (grid.H - 0.5) * dy]
+            out["grid_bounds"] = torch.tensor([gb], dtype=torch.float64, device=self.device).repeat(B, 1)
         if B == 0:
             return out
-        _lib.call("lipmpc_rrt_plan_batch", device=self.device_index, p=C.byref(self.params), B=B, obs_xy=xy, obs_nv=nv, n_obs_max=n_obs,
-                  v_max=v_max, start=st, goal=goal, seed=seeds_d, workspace=self._workspace(B), **_named(out, table),
-                  S_max=S_max, hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.call("lipmpc_rrt_plan_grid_batch", device=self.device_index, p=C.byref(self.params), B=B, **grid._args(B, self.device),
+                  start=st, goal=goal, seed=seeds_d, workspace=self._workspace(B), **_named(out, table), S_max=S_max,
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         self.last = out
         return out
 

@@ -35,7 +35,8 @@ extern "C" {
                                 *    + lipmpc_set_workspace / lipmpc_workspace_bytes;
                                 *    backward-compatible additions since: + lipmpc_set_warm_start / lipmpc_warm_words;
                                 *    + lipmpc_rrt_default_params / lipmpc_rrt_workspace_bytes / lipmpc_rrt_plan_batch;
-                                *    + lipmpc_neighbour_workspace_bytes / lipmpc_neighbour_c_eta_batch */
+                                *    + lipmpc_neighbour_workspace_bytes / lipmpc_neighbour_c_eta_batch;
+                                *    + lipmpc_map_update_batch; + lipmpc_rrt_plan_grid_batch, LIPMPC_RRT_OUTSIDE_GRID */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -390,6 +391,48 @@ int lipmpc_sense_grid_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resol
                                       int32_t* iters, uint64_t* active, uint64_t* working, double* diag, const double* bounds,
                                       void* hip_stream);
 
+/* SCAN INTEGRATION (backward-compatible addition): one call adds one scan per robot to an occupancy-EVIDENCE grid -- the memory
+ * between the scans and lipmpc_rrt_plan_grid_batch.  Asynchronous on hip_stream; no allocation and no host synchronisation, so
+ * the call can be captured in a graph.
+ *  W, H, grid_shared, origin, cell: the grid's geometry exactly as lipmpc_lidar_grid_c_eta_batch takes it (the same cell
+ *             rectangles, the same i * H + j layout; origin / cell HOST pointers).  It need not be the geometry of the map scanned.
+ *  state      [B,5]  only (p_x, p_y) = p0 are read
+ *  hits       [B,resolution,2] as the scans write them: a NaN coordinate = the ray has no reading
+ *  ray_table  [resolution,2] as the scans take it; lidar_range as the scan's
+ *  mask       [B] int32 or NULL: a robot with mask == 0 is skipped (a fleet passes `walking`)
+ *  w_hit, w_miss  integer weights, each 1..32767;  depth >= 0, finite (a caller's default: half the smaller cell size)
+ *  evidence   int32, [W,H] if grid_shared else [B,W,H], updated IN PLACE
+ * THE UPDATE, in IEEE double, no contraction, division and square root correctly rounded, every expression evaluated as written:
+ *  - robot cell (ci, cj) as the grid scan's: floor((x0 - ox) / dx), floor((y0 - oy) / dy).  A robot with mask == 0, or unless
+ *    |ci|, |cj| < 2^30 (a NaN or infinite position included), contributes nothing.
+ *  - window: nx = floor((lidar_range + depth) / dx) + 2 columns, ny likewise rows: only cells (i, j) with |i - ci| <= nx and
+ *    |j - cj| <= ny are updated.
+ *  - ray i WITH a reading q: d = (q_x - x0, q_y - y0), L = sqrt(d_x * d_x + d_y * d_y), s = depth / L, the END POINT
+ *    e = (q_x + s * d_x, q_y + s * d_y).  If L == 0 or L, e_x or e_y is not finite the ray contributes nothing.  The HIT CELL is
+ *    (floor((e_x - ox) / dx), floor((e_y - oy) / dy)); a hit cell outside the window is dropped (the ray still marches).
+ *    Why depth: a grid scan's reading lies exactly ON the face of the solid cell, so for a ray travelling toward -x or -y the
+ *    floor of the reading itself names the free neighbour; the overshoot puts the hit inside the wall.
+ *  - ray i WITHOUT a reading: e = (x0 + lidar_range * cos_i, y0 + lidar_range * sin_i), as the scan forms it; no hit cell.
+ *  - the march from p0 to e, by the rules of the grid scan above with r = (e_x - x0, e_y - y0) in the place of its d: crossings
+ *    recomputed from the boundary's index, x on a tie, the ray then in the next cell of that axis, entered at t.  The robot's own
+ *    cell is visited first.  The ray stops, the cell just entered NOT visited: unless t <= 1 (NaN included); when that cell is
+ *    outside the window; when it is the hit cell.  Every visited cell that is not the ray's hit cell is PASSED by the ray.
+ *  - ONE UPDATE PER CELL, ROBOT AND CALL: a cell of the window that is the hit cell of any ray of the scan gets + w_hit; a cell
+ *    otherwise passed by any ray gets - w_miss (hit wins over passed).  Cells outside the grid are ignored.  Plain int32
+ *    addition, NO SATURATION: the sum wraps beyond int32 (no sooner than after 65536 updates of one cell at the largest weight).
+ *  - shared map: all robots add into the one grid with integer atomics.  Integer addition commutes, so the result does not
+ *    depend on the launch order or on how the atomics fell: two calls from the same inputs give identical bits, and the shared
+ *    map is the sum of the per-robot maps.
+ * Reproduced integer for integer in numpy by tests/map_oracle.py.
+ * The window, (2 nx + 1) x (2 ny + 1) cells, is kept per robot as two bitmaps (passed, hit) in the kernel's LDS: a (range + depth,
+ * cell) pair whose window exceeds 49152 cells (2 x 6 KiB) is refused with LIPMPC_E_UNSUPPORTED before anything is enqueued.
+ * Other refusals (LIPMPC_E_ARG): resolution outside 1..384, W or H < 1, a cell size that is not positive and finite, a range
+ * or a depth that is negative or not finite, a weight outside 1..32767, a null state / hits / ray_table / evidence / origin / cell. */
+int lipmpc_map_update_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                            const double* origin, const double* cell, double lidar_range, double depth, int32_t w_hit,
+                            int32_t w_miss, const double* state, const double* hits, const double* ray_table,
+                            const int32_t* mask, int32_t* evidence, void* hip_stream);
+
 /* RRT* SUB-GOAL PLANNER (backward-compatible addition): the global planner of HumanoidMPCWithRRT
  * (HumanoidMPCVariants/HumanoidMPCWithRRT.py:21-135) for B independent problems, one workgroup per problem.  Per problem b:
  *  - bounds: min / max over {start_x, goal_x, every ring vertex x} -/+ margin, the same for y (the reference's origin is
@@ -419,6 +462,7 @@ int lipmpc_sense_grid_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resol
 #define LIPMPC_RRT_GRID_TOO_LARGE   4  /* (W+1)(H+1) > max_cells or H+1 > 4096 */
 #define LIPMPC_RRT_NO_OBSTACLE_GRID 5  /* no occupied cell: the distance transform is not defined */
 #define LIPMPC_RRT_PATH_OVERFLOW    6  /* the path has more than S_max sub-goals (path_cost is still written) */
+#define LIPMPC_RRT_OUTSIDE_GRID     7  /* lipmpc_rrt_plan_grid_batch only: the start or the goal rounds to a cell outside the given grid */
 
 typedef struct lipmpc_rrt_params {
   int32_t width;        /* W, grid cells across x minus one: 1..4095           (width_grid_size, :102) */
@@ -450,6 +494,26 @@ int lipmpc_rrt_plan_batch(int device, const lipmpc_rrt_params* p, int64_t B, con
                           void* workspace, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                           int32_t* grid_dims, int32_t* occ_d2, double* cost_grid, double* tree, int32_t S_max,
                           void* hip_stream);
+
+/* The planner on a GIVEN occupancy grid (backward-compatible addition): lipmpc_rrt_plan_batch with the occupancy taken from
+ * `occ` instead of rasterised rings -- a GridMap, e.g. the thresholded evidence of lipmpc_map_update_batch.
+ *  W, H, grid_shared, origin, cell, occ: the grid as lipmpc_lidar_grid_c_eta_batch takes it (occ uint8 DEVICE, [W,H] if
+ *         grid_shared else [B,W,H], cell (i, j) at occ[i * H + j], occupied if nonzero; origin / cell HOST pointers); W, H >= 2
+ *  the planner's grid of problem b is the W x H cell CENTRES: min = origin + cell / 2, max = origin + (W - 1/2) * cell per
+ *         axis, W_p = W - 1, H_p = H - 1 -- the inverse of the placement GridMap.from_planner gives a planner grid -- and
+ *         world <-> cell are the maps of lipmpc_rrt_plan_batch with those bounds; cell index i * H + j; grid_dims = (W, H)
+ *  p->width and p->margin are ignored (and not checked)
+ *  status: LIPMPC_RRT_GRID_TOO_LARGE if W * H > max_cells or H > 4096 or W > 4096; else LIPMPC_RRT_OUTSIDE_GRID if the rounded
+ *         cell of the start or the goal is not a cell of the grid (a NaN coordinate included); both are decided before the
+ *         distance transform (occ_d2 / cost_grid untouched); then as lipmpc_rrt_plan_batch
+ * Distance transform, sampler, tree and outputs, the workspace and every other status: exactly lipmpc_rrt_plan_batch's (the
+ * same kernels).  LIPMPC_E_ARG: W or H < 2, a cell size that is not positive and finite, an origin that is not finite, a null
+ * origin / cell / occ, and what lipmpc_rrt_plan_batch refuses.  Restated in numpy by tests/rrt_grid_oracle.py. */
+int lipmpc_rrt_plan_grid_batch(int device, const lipmpc_rrt_params* p, int64_t B, int32_t W, int32_t H, int32_t grid_shared,
+                               const double* origin, const double* cell, const uint8_t* occ, const double* start,
+                               const double* goal, const uint64_t* seed, void* workspace, double* sub_goals, int32_t* n_sub,
+                               int32_t* status, double* path_cost, int32_t* grid_dims, int32_t* occ_d2, double* cost_grid,
+                               double* tree, int32_t S_max, void* hip_stream);
 
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
