@@ -272,6 +272,12 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
 }
+// A read of a double in LDS that is issued where it is written and waited for at its first use: volatile, so that it is not
+// sunk into the region that consumes it, right in front of its own wait; through an LDS-space pointer, because a volatile
+// access through a generic pointer stays a flat load.
+__device__ __forceinline__ double lds_read_here(const double* p) {
+  return *(const volatile __attribute__((address_space(3))) double*)p;
+}
 struct RowFlags {
   unsigned m = 0u;
   __device__ __forceinline__ bool operator[](int i) const { return (m >> i) & 1u; }

@@ -108,6 +108,10 @@
   for (int it = 0; it <= P.max_iter; ++it) {
     if (__all(done)) break;
     if (!done) {
+      // mu of the previous iteration (no-progress safeguard below), read HERE -- the factor of the iteration before is dead, the
+      // register file at its emptiest -- and consumed after the mu reduction, so that its LDS round trip is off the chain.
+      // (lds_read_here: an ordinary load is sunk into the lane-0 region that consumes it, right in front of its wait.)
+      const double mu_prev = lds_read_here(&lds_mu[grp][0]);
       double w[NR], d[NR];
       double mu_l = 0.0, rpmax_l = 0.0, zmax_l = 0.0;
 #pragma unroll
@@ -135,11 +139,14 @@
       }
       const double musum = gsum<G>(mu_l);
       const double mu = musum * inv_m;
+      // (every lane takes mu_prev here, behind mu, where it has long arrived: consumed only inside the lane-0 region below,
+      // its wait would come back behind that region, as a wait for the region's own LDS write)
+      double mu_prev_in = mu_prev;
+      asm volatile("" : "+v"(mu_prev_in) : "v"(mu));
       {   // no-progress safeguard, a ramp in mu / mu_prev (oracle/lipmpc_oracle.py).  Both values live in LDS: one more
           // double kept in registers across the factorisation costs 5 % of the iteration in AGPR traffic.
-        const double mu_prev = lds_mu[grp][0];
         // (hardware reciprocal seed, 4.5e-8: the ramp is continuous, so that is as good as a division here)
-        const double ramp = fmin(1.0, fmax(0.0, (mu * __builtin_amdgcn_rcp(mu_prev) - IPM_SLOW_RATIO) * (1.0 / (1.0 - IPM_SLOW_RATIO))));
+        const double ramp = fmin(1.0, fmax(0.0, (mu * __builtin_amdgcn_rcp(mu_prev_in) - IPM_SLOW_RATIO) * (1.0 / (1.0 - IPM_SLOW_RATIO))));
         if (lane == 0) { lds_mu[grp][0] = mu; lds_mu[grp][1] = (it >= IPM_SLOW_FROM) ? IPM_SLOW_SIGMA * ramp : 0.0; }
       }
       // largest primal residual and the divergence test (z or |q| out of range, NaN included) in ONE group reduction: a
@@ -180,6 +187,8 @@
 #pragma unroll
         for (int i = 0; i < NR; ++i) w[i] = fma(d[i], rp[i] - s[i], z[i]);
         const double dqa = solve(m2qg - GT_rows(w, axs, ays));
+        // (the sigma floor of the safeguard, read behind the substitution chain: the predictor's row work hides its round trip)
+        const double sigma_floor = lds_read_here(&lds_mu[grp][1]);
         PH(3)
         double dl[NR], c2[NR];                             // c2 = ds_aff dz_aff: all the corrector needs of the predictor
         rows_dir(dqa, dl);
@@ -213,7 +222,7 @@
         const double mu_aff = fma(a_aff * a_aff, gsum<G>(s2_l), (1.0 - a_aff) * musum) * inv_m;
         const double ratio = mu_aff * chain_rcp(mu);
         double sigma = ratio * ratio * ratio;
-        sigma = vmax(sigma, lds_mu[grp][1]);      // no-progress safeguard: floor computed at the top of the iteration
+        sigma = vmax(sigma, sigma_floor);         // no-progress safeguard: floor computed at the top of the iteration
         const double sigma_mu = sigma * mu;
         PH(4)
         // corrector: rc = s z + ds_a dz_a - sigma mu

@@ -54,6 +54,19 @@
     const double k2 = kap * kap;
     const double Pc0 = 2.0 * k2 * Ec0 + 4.0 * k2 * S0, Pc1 = 2.0 * k2 * Ec1 + 4.0 * k2 * S1;
     lds_P[grp][a][c][0] = Pc0; lds_P[grp][a][c][1] = Pc1;
+    wave_sync();
+    // P_max(a,b), row c, of every block b >= 1 as ONE 16-byte read each from stage max(a, b) -- for b <= a that is the pair
+    // this lane has just written -- issued here, in front of the rest of the block arithmetic: no select on (b <= a), which
+    // cost an exec-masked region with a read, a wait and a lane mask of its own per block.  Block 0 is always the lane's own
+    // pair.  (lds_P holds LMAX stages, so lanes past the horizon and past the variable slots of the 8-variable bodies stay
+    // in range: they read their own pair.)
+    double q0[NMAX], q1[NMAX];
+    q0[0] = Pc0; q1[0] = Pc1;
+#pragma unroll
+    for (int b = 1; b < NMAX; ++b) {
+      const double2 pb = *reinterpret_cast<const double2*>(lds_P[grp][a > b ? a : b][c]);
+      q0[b] = pb.x; q1[b] = pb.y;
+    }
     // LDCBF block sum_t d_t eta eta^T of the stage: accumulated as (own own, own partner, partner partner); the two
     // lanes of a stage hold the same three sums with own / partner swapped
     double coo = c ? cys : cxs, cop = cxys, cpp = c ? cxs : cys;
@@ -68,15 +81,12 @@
     const double Fn0 = gdown<G, 2>(Fc0, lane), Fn1 = gdown<G, 2>(Fc1, lane);
     const double Dg0 = (c ? 0.0 : 2.0) - k2 * Ec0 + Fc0 + Fn0 + Cc0;
     const double Dg1 = (c ? 2.0 : 0.0) - k2 * Ec1 + Fc1 + Fn1 + Cc1;
-    wave_sync();
     // block b of the row: (-1)^(a+b) P_max(a,b) + [b==a] Dg - [b==a-1] F_a - [b==a+1] F_{a+1}; the three
     // indicator terms are FMAs against 0/1 masks (eqm), not selects.  Lanes/stages beyond N fall
     // out as rows of 2I because all their weights are zero.
 #pragma unroll
     for (int b = 0; b < NMAX; ++b) {
-      const bool own = (b <= a);
-      const double q0v = own ? Pc0 : lds_P[grp][b][c][0];
-      const double q1v = own ? Pc1 : lds_P[grp][b][c][1];
+      const double q0v = q0[b], q1v = q1[b];
       const double sg = sgn_a * ((b & 1) ? -1.0 : 1.0);
       double k0 = fma(eqm[b], Dg0, sg * q0v), k1 = fma(eqm[b], Dg1, sg * q1v);
       if (b + 1 < NMAX) { k0 = fma(-eqm[b + 1], Fc0, k0); k1 = fma(-eqm[b + 1], Fc1, k1); }
@@ -143,7 +153,7 @@
       const double nip = -ipiv;
       static_for<1, NV>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        Yu[j] = zero_unless(fresh(lane) < j, Krow[j] * nip);
+        Yu[j] = zero_unless(ln < j, Krow[j] * nip);        // (ln: the one opaque copy of the lane index this call makes)
       });
     }
     return ok;

@@ -8,7 +8,7 @@
 #      -> <out>/pmc.csv (mean per launch over the timed launches) and <out>/traffic.json (what bench.py reads from
 #         profiles/traffic.json: HBM bytes and executed FP64 flops per launch of this workload)
 # Raw traces are summarised and deleted (gpurun copies back at most 64 MiB).
-# Usage: bash tools/profile_round.sh <tag> [extra bench.py args]
+# Usage: bash tools/profile_round.sh <tag> [extra bench.py args]        (SKIP_PMC=1: the kernel trace only, no counter passes)
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=$1; shift || true
@@ -32,6 +32,7 @@ open(O + '/bench_launches.txt', 'w').write('last %d plan_step_kernel launches: m
     vg.get('SGPR_Count', '?'), vg.get('LDS_Block_Size', '?'), vg.get('Scratch_Size', '?')))
 PY
 rm -rf /tmp/prof_stats
+if [ "${SKIP_PMC:-0}" == "1" ]; then cat $O/bench_launches.txt; exit 0; fi
 echo "counter,mean_per_launch_over_the_10_timed_launches" > $O/pmc.csv
 for c in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY" \
          "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_MFMA_MOPS_F64" \
