@@ -79,6 +79,10 @@ SIGNATURES = {
                                            "sub_goals n_sub status path_cost grid_dims occ_d2 cost_grid tree S_max:i32 hip_stream"),
     "lipmpc_rrt_plan_grid_batch": _sig(C.c_int, "device:int p:rrt_params B:i64 W:i32 H:i32 grid_shared:i32 origin cell occ start goal seed workspace "
                                                 "sub_goals n_sub status path_cost grid_dims occ_d2 cost_grid tree S_max:i32 hip_stream"),
+    "lipmpc_grid_field_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 grid_shared:i32 origin cell occ goal r_inflate:i32 field field_status "
+                                             "hip_stream"),
+    "lipmpc_grid_path_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell occ grid_shared:i32 field field_status goal start "
+                                            "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost hip_stream"),
     "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
                                              "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),

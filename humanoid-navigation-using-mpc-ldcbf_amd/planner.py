@@ -3,6 +3,9 @@
 
 ``RrtStarPlanner.plan_batch`` plans B problems in one call and returns ``sub_goals [B,S_max,2]`` / ``n_sub [B]`` in the form
 ``BatchedLipMpc.rollout_subgoals`` takes them; an instance is also the ``planner=`` of ``HumanoidMPCWithRRT``.
+
+``GridFieldPlanner`` is the complete, deterministic planner on a given grid: a cost-to-go field from the goal
+(``lipmpc_grid_field_batch``) and sub-goals down it (``lipmpc_grid_path_batch``), in the same output form.
 """
 from __future__ import annotations
 
@@ -12,12 +15,23 @@ import numpy as np
 import torch
 
 from . import _lib
-from .solver import _alloc, _named, pack_rings
+from .solver import _alloc, _check_table, _named, pack_rings
 
 RRT_FOUND, RRT_NO_PATH, RRT_START_OCCUPIED, RRT_GOAL_OCCUPIED, RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, \
     RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID = range(8)
 RRT_STATUS_NAMES = ("FOUND", "NO_PATH", "START_OCCUPIED", "GOAL_OCCUPIED", "GRID_TOO_LARGE", "NO_OBSTACLE_GRID",
                     "PATH_OVERFLOW", "OUTSIDE_GRID")
+
+
+FIELD_INF = 0xFFFFFFFF      # LIPMPC_FIELD_INF: a cell of a field that is blocked or has no path to the goal
+FIELD_NO_CAP = 0x7FFFFFFF   # max_seg of "no spacing cap": no field value reaches it (a field stays below 7 * 2^17)
+
+
+def field_plan_outputs(B, F, W, H, S_max):
+    """Outputs of GridFieldPlanner.plan_grid_batch, in the order it returns them (field, field_status: GridFieldPlanner.field's)."""
+    f64, i32 = torch.float64, torch.int32
+    return {"sub_goals": (f64, (B, S_max, 2), True), "n_sub": (i32, (B,), True), "status": (i32, (B,), True), "path_cost": (f64, (B,), True),
+            "field": (torch.uint32, (F, W, H), True), "field_status": (i32, (F,), True)}
 
 
 def plan_outputs(B, S_max, max_cells, n_samples):
@@ -196,3 +210,85 @@ class RrtStarPlanner:
         if st != RRT_FOUND:
             raise RuntimeError(f"RrtStarPlanner: no sub-goals ({RRT_STATUS_NAMES[st]})")
         return out["sub_goals"][0, :n].cpu().numpy()
+
+
+class GridFieldPlanner:
+    """A complete, deterministic planner on a GIVEN occupancy grid (include/lipmpc.h, GRID FIELD PLANNER): the cost-to-go field
+    from the goal over the 8-connected unblocked cells (axial step 5, diagonal 7, no corner cut), then per robot a descent down
+    the field, pulled taut into sub-goals.  A path that exists is found and is a shortest one in that metric; there is no seed;
+    one field serves every robot that shares the map and the goal.
+    ``r_inflate``: cells within this many cells (Euclidean) of a solid cell are blocked, 0..16 -- the body radius over the cell
+    size, rounded up.  ``max_seg``: the sub-goals' spacing cap in field units (5 per cell), >= 5; None = no cap.
+    Ring maps: plan on ``GridMap.from_planner(...)``."""
+
+    def __init__(self, r_inflate: int = 0, max_seg: int | None = None, device: int | None = None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("lipmpc needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
+        self.lib = _lib.load()
+        self.r_inflate = int(r_inflate)
+        self.max_seg = FIELD_NO_CAP if max_seg is None else int(max_seg)
+        if not 0 <= self.r_inflate <= 16 or self.max_seg < 5:
+            raise ValueError(f"invalid field planner parameters (r_inflate {r_inflate}: 0..16, max_seg {max_seg}: >= 5 or None)")
+        self.device_index = torch.cuda.current_device() if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index)
+        self.last = None            # outputs of the last plan_grid_batch
+
+    def _goal(self, goal):
+        goal = torch.as_tensor(goal).to(device=self.device, dtype=torch.float64).contiguous()
+        if goal.dim() != 2 or goal.shape[1] != 2:
+            raise ValueError("goal must be [1,2] or [B,2]")
+        return goal
+
+    def _field(self, goal, grid, out):
+        _lib.call("lipmpc_grid_field_batch", device=self.device_index, F=goal.shape[0], **grid._args(goal.shape[0], self.device), goal=goal,
+                  r_inflate=self.r_inflate, field=out["field"], field_status=out["field_status"],
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def field(self, goal, grid, out=None):
+        """The cost-to-go fields of ``goal`` [F,2] on ``grid`` (a GridMap: shared, or one map per goal).  Returns dict(field
+        [F,W,H] uint32 (FIELD_INF = blocked or cut off), status [F]: 0 OK, 1 the goal's cell is outside the grid, 2 it is blocked
+        -- then the whole field is FIELD_INF).  ``out``: dict(field, field_status) to write into."""
+        goal = self._goal(goal)
+        F = goal.shape[0]
+        grid = grid.to(self.device)
+        table = field_plan_outputs(0, F, grid.W, grid.H, 1)
+        names = ("field", "field_status")
+        if out is None:
+            out = _alloc(table, names, self.device)
+        else:
+            _check_table({k: table[k] for k in names}, out, self.device, "out")
+        self._field(goal, grid, out)
+        return dict(field=out["field"], status=out["field_status"])
+
+    def plan_grid_batch(self, goal, grid, start, S_max: int | None = 64, seeds=None, out=None):
+        """Plan B robots from ``start`` [B,2] on ``grid``.  ``goal`` [B,2]: one field per robot (``grid`` shared or one map per
+        robot); ``goal`` [1,2]: ONE field that every robot descends (``grid`` shared) -- the caller opts in by the shape, rows
+        are never compared.  ``seeds`` is accepted and ignored (the planner has none): an instance is a ``planner=`` of
+        ``UnknownEnvFleet.run_replanning``.  Returns the dict of ``RrtStarPlanner.plan_grid_batch`` -- sub_goals [B,S_max,2] (rows
+        past n_sub are 0 in a fresh ``out``, untouched in a given one; the last sub-goal is the goal itself, bit for bit), n_sub
+        [B], status [B] (RRT_*), path_cost [B] (the path's length in cells) -- plus field [F,W,H] and field_status [F].
+        ``out``: that dict, to write into (a captured graph replays into the same buffers)."""
+        goal = self._goal(goal)
+        start = torch.as_tensor(start).to(device=self.device, dtype=torch.float64).contiguous()
+        if start.dim() != 2 or start.shape[1] != 2:
+            raise ValueError("start must be [B,2]")
+        B, F = start.shape[0], goal.shape[0]
+        if F != B and F != 1:
+            raise ValueError(f"goal must be [1,2] or [B,2] with B = {B}")
+        grid = grid.to(self.device)
+        S_max = 64 if S_max is None else int(S_max)
+        table = field_plan_outputs(B, F, grid.W, grid.H, S_max)
+        if out is None:
+            out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost"), self.device, torch.zeros)
+            out.update(_alloc(table, ("field", "field_status"), self.device))            # written whole by the field call
+        else:
+            _check_table(table, out, self.device, "out")
+        if B == 0:
+            return out
+        self._field(goal, grid, out)
+        ga = grid._args(F, self.device)
+        _lib.call("lipmpc_grid_path_batch", device=self.device_index, B=B, F=F, **ga, field=out["field"], field_status=out["field_status"],
+                  goal=goal, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
+                  **_named(out, ("sub_goals", "n_sub", "status", "path_cost")), hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self.last = out
+        return out

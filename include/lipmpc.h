@@ -515,6 +515,78 @@ int lipmpc_rrt_plan_grid_batch(int device, const lipmpc_rrt_params* p, int64_t B
                                int32_t* status, double* path_cost, int32_t* grid_dims, int32_t* occ_d2, double* cost_grid,
                                double* tree, int32_t S_max, void* hip_stream);
 
+/* GRID FIELD PLANNER (backward-compatible addition): a COMPLETE, DETERMINISTIC global planner on an occupancy grid.  A
+ * cost-to-go field from a goal cell (lipmpc_grid_field_batch) and, down that field, sub-goals for any number of robots
+ * (lipmpc_grid_path_batch).  A path that exists is found, it is a shortest one in the metric below, there is no seed, and one
+ * field serves every robot that shares the map and the goal.  Both calls: all pointers DEVICE pointers but origin / cell (HOST);
+ * asynchronous on hip_stream; no allocation and no host synchronisation, so they can be captured in a graph; every refusal is a
+ * return code decided on the host before anything is enqueued.
+ *
+ * lipmpc_grid_field_batch: F fields, one workgroup per field.
+ *  W, H, grid_shared, origin, cell, occ: the grid as lipmpc_rrt_plan_grid_batch takes it (occ uint8, [W,H] if grid_shared else
+ *         [F,W,H], cell (i, j) at occ[i * H + j]; the cell rectangles of lipmpc_lidar_grid_c_eta_batch); W, H >= 2
+ *  goal   [F,2];  r_inflate  0..16, in cells (e.g. the body radius over the cell size, rounded up)
+ *  field  [F,W,H] uint32, layout i * H + j;  field_status [F] int32
+ * THE FIELD of one goal:
+ *  - solid(c) <=> occ[c] != 0.  blocked(i, j) <=> some solid cell (i', j') OF THE GRID has (i - i')^2 + (j - j')^2 <= r_inflate^2.
+ *    There are no cells outside the grid: nothing outside blocks, and no move leaves the grid.
+ *  - goal cell: (floor((g_x - ox) / dx), floor((g_y - oy) / dy)), the grid scan's robot-cell rule, in IEEE double.
+ *  - field_status: LIPMPC_FIELD_OK; LIPMPC_FIELD_GOAL_OUTSIDE if the goal cell is outside the grid (a NaN coordinate included);
+ *    else LIPMPC_FIELD_GOAL_BLOCKED if it is blocked.  On a non-zero status the whole field is 0xFFFFFFFF (INF).
+ *  - moves go between unblocked cells, 8-connected; an axial step costs 5, a diagonal step 7.  A diagonal (di, dj) from (i, j)
+ *    is allowed only if (i + di, j) and (i, j + dj) are both unblocked (no corner is cut).
+ *  - field[c] = the least total cost from c to the goal cell; INF if there is no path or c is blocked.
+ *  The metric counts CELLS: on a grid with dx != dy lengths are in cells, not in metres.
+ *  The least cost is unique, so the field does not depend on the order in which the kernel relaxes its cells: two calls give
+ *  identical bits.  The field is kept in LDS, sized to the map, when 4 W H bytes beside the blocked bitmap (W H / 8 bytes) fit the
+ *  160 KiB of a workgroup (up to about 39,700 cells; a 92 x 80 map takes 30 KiB); a larger map is relaxed in `field` itself.
+ * LIPMPC_E_UNSUPPORTED: W * H > 2^17, W > 4096 or H > 4096 (the RRT planner's caps).  LIPMPC_E_ARG: F < 0, W or H < 2, a cell
+ *  size that is not positive and finite, an origin that is not finite, r_inflate outside 0..16, a null origin / cell / occ / goal /
+ *  field / field_status.  F = 0 enqueues nothing and returns 0. */
+#define LIPMPC_FIELD_OK            0
+#define LIPMPC_FIELD_GOAL_OUTSIDE  1
+#define LIPMPC_FIELD_GOAL_BLOCKED  2
+#define LIPMPC_FIELD_INF           0xFFFFFFFFu
+int lipmpc_grid_field_batch(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin,
+                            const double* cell, const uint8_t* occ, const double* goal, int32_t r_inflate, uint32_t* field,
+                            int32_t* field_status, void* hip_stream);
+
+/* lipmpc_grid_path_batch: B robots, one lane per robot, each down a field of lipmpc_grid_field_batch.
+ *  F      1 or B: robot b uses field f = (F == 1 ? 0 : b) -- with F = 1 every robot descends the one field
+ *  W, H, origin, cell, occ, grid_shared, goal [F,2], r_inflate: what the field call was given (occ [W,H] if grid_shared else [F,W,H])
+ *  field [F,W,H], field_status [F]: its outputs;  start [B,2]
+ *  max_seg  >= 5, in field units: the spacing cap of the sub-goals (a value no field reaches, e.g. 2^31 - 1: no cap)
+ *  sub_goals [B,S_max,2], n_sub [B], status [B] (LIPMPC_RRT_*: everything downstream of the RRT planner reads them unchanged),
+ *  path_cost [B]
+ * PER ROBOT, passable(c) <=> field[c] != INF:
+ *  - status, the first that applies: field_status[f] is GOAL_OUTSIDE -> LIPMPC_RRT_OUTSIDE_GRID; is GOAL_BLOCKED ->
+ *    LIPMPC_RRT_GOAL_OCCUPIED; the start cell (floor rule) is outside the grid -> LIPMPC_RRT_OUTSIDE_GRID; the start cell is
+ *    solid -> LIPMPC_RRT_START_OCCUPIED.
+ *  - SNAP: if the start cell is not passable (a robot walks closer to walls than r_inflate), the start becomes the cell with a
+ *    finite field within Chebyshev distance r_inflate + 1 of it that has the least (d^2, field, index), d^2 = di^2 + dj^2,
+ *    index = i * H + j; LIPMPC_RRT_NO_PATH if there is none.
+ *  - DESCENT: from cell c the next cell is the first neighbour n in the order (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1),
+ *    (1,0), (1,1) with field[n] + cost == field[c], a diagonal only past two passable side cells; it ends where the field is 0.
+ *    The path is c_0 (the start after the snap), c_1, ..., c_L (the goal cell).
+ *  - SUB-GOALS BY STRING PULLING: the anchor a is c_0.  Walking k = 1, 2, ...: when LOS(a, c_k) fails, or the path cost since the
+ *    anchor, field[a] - field[c_k], reaches max_seg, the centre of c_{k-1} is emitted -- of c_k if c_{k-1} is the anchor itself
+ *    -- the emitted cell becomes the anchor and the walk goes on from the cell after it.  LOS is the RRT planner's segment rule:
+ *    endpoints in lexicographic order, m = max(|di|, |dj|), cells a + floor((2 k d + m) / (2 m)), k = 0..m, every one passable.
+ *    A cell centre is (ox + (i + 0.5) * dx, oy + (j + 0.5) * dy), evaluated as written in double, no contraction.
+ *    The goal cell's centre is never emitted: the LAST sub-goal is the given goal[f], bit for bit (a caller recognises the
+ *    arrival at its final goal by equality).
+ *  - outputs: LIPMPC_RRT_FOUND with n_sub >= 1 rows written, rows from n_sub on untouched; more than S_max sub-goals ->
+ *    LIPMPC_RRT_PATH_OVERFLOW, nothing written; n_sub = 0 unless FOUND; path_cost = field[start cell after the snap] / 5.0, the
+ *    path's length in cells (NaN unless FOUND / PATH_OVERFLOW).  A `field` that is no cost-to-go field of this map (no neighbour
+ *    satisfies the descent) ends LIPMPC_RRT_NO_PATH.
+ * Restated in numpy by tests/field_oracle.py (Dijkstra); the device's outputs equal it bit for bit.
+ * LIPMPC_E_UNSUPPORTED as the field call.  LIPMPC_E_ARG: what the field call refuses, B < 0, F neither 1 nor B, max_seg < 5,
+ *  S_max < 1, a null pointer.  B = 0 enqueues nothing and returns 0. */
+int lipmpc_grid_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell,
+                           const uint8_t* occ, int32_t grid_shared, const uint32_t* field, const int32_t* field_status,
+                           const double* goal, const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
+                           double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, void* hip_stream);
+
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
  * c_eta, in the form lipmpc_plan_step_batch_c_eta solves against -- after the rows of a scan (first_slot = the scan's
