@@ -83,6 +83,10 @@ SIGNATURES = {
                                              "hip_stream"),
     "lipmpc_grid_path_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell occ grid_shared:i32 field field_status goal start "
                                             "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost hip_stream"),
+    "lipmpc_grid_frontier_field_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 evidence t_free:i32 t_occ:i32 r_inflate:i32 min_unknown:i32 "
+                                                      "frontier field n_frontier hip_stream"),
+    "lipmpc_grid_frontier_path_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell evidence t_occ:i32 field n_frontier start "
+                                                     "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost target_cell hip_stream"),
     "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
                                              "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),

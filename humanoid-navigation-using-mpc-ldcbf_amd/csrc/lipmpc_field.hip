@@ -5,6 +5,11 @@
 //                        point.  The field lives in LDS (sized to the map) when it fits beside the blocked bitmap, else in the
 //                        output buffer itself.
 //   grid_path_kernel     one lane per robot: snap, steepest descent down a field, sub-goals by string pulling.
+// and the frontier explorer (lipmpc_grid_frontier_field_batch, lipmpc_grid_frontier_path_batch) on an evidence grid:
+//   frontier_field_*_kernel  one workgroup per map: evidence -> solid and unknown bitmaps, blocked = unknown | solid dilated,
+//                            frontier = unblocked with enough unknown neighbours, then the same relaxation from EVERY frontier
+//                            cell at once: the cost-to-go to the nearest frontier.
+//   frontier_path_kernel     grid_path_kernel's snap, descent and string pulling, ending at the first frontier cell reached.
 // Everything the two kernels compare is an integer but the two floors that name a cell; the cell centres are one multiply and
 // one add, contraction off.  tests/field_oracle.py restates both contracts (Dijkstra) and the GPU tests hold every output to it
 // bit for bit.
@@ -16,6 +21,9 @@
 // races fell in.  The diagonal rule is judged on the FIELD (both side cells finite) instead of the bitmap: a side cell of a legal
 // diagonal is unblocked and an axial neighbour of n, so it is finite wherever n is once the sweeps have settled -- the same fixed
 // point, and a sweep reads nine field words and one bit per cell.
+// SEVERAL SOURCES change nothing in that argument: with f(s) = 0 on every frontier cell s, a value is the cost of a real path to
+// SOME source, the fixed point's finite values are >= the least cost to any source and, along a least-cost path to the nearest
+// one, <= it.  The frontier field is as unique as the goal field, whatever order the races fell in.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -34,6 +42,7 @@ constexpr int64_t LDS_LIMIT = 160 * 1024;
 constexpr int64_t LDS_SLACK = 256;                  // the workgroup reduction's own words
 constexpr uint32_t INF = 0xFFFFFFFFu;
 constexpr int R_INFLATE_MAX = 16;
+constexpr int THRESHOLD_MAX = 1 << 30;                // of the frontier calls' t_free and t_occ: -t_free is an int32
 constexpr uint32_t AXIAL = 5, DIAGONAL = 7;
 
 // bitmap words of n cells: whole 64-cell ballots, + 2 so that a 64-bit window may start in the last word
@@ -46,6 +55,16 @@ __host__ __device__ inline int64_t field_lds_bytes(int64_t ncells, bool in_lds) 
 }
 
 inline bool field_fits_lds(int64_t ncells) { return field_lds_bytes(ncells, true) + LDS_SLACK <= LDS_LIMIT; }
+
+// LDS of the frontier field kernels: three bitmaps (blocked, solid, unknown: the frontier test reads the last two while the
+// field is seeded, so the field does not take their place), the frontier count (a word pair: the field stays 8-byte aligned),
+// then the field -- or bitmaps and count alone
+__host__ __device__ inline int64_t frontier_bitmap_words(int64_t ncells) { return 3 * bitmap_words(ncells) + 2; }
+__host__ __device__ inline int64_t frontier_lds_bytes(int64_t ncells, bool in_lds) {
+  return 4 * (frontier_bitmap_words(ncells) + (in_lds ? ncells : 0));
+}
+
+inline bool frontier_fits_lds(int64_t ncells) { return frontier_lds_bytes(ncells, true) + LDS_SLACK <= LDS_LIMIT; }
 
 __device__ inline bool bit_of(const uint32_t* bm, int c) { return (bm[c >> 5] >> (c & 31)) & 1u; }
 
@@ -62,64 +81,30 @@ __device__ inline bool cell_of(double x, double y, double ox, double oy, double 
 template <typename P> __device__ inline uint32_t ld(P p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 template <typename P> __device__ inline void st(P p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-// blockIdx.x = field.  `fld`: the field's working copy ([W*H], LDS or the output itself); `solid`: bitmap scratch, free to
-// overlap fld; `blk`: the blocked bitmap.
-template <bool COPY_OUT, typename FieldPtr>
-__device__ inline void field_body(FieldPtr fld, uint32_t* solid, uint32_t* blk, int W, int H, int64_t occ_stride, double ox, double oy,
-                                  double dx, double dy, const uint8_t* __restrict__ occ, const double* __restrict__ goal,
-                                  int r_inflate, uint32_t* field_out, int32_t* __restrict__ field_status) {
-  const int64_t f = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
-  const uint8_t* oc = occ + f * occ_stride;
-  uint32_t* out = field_out + f * (int64_t)ncells;
+// 64 bits of a bitmap from cell c on (layout i * H + j; a bitmap has two spare words, so the pair is always inside)
+__device__ inline uint64_t window(const uint32_t* bm, int c) { return (((uint64_t)bm[(c >> 5) + 1] << 32) | bm[c >> 5]) >> (c & 31); }
 
-  // solid bytes -> bitmap words: a wave's ballot over 64 consecutive cells is a word pair
-  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
-    const int c = c0 + lane;
-    const uint64_t m = __ballot(c < ncells && oc[c] != 0);
-    if (lane == 0) { solid[c0 >> 5] = (uint32_t)m; solid[(c0 >> 5) + 1] = (uint32_t)(m >> 32); }
-  }
-  if (tid < 2) { solid[words - 2 + tid] = 0; blk[words - 2 + tid] = 0; }
-  __syncthreads();
-  // blocked = solid dilated by the disc: per row i + di the cells j - w .. j + w, w = floor(sqrt(r^2 - di^2)), are at most 33
-  // consecutive bits of the bitmap (layout i * H + j), one 64-bit window
+// some solid cell of the grid within the disc of r_inflate around (i, j): per row i + di the cells j - w .. j + w,
+// w = floor(sqrt(r^2 - di^2)), are at most 33 consecutive bits of the bitmap, one 64-bit window
+__device__ inline bool disc_hits(const uint32_t* solid, int W, int H, int i, int j, int r_inflate) {
   const int r2 = r_inflate * r_inflate;
-  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
-    const int c = c0 + lane;
-    bool b = false;
-    if (c < ncells) {
-      const int i = c / H, j = c - i * H;
-      for (int di = -r_inflate; di <= r_inflate; ++di) {
-        const int ii = i + di, rem = r2 - di * di;
-        if (ii < 0 || ii >= W) continue;
-        int w = (int)sqrtf((float)rem);
-        while (w * w > rem) --w;
-        while ((w + 1) * (w + 1) <= rem) ++w;
-        const int lo = max(j - w, 0), hi = min(j + w, H - 1);
-        const int c1 = ii * H + lo, n = hi - lo + 1;
-        const uint64_t win = (((uint64_t)solid[(c1 >> 5) + 1] << 32) | solid[c1 >> 5]) >> (c1 & 31);
-        b |= (win & ((1ull << n) - 1)) != 0;
-      }
-    }
-    const uint64_t m = __ballot(b);
-    if (lane == 0) { blk[c0 >> 5] = (uint32_t)m; blk[(c0 >> 5) + 1] = (uint32_t)(m >> 32); }
+  bool b = false;
+  for (int di = -r_inflate; di <= r_inflate; ++di) {
+    const int ii = i + di, rem = r2 - di * di;
+    if (ii < 0 || ii >= W) continue;
+    int w = (int)sqrtf((float)rem);
+    while (w * w > rem) --w;
+    while ((w + 1) * (w + 1) <= rem) ++w;
+    const int lo = max(j - w, 0), hi = min(j + w, H - 1);
+    b |= (window(solid, ii * H + lo) & ((1ull << (hi - lo + 1)) - 1)) != 0;
   }
-  __syncthreads();                                    // (the solid bitmap is dead from here: the field may take its place)
+  return b;
+}
 
-  int gi = 0, gj = 0;
-  const bool inside = cell_of(goal[2 * f], goal[2 * f + 1], ox, oy, dx, dy, W, H, gi, gj);
-  const int gc = gi * H + gj;
-  const int status = !inside ? LIPMPC_FIELD_GOAL_OUTSIDE : bit_of(blk, gc) ? LIPMPC_FIELD_GOAL_BLOCKED : LIPMPC_FIELD_OK;
-  if (tid == 0) field_status[f] = status;
-  if (status != LIPMPC_FIELD_OK) {
-    for (int c = tid; c < ncells; c += FIELD_THREADS) out[c] = INF;
-    return;
-  }
-  for (int c = tid; c < ncells; c += FIELD_THREADS) st(fld + c, c == gc ? 0u : INF);
-  __syncthreads();
-
-  // sweeps: thread t owns the cells t, t + T, ...; (i, j) advance by T = qi * H + rj without a division
+// the sweeps, from a field that holds 0 on its sources and INF elsewhere, to the fixed point: thread t owns the cells t, t + T,
+// ...; (i, j) advance by T = qi * H + rj without a division
+template <typename FieldPtr> __device__ inline void relax(FieldPtr fld, const uint32_t* blk, int W, int H) {
+  const int tid = threadIdx.x, ncells = W * H;
   const int qi = FIELD_THREADS / H, rj = FIELD_THREADS - qi * H, i0 = tid / H, j0 = tid - i0 * H;
   for (;;) {
     int changed = 0;
@@ -144,6 +129,54 @@ __device__ inline void field_body(FieldPtr fld, uint32_t* solid, uint32_t* blk, 
     }
     if (!__syncthreads_or(changed)) break;
   }
+}
+
+// blockIdx.x = field.  `fld`: the field's working copy ([W*H], LDS or the output itself); `solid`: bitmap scratch, free to
+// overlap fld; `blk`: the blocked bitmap.
+template <bool COPY_OUT, typename FieldPtr>
+__device__ inline void field_body(FieldPtr fld, uint32_t* solid, uint32_t* blk, int W, int H, int64_t occ_stride, double ox, double oy,
+                                  double dx, double dy, const uint8_t* __restrict__ occ, const double* __restrict__ goal,
+                                  int r_inflate, uint32_t* field_out, int32_t* __restrict__ field_status) {
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  const uint8_t* oc = occ + f * occ_stride;
+  uint32_t* out = field_out + f * (int64_t)ncells;
+
+  // solid bytes -> bitmap words: a wave's ballot over 64 consecutive cells is a word pair
+  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+    const int c = c0 + lane;
+    const uint64_t m = __ballot(c < ncells && oc[c] != 0);
+    if (lane == 0) { solid[c0 >> 5] = (uint32_t)m; solid[(c0 >> 5) + 1] = (uint32_t)(m >> 32); }
+  }
+  if (tid < 2) { solid[words - 2 + tid] = 0; blk[words - 2 + tid] = 0; }
+  __syncthreads();
+  // blocked = solid dilated by the disc
+  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+    const int c = c0 + lane;
+    bool b = false;
+    if (c < ncells) {
+      const int i = c / H, j = c - i * H;
+      b = disc_hits(solid, W, H, i, j, r_inflate);
+    }
+    const uint64_t m = __ballot(b);
+    if (lane == 0) { blk[c0 >> 5] = (uint32_t)m; blk[(c0 >> 5) + 1] = (uint32_t)(m >> 32); }
+  }
+  __syncthreads();                                    // (the solid bitmap is dead from here: the field may take its place)
+
+  int gi = 0, gj = 0;
+  const bool inside = cell_of(goal[2 * f], goal[2 * f + 1], ox, oy, dx, dy, W, H, gi, gj);
+  const int gc = gi * H + gj;
+  const int status = !inside ? LIPMPC_FIELD_GOAL_OUTSIDE : bit_of(blk, gc) ? LIPMPC_FIELD_GOAL_BLOCKED : LIPMPC_FIELD_OK;
+  if (tid == 0) field_status[f] = status;
+  if (status != LIPMPC_FIELD_OK) {
+    for (int c = tid; c < ncells; c += FIELD_THREADS) out[c] = INF;
+    return;
+  }
+  for (int c = tid; c < ncells; c += FIELD_THREADS) st(fld + c, c == gc ? 0u : INF);
+  __syncthreads();
+
+  relax(fld, blk, W, H);
   if (COPY_OUT)
     for (int c = tid; c < ncells; c += FIELD_THREADS) out[c] = ld(fld + c);
 }
@@ -165,6 +198,96 @@ __global__ void __launch_bounds__(FIELD_THREADS) grid_field_global_kernel(int W,
   uint32_t* fld = field + (int64_t)blockIdx.x * W * H;
   field_body<false>(fld, field_lds + bitmap_words((int64_t)W * H), field_lds, W, H, occ_stride, ox, oy, dx, dy, occ, goal, r_inflate, field,
              field_status);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// blockIdx.x = map.  `fld`: the field's working copy ([W*H], LDS or the output itself); `bm`: three bitmaps and the count's
+// word, apart from fld.
+template <bool COPY_OUT, typename FieldPtr>
+__device__ inline void frontier_body(FieldPtr fld, uint32_t* bm, int W, int H, const int32_t* __restrict__ evidence, int t_free,
+                                     int t_occ, int r_inflate, int min_unknown, uint8_t* __restrict__ frontier, uint32_t* field_out,
+                                     int32_t* __restrict__ n_frontier) {
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  uint32_t *blk = bm, *solid = bm + words, *unk = bm + 2 * words, *n_front = bm + 3 * words;
+  const int32_t* ev = evidence + f * (int64_t)ncells;
+  uint32_t* out = field_out + f * (int64_t)ncells;
+  uint8_t* fr_out = frontier ? frontier + f * (int64_t)ncells : nullptr;
+
+  // evidence -> solid and unknown bitmaps (t_free, t_occ >= 1: the two plain comparisons hold for every int32, and never both)
+  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+    const int c = c0 + lane;
+    const int e = c < ncells ? ev[c] : 0;
+    const bool is_solid = c < ncells && e >= t_occ, is_free = e <= -t_free;
+    const uint64_t ms = __ballot(is_solid), mu = __ballot(c < ncells && !is_solid && !is_free);
+    if (lane == 0) {
+      solid[c0 >> 5] = (uint32_t)ms; solid[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      unk[c0 >> 5] = (uint32_t)mu; unk[(c0 >> 5) + 1] = (uint32_t)(mu >> 32);
+    }
+  }
+  if (tid < 2) { solid[words - 2 + tid] = 0; unk[words - 2 + tid] = 0; blk[words - 2 + tid] = 0; }
+  if (tid == 0) *n_front = 0;
+  __syncthreads();
+  // blocked = not free, or within the disc of a solid cell = unknown | solid dilated (the disc holds its own centre)
+  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+    const int c = c0 + lane;
+    bool b = false;
+    if (c < ncells) {
+      const int i = c / H, j = c - i * H;
+      b = bit_of(unk, c) | disc_hits(solid, W, H, i, j, r_inflate);
+    }
+    const uint64_t m = __ballot(b);
+    if (lane == 0) { blk[c0 >> 5] = (uint32_t)m; blk[(c0 >> 5) + 1] = (uint32_t)(m >> 32); }
+  }
+  __syncthreads();
+  // frontier = unblocked with >= min_unknown unknown cells among the neighbours inside the grid: per row i - 1, i, i + 1 the
+  // cells j - 1 .. j + 1, clipped to the row, are up to three bits of one window (the cell itself is unblocked, so not unknown).
+  // Every frontier cell is a source of the field.
+  int mine = 0;
+  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+    const int c = c0 + lane;
+    bool fr = false;
+    if (c < ncells) {
+      if (!bit_of(blk, c)) {
+        const int i = c / H, j = c - i * H;
+        const int lo = max(j - 1, 0), hi = min(j + 1, H - 1);
+        const uint64_t mask = (1ull << (hi - lo + 1)) - 1;
+        int cnt = __popcll(window(unk, c - j + lo) & mask);
+        if (i > 0) cnt += __popcll(window(unk, c - H - j + lo) & mask);
+        if (i < W - 1) cnt += __popcll(window(unk, c + H - j + lo) & mask);
+        fr = cnt >= min_unknown;
+      }
+      st(fld + c, fr ? 0u : INF);
+      if (fr_out) fr_out[c] = fr;
+    }
+    mine += __popcll(__ballot(fr));
+  }
+  if (lane == 0 && mine) atomicAdd(n_front, (uint32_t)mine);     // (integers: the sum is the same in any order)
+  __syncthreads();
+  const int n = (int)*n_front;
+  if (tid == 0) n_frontier[f] = n;
+  if (n) relax(fld, blk, W, H);                          // (no frontier: the field is INF as it stands)
+  if (COPY_OUT)
+    for (int c = tid; c < ncells; c += FIELD_THREADS) out[c] = ld(fld + c);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_field_lds_kernel(int W, int H, const int32_t* __restrict__ evidence, int t_free,
+                                                                           int t_occ, int r_inflate, int min_unknown,
+                                                                           uint8_t* __restrict__ frontier, uint32_t* __restrict__ field,
+                                                                           int32_t* __restrict__ n_frontier) {
+  extern __shared__ uint32_t field_lds[];
+  frontier_body<true>(field_lds + frontier_bitmap_words((int64_t)W * H), field_lds, W, H, evidence, t_free, t_occ, r_inflate, min_unknown,
+                      frontier, field, n_frontier);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_field_global_kernel(int W, int H, const int32_t* __restrict__ evidence,
+                                                                              int t_free, int t_occ, int r_inflate, int min_unknown,
+                                                                              uint8_t* __restrict__ frontier, uint32_t* field,
+                                                                              int32_t* __restrict__ n_frontier) {
+  extern __shared__ uint32_t field_lds[];
+  frontier_body<false>(field + (int64_t)blockIdx.x * W * H, field_lds, W, H, evidence, t_free, t_occ, r_inflate, min_unknown, frontier,
+                       field, n_frontier);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -202,6 +325,57 @@ __device__ inline int descend(const uint32_t* __restrict__ fld, int W, int H, in
   return -1;
 }
 
+// snap: the finite cell of the window round (si, sj) with the least (d^2, field, index); ascending index, so only a smaller pair
+// replaces; -1 if the window has none
+__device__ inline int snap(const uint32_t* __restrict__ fld, int W, int H, int si, int sj, int r_inflate) {
+  const int n = r_inflate + 1;
+  uint64_t best = ~0ull;
+  int at = -1;
+  for (int i = max(si - n, 0); i <= min(si + n, W - 1); ++i)
+    for (int j = max(sj - n, 0); j <= min(sj + n, H - 1); ++j) {
+      const uint32_t v = fld[i * H + j];
+      if (v == INF) continue;
+      const uint64_t key = ((uint64_t)(uint32_t)((i - si) * (i - si) + (j - sj) * (j - sj)) << 32) | v;
+      if (key < best) { best = key; at = i * H + j; }
+    }
+  return at;
+}
+
+__device__ inline void centre(int c, int H, double ox, double oy, double dx, double dy, double* p) {
+  const int i = c / H, j = c - i * H;
+  p[0] = ox + ((double)i + 0.5) * dx;
+  p[1] = oy + ((double)j + 0.5) * dy;
+}
+
+// the walk from s down the field to the first cell whose field is 0 (`last`): the number of sub-goals, that cell's included (its
+// row is the caller's to write), or -1 where no neighbour satisfies the descent.  `sg`: where to write them, or null to count.
+__device__ inline int walk(const uint32_t* __restrict__ fld, int W, int H, int s, int max_seg, double ox, double oy, double dx, double dy,
+                           double* sg, int& last_cell) {
+  int count = 0;
+  auto emit = [&](int c) {
+    if (sg) centre(c, H, ox, oy, dx, dy, sg + 2 * count);
+    ++count;
+  };
+  last_cell = s;
+  if (fld[s] != 0) {
+    int a = s, prev = s, cur = descend(fld, W, H, s);
+    while (cur >= 0) {
+      const bool last = fld[cur] == 0;
+      if (!los(fld, H, a, cur) || fld[a] - fld[cur] >= (uint32_t)max_seg) {
+        if (prev != a) { emit(prev); a = prev; continue; }          // cur is looked at again from the new anchor
+        if (last) break;
+        emit(cur); a = cur;
+      }
+      if (last) break;
+      prev = cur;
+      cur = descend(fld, W, H, cur);
+    }
+    if (cur < 0) return -1;
+    last_cell = cur;
+  }
+  return count + 1;
+}
+
 // One lane per robot.
 __global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int one_field, int W, int H, int64_t occ_stride, double ox,
                                                                  double oy, double dx, double dy, const uint8_t* __restrict__ occ,
@@ -225,58 +399,53 @@ __global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int 
   if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan);
   int s = si * H + sj;
   if (occ[f * occ_stride + s] != 0) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan);
-  if (fld[s] == INF) {
-    // snap: the finite cell of the window with the least (d^2, field, index); ascending index, so only a smaller pair replaces
-    const int n = r_inflate + 1;
-    uint64_t best = ~0ull;
-    int at = -1;
-    for (int i = max(si - n, 0); i <= min(si + n, W - 1); ++i)
-      for (int j = max(sj - n, 0); j <= min(sj + n, H - 1); ++j) {
-        const uint32_t v = fld[i * H + j];
-        if (v == INF) continue;
-        const uint64_t key = ((uint64_t)(uint32_t)((i - si) * (i - si) + (j - sj) * (j - sj)) << 32) | v;
-        if (key < best) { best = key; at = i * H + j; }
-      }
-    if (at < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);
-    s = at;
-  }
+  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
+  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);
   double* sg = sub_goals + b * (int64_t)S_max * 2;
   // the walk, twice: count the sub-goals, then -- if they fit -- write them (rows past n_sub stay untouched)
-  auto walk = [&](bool write) {
-    int count = 0;
-    auto emit = [&](int c) {
-      if (write) {
-        const int i = c / H, j = c - i * H;
-        sg[2 * count] = ox + ((double)i + 0.5) * dx;
-        sg[2 * count + 1] = oy + ((double)j + 0.5) * dy;
-      }
-      ++count;
-    };
-    if (fld[s] != 0) {
-      int a = s, prev = s, cur = descend(fld, W, H, s);
-      while (cur >= 0) {
-        const bool last = fld[cur] == 0;
-        if (!los(fld, H, a, cur) || fld[a] - fld[cur] >= (uint32_t)max_seg) {
-          if (prev != a) { emit(prev); a = prev; continue; }          // cur is looked at again from the new anchor
-          if (last) break;
-          emit(cur); a = cur;
-        }
-        if (last) break;
-        prev = cur;
-        cur = descend(fld, W, H, cur);
-      }
-      if (cur < 0) return -1;
-    }
-    return count + 1;                                                 // + the goal itself
-  };
-  const int n = walk(false);
+  int last_cell;
+  const int n = walk(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
   if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);                 // (a `field` that is no cost-to-go field of this map)
   const double cost = (double)fld[s] / 5.0;
   if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, cost);
-  walk(true);
-  sg[2 * (n - 1)] = goal[2 * f];
+  walk(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  sg[2 * (n - 1)] = goal[2 * f];                                      // the goal itself, not its cell's centre
   sg[2 * (n - 1) + 1] = goal[2 * f + 1];
   done(LIPMPC_RRT_FOUND, n, cost);
+}
+
+// One lane per robot: grid_path_kernel down a frontier field, to the centre of the first frontier cell reached.
+__global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, int one_field, int W, int H, double ox, double oy, double dx,
+                                                                     double dy, const int32_t* __restrict__ evidence, int t_occ,
+                                                                     const uint32_t* __restrict__ field,
+                                                                     const int32_t* __restrict__ n_frontier,
+                                                                     const double* __restrict__ start, int r_inflate, int max_seg,
+                                                                     int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+                                                                     int32_t* __restrict__ status, double* __restrict__ path_cost,
+                                                                     int32_t* __restrict__ target_cell) {
+  const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const int64_t f = one_field ? 0 : b;
+  const int ncells = W * H;
+  const uint32_t* fld = field + f * (int64_t)ncells;
+  auto done = [&](int st_, int n, double cost, int target) { status[b] = st_; n_sub[b] = n; path_cost[b] = cost; target_cell[b] = target; };
+  const double nan = __builtin_nan("");
+  int si = 0, sj = 0;
+  if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan, -1);
+  int s = si * H + sj;
+  if (evidence[f * (int64_t)ncells + s] >= t_occ) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan, -1);
+  if (n_frontier[f] == 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
+  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  double* sg = sub_goals + b * (int64_t)S_max * 2;
+  int last_cell;
+  const int n = walk(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
+  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);             // (a `field` that is no frontier field of this map)
+  const double cost = (double)fld[s] / 5.0;
+  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, cost, last_cell);
+  walk(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
+  done(LIPMPC_RRT_FOUND, n, cost, last_cell);
 }
 
 // what both entry points refuse about the grid: E_ARG, then the caps
@@ -329,5 +498,47 @@ extern "C" int lipmpc_grid_path_batch(int device, int64_t B, int64_t F, int32_t 
                      (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1],
                      cell[0], cell[1], occ, field, field_status, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
                      path_cost);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_field_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                                int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier,
+                                                uint32_t* field, int32_t* n_frontier, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
+      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || !field || !n_frontier)
+    return LIPMPC_E_ARG;
+  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t ncells = (int64_t)W * H;
+  const bool in_lds = frontier_fits_lds(ncells);
+  const size_t lds = (size_t)frontier_lds_bytes(ncells, in_lds);
+  if (in_lds) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_field_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+      return LIPMPC_E_HIP;
+    hipLaunchKernelGGL(frontier_field_lds_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, evidence, t_free, t_occ,
+                       r_inflate, min_unknown, frontier, field, n_frontier);
+  } else {
+    hipLaunchKernelGGL(frontier_field_global_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, evidence, t_free, t_occ,
+                       r_inflate, min_unknown, frontier, field, n_frontier);
+  }
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                               const double* cell, const int32_t* evidence, int32_t t_occ, const uint32_t* field,
+                                               const int32_t* n_frontier, const double* start, int32_t r_inflate, int32_t max_seg,
+                                               int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                               int32_t* target_cell, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
+  if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (!evidence || !field || !n_frontier || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell) return LIPMPC_E_ARG;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(frontier_path_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, field,
+                     n_frontier, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

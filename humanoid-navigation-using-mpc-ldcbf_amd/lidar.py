@@ -332,7 +332,8 @@ class UnknownEnvFleet:
     ``mapper=OccupancyMapper(...)``: the robots map what they see -- every sample the scan's readings of the walking robots are
     integrated into the mapper's evidence grid (lipmpc_map_update_batch) between the scan and the solve, inside the captured
     graph; the loop itself is not disturbed (same X_pred / U_pred, bit for bit).  A run adds to the evidence the mapper holds
-    (``mapper.reset()`` forgets it).  ``run_replanning`` plans on that map."""
+    (``mapper.reset()`` forgets it).  ``run_replanning`` plans on that map toward given goals; ``run_exploring`` needs no goals:
+    the robots walk to the map's frontiers until none is left."""
 
     def __init__(self, env_rings=None, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
                  exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None, mapper=None):
@@ -523,6 +524,79 @@ class UnknownEnvFleet:
 
         res = self._run(state0, final, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=replan)
         res.update(info, working_goal=self._plan["goal"], walking=self._plan["fl"]["walking"])
+        return res
+
+    def run_exploring(self, state0, first_foot, k_max, explorer, replan_every, lookahead, noise="seeded", noise_seed=0, delta=None,
+                      stop_obj=0.05, use_graph=True, S_max=None):
+        """``run`` without goals: the fleet explores (``mapper`` is required; ``explorer``: a ``FrontierPlanner`` on the fleet's
+        device).  Every robot walks to the nearest frontier of the map the fleet builds, until no frontier is left.  The loop is
+        driven from the host, all per-robot work runs on the device, nothing is copied device -> host per sample or per replan.
+        Before sample 0 one NOISE-FREE scan of ``state0`` goes into the map (without it no cell is free and nothing can be
+        planned).  Every ``replan_every`` samples (sample 0 included) all robots are planned in one ``explorer.plan`` on
+        ``mapper.evidence``:
+          - a robot whose plan is RRT_FOUND gets as working goal the first sub-goal of its path that is at least ``lookahead``
+            from it, or the frontier cell's centre when none is (``select_working_goals`` with its target as the goal);
+          - a robot that is not walking, whose last_status is SOLVED or UNCERTIFIED, and whose plan is FOUND walks again: robots
+            the stop rule stopped and robots parked earlier (a robot stopped by a failed solve stays stopped, as everywhere);
+          - a robot whose plan is not FOUND is parked (walking = 0; it keeps its working goal).
+        After the last sample one closing plan on the final map and positions parks likewise and sets no goal; it is not counted.
+        The model's limits: every robot goes to ITS nearest frontier (no task assignment), and the walker cannot turn on the
+        spot -- a working goal that jumps behind a robot can end its run in an INFEASIBLE solve.
+        Returns what ``run`` returns, plus n_replans (int), explore_status [B] (RRT_*) of the closing plan, working_goal [B,2],
+        walking [B] (int8), n_frontier and known_free [n_replans,F] (device tensors: per replan the frontier cells, and the cells
+        with evidence <= -t_free, of every map), and done [B] (bool): not walking, not stopped by a failed solve, and the closing
+        plan said RRT_NO_PATH -- for the robot nothing is left to explore.  The tensors are the object's or fresh ones; the
+        next run of the same shape overwrites the former."""
+        from .planner import RRT_FOUND, RRT_NO_PATH
+        from .solver import STATUS_SOLVED, STATUS_UNCERTIFIED
+        mapper = self.mapper
+        if mapper is None:
+            raise ValueError("run_exploring explores the fleet's map: UnknownEnvFleet(..., mapper=OccupancyMapper(...))")
+        replan_every, lookahead, k_max = int(replan_every), float(lookahead), int(k_max)
+        if replan_every < 1 or not lookahead >= 0.0:
+            raise ValueError("replan_every >= 1 and lookahead >= 0")
+        dev = self.device
+        state0 = state0.to(device=dev, dtype=torch.float64).contiguous()
+        B = state0.shape[0]
+        ev = mapper.evidence if mapper.evidence.dim() == 3 else mapper.evidence[None]
+        F = ev.shape[0]
+        rows = (k_max + replan_every - 1) // replan_every
+        t_free = mapper.w_miss if explorer.t_free is None else explorer.t_free
+        n_frontier = torch.zeros((rows, F), dtype=torch.int32, device=dev)
+        known_free = torch.zeros((rows, F), dtype=torch.int64, device=dev)
+        plan_out = [None]                                    # the plan's buffers: made by the first plan, reused by every later one
+        info = dict(n_replans=0)
+
+        def replan(k, pl, closing=False):
+            if not closing and k % replan_every:
+                return
+            fl, working = pl["fl"], pl["goal"]
+            if k == 0 and not closing:
+                # the first look round, noise-free: the run's own scans start with sample 0
+                self.sensor.sense(fl["state"], None, out=pl["sen"], c_eta=True, rings=False, schedule=pl["sched"])
+                mapper.update(fl["state"], pl["sen"]["hits"])
+            pos = fl["state"][:, (0, 2)].contiguous()
+            plan = plan_out[0] = explorer.plan(mapper, pos, S_max=64 if S_max is None else S_max, out=plan_out[0])
+            found = plan["status"] == RRT_FOUND
+            solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
+            if not closing:
+                resume = (fl["walking"] == 0) & solved & found
+                fl["walking"].masked_fill_(resume, 1)
+                fl["last_obj"].masked_fill_(resume, float("inf"))      # the objective of the goal it has reached says nothing about the next
+                picked = select_working_goals(pos, plan["target"], plan["sub_goals"], plan["n_sub"], plan["status"], lookahead, RRT_FOUND)
+                working.copy_(torch.where(found[:, None], picked, working))
+                n_frontier[info["n_replans"]].copy_(plan["n_frontier"])
+                known_free[info["n_replans"]].copy_((ev <= -t_free).sum((1, 2)))
+                info["n_replans"] += 1
+            fl["walking"].masked_fill_(~found, 0)
+            info["explore_status"] = plan["status"]
+
+        res = self._run(state0, state0[:, (0, 2)], first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=replan)
+        fl = self._plan["fl"]
+        replan(k_max, self._plan, closing=True)
+        solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
+        res.update(info, working_goal=self._plan["goal"], walking=fl["walking"], n_frontier=n_frontier, known_free=known_free,
+                   done=(fl["walking"] == 0) & solved & (info["explore_status"] == RRT_NO_PATH))
         return res
 
 

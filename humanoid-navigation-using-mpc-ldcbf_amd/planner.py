@@ -6,6 +6,10 @@
 
 ``GridFieldPlanner`` is the complete, deterministic planner on a given grid: a cost-to-go field from the goal
 (``lipmpc_grid_field_batch``) and sub-goals down it (``lipmpc_grid_path_batch``), in the same output form.
+
+``FrontierPlanner`` needs no goal: on the evidence grid an ``OccupancyMapper`` builds it finds the frontier of the known free
+space, the cost-to-go to the nearest frontier cell (``lipmpc_grid_frontier_field_batch``) and sub-goals down it
+(``lipmpc_grid_frontier_path_batch``).
 """
 from __future__ import annotations
 
@@ -32,6 +36,14 @@ def field_plan_outputs(B, F, W, H, S_max):
     f64, i32 = torch.float64, torch.int32
     return {"sub_goals": (f64, (B, S_max, 2), True), "n_sub": (i32, (B,), True), "status": (i32, (B,), True), "path_cost": (f64, (B,), True),
             "field": (torch.uint32, (F, W, H), True), "field_status": (i32, (F,), True)}
+
+
+def frontier_outputs(B, F, W, H, S_max):
+    """Outputs of FrontierPlanner.plan, in the order it returns them (field, frontier, n_frontier: FrontierPlanner.field's)."""
+    f64, i32 = torch.float64, torch.int32
+    return {"sub_goals": (f64, (B, S_max, 2), True), "n_sub": (i32, (B,), True), "status": (i32, (B,), True), "path_cost": (f64, (B,), True),
+            "target": (f64, (B, 2), True), "target_cell": (i32, (B,), True), "field": (torch.uint32, (F, W, H), True),
+            "frontier": (torch.uint8, (F, W, H), True), "n_frontier": (i32, (F,), True)}
 
 
 def plan_outputs(B, S_max, max_cells, n_samples):
@@ -290,5 +302,115 @@ class GridFieldPlanner:
         _lib.call("lipmpc_grid_path_batch", device=self.device_index, B=B, F=F, **ga, field=out["field"], field_status=out["field_status"],
                   goal=goal, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost")), hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self.last = out
+        return out
+
+
+class FrontierPlanner:
+    """Nearest-frontier exploration (Yamauchi 1997) on an evidence grid (include/lipmpc.h, FRONTIER EXPLORER): a cell is solid
+    with evidence >= ``t_occ``, free with evidence <= -``t_free`` and unknown otherwise; a FRONTIER cell is an unblocked cell with
+    at least ``min_unknown`` unknown cells among its 8 neighbours; the field is the cost-to-go to the nearest frontier cell over the
+    metric of ``GridFieldPlanner``, and every robot descends it to the centre of the frontier cell it reaches.  On a shared map one
+    field serves every robot.  ``r_inflate``: free cells within this many cells of a solid one are blocked, 0..16 (unknown cells
+    are impassable but not inflated).  ``t_free`` / ``t_occ``: None = the mapper's ``w_miss`` / ``w_hit``.  ``max_seg``: as
+    ``GridFieldPlanner``'s.
+    The model's limits: every robot heads for ITS nearest frontier -- there is no task assignment, two robots side by side pick
+    the same cell -- and n_frontier == 0 (status RRT_NO_PATH for everybody) is how "nothing left to explore" is told."""
+
+    def __init__(self, r_inflate: int = 2, min_unknown: int = 2, t_free: int | None = None, t_occ: int | None = None,
+                 max_seg: int | None = None, device: int | None = None):
+        self.r_inflate, self.min_unknown = int(r_inflate), int(min_unknown)
+        self.t_free = None if t_free is None else int(t_free)
+        self.t_occ = None if t_occ is None else int(t_occ)
+        self.max_seg = FIELD_NO_CAP if max_seg is None else int(max_seg)
+        if not 0 <= self.r_inflate <= 16 or not 1 <= self.min_unknown <= 8 or self.max_seg < 5 or \
+                any(t is not None and not 1 <= t <= 1 << 30 for t in (self.t_free, self.t_occ)):
+            raise ValueError(f"invalid frontier planner parameters (r_inflate {r_inflate}: 0..16, min_unknown {min_unknown}: 1..8, "
+                             f"t_free {t_free}, t_occ {t_occ}: 1..2^30 or None, max_seg {max_seg}: >= 5 or None)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("lipmpc needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
+        self.lib = _lib.load()
+        self.device_index = torch.cuda.current_device() if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index)
+        self._placed = {}           # (origin, cell) -> the two host arrays the C call reads
+        self.last = None            # outputs of the last plan
+
+    def _map(self, m, origin=None, cell=None):
+        """(evidence [F,W,H], t_free, t_occ, origin, cell) of a mapper or of an evidence tensor [W,H] / [F,W,H]."""
+        if isinstance(m, torch.Tensor):
+            ev, t_free, t_occ = m, self.t_free, self.t_occ
+            if t_free is None or t_occ is None:
+                raise ValueError("an evidence tensor has no weights: give the planner t_free and t_occ")
+        else:
+            ev = m.evidence
+            t_free, t_occ = (m.w_miss if self.t_free is None else self.t_free), (m.w_hit if self.t_occ is None else self.t_occ)
+            origin, cell = (m.origin if origin is None else origin), (m.cell if cell is None else cell)
+        if ev.dtype != torch.int32 or ev.device != self.device or not ev.is_contiguous() or ev.dim() not in (2, 3):
+            raise ValueError("evidence: a contiguous int32 tensor [W,H] or [F,W,H] on the planner's device")
+        return (ev if ev.dim() == 3 else ev[None]), int(t_free), int(t_occ), origin, cell
+
+    def _field(self, ev, t_free, t_occ, out):
+        F, W, H = ev.shape
+        _lib.call("lipmpc_grid_frontier_field_batch", device=self.device_index, F=F, W=W, H=H, evidence=ev, t_free=t_free, t_occ=t_occ,
+                  r_inflate=self.r_inflate, min_unknown=self.min_unknown, frontier=out["frontier"], field=out["field"],
+                  n_frontier=out["n_frontier"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def field(self, mapper_or_evidence, out=None):
+        """The frontier and the cost-to-go to it of an ``OccupancyMapper`` (shared or per-robot maps) or of an evidence tensor
+        [W,H] / [F,W,H].  Returns dict(field [F,W,H] uint32 (0 on frontier cells, FIELD_INF = blocked or cut off), frontier
+        [F,W,H] uint8, n_frontier [F]: 0 = nothing left to explore, the whole field FIELD_INF).  ``out``: that dict, to write into."""
+        ev, t_free, t_occ, _, _ = self._map(mapper_or_evidence)
+        table = frontier_outputs(0, *ev.shape, 1)
+        names = ("field", "frontier", "n_frontier")
+        if out is None:
+            out = _alloc(table, names, self.device)
+        else:
+            _check_table({k: table[k] for k in names}, out, self.device, "out")
+        self._field(ev, t_free, t_occ, out)
+        return {k: out[k] for k in names}
+
+    def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None):
+        """Plan B robots from ``start`` [B,2] to their nearest frontier: on a shared map (a mapper without ``per_robot``, an
+        evidence tensor [W,H] or [1,W,H]) every robot descends the one field, else there are B maps.  ``origin`` / ``cell``: the
+        grid's placement, for an evidence tensor (a mapper brings its own).  Returns the planners' dict -- sub_goals [B,S_max,2]
+        (rows past n_sub are 0 in a fresh ``out``, untouched in a given one; the last sub-goal is the centre of the frontier cell),
+        n_sub [B], status [B] (RRT_FOUND, RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID, RRT_START_OCCUPIED; RRT_NO_PATH: no frontier
+        left, or none within reach), path_cost [B] in cells -- plus target [B,2] (the frontier cell's centre; NaN unless FOUND or
+        PATH_OVERFLOW), target_cell [B] (its index i * H + j, else -1), n_frontier [F], field and frontier [F,W,H].
+        ``out``: that dict, to write into (a captured graph replays into the same buffers; nothing is allocated then)."""
+        ev, t_free, t_occ, origin, cell = self._map(mapper_or_evidence, origin, cell)
+        if origin is None or cell is None:
+            raise ValueError("an evidence tensor has no placement: give origin and cell")
+        cell = (float(cell), float(cell)) if isinstance(cell, (int, float)) else (float(cell[0]), float(cell[1]))
+        origin = (float(origin[0]), float(origin[1]))
+        start = torch.as_tensor(start).to(device=self.device, dtype=torch.float64).contiguous()
+        if start.dim() != 2 or start.shape[1] != 2:
+            raise ValueError("start must be [B,2]")
+        B, (F, W, H), S_max = start.shape[0], ev.shape, int(S_max)
+        if F != B and F != 1:
+            raise ValueError(f"{F} maps for {B} robots: one shared map, or one per robot")
+        table = frontier_outputs(B, F, W, H, S_max)
+        if out is None:
+            out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost", "target", "target_cell"), self.device, torch.zeros)
+            out.update(_alloc(table, ("field", "frontier", "n_frontier"), self.device))      # written whole by the field call
+        else:
+            _check_table(table, out, self.device, "out")
+        if B == 0:
+            return out
+        key = (origin, cell)
+        if key not in self._placed:
+            self._placed[key] = (C.c_double * 2)(*origin), (C.c_double * 2)(*cell)
+        org_c, cell_c = self._placed[key]
+        self._field(ev, t_free, t_occ, out)
+        _lib.call("lipmpc_grid_frontier_path_batch", device=self.device_index, B=B, F=F, W=W, H=H, origin=C.addressof(org_c),
+                  cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ, field=out["field"], n_frontier=out["n_frontier"], start=start,
+                  r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
+                  **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell")),
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+        # the target's centre by the contract's expression (double, one multiply and one add per axis: torch does not contract)
+        tc = out["target_cell"]
+        i, j = torch.div(tc, H, rounding_mode="floor"), torch.remainder(tc, H)
+        xy = torch.stack([origin[0] + (i.double() + 0.5) * cell[0], origin[1] + (j.double() + 0.5) * cell[1]], 1)
+        out["target"].copy_(torch.where((tc >= 0)[:, None], xy, torch.full_like(xy, float("nan"))))
         self.last = out
         return out

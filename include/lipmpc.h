@@ -36,7 +36,9 @@ extern "C" {
                                 *    backward-compatible additions since: + lipmpc_set_warm_start / lipmpc_warm_words;
                                 *    + lipmpc_rrt_default_params / lipmpc_rrt_workspace_bytes / lipmpc_rrt_plan_batch;
                                 *    + lipmpc_neighbour_workspace_bytes / lipmpc_neighbour_c_eta_batch;
-                                *    + lipmpc_map_update_batch; + lipmpc_rrt_plan_grid_batch, LIPMPC_RRT_OUTSIDE_GRID */
+                                *    + lipmpc_map_update_batch; + lipmpc_rrt_plan_grid_batch, LIPMPC_RRT_OUTSIDE_GRID;
+                                *    + lipmpc_grid_field_batch / lipmpc_grid_path_batch;
+                                *    + lipmpc_grid_frontier_field_batch / lipmpc_grid_frontier_path_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -586,6 +588,68 @@ int lipmpc_grid_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t 
                            const uint8_t* occ, int32_t grid_shared, const uint32_t* field, const int32_t* field_status,
                            const double* goal, const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
                            double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, void* hip_stream);
+
+/* FRONTIER EXPLORER (backward-compatible addition): where to walk when nobody hands over a goal -- nearest-frontier exploration
+ * (Yamauchi 1997) on the evidence grid of lipmpc_map_update_batch.  A FRONTIER cell is a cell a robot can stand in that touches
+ * cells nobody has decided yet; lipmpc_grid_frontier_field_batch finds them and relaxes the cost-to-go to the NEAREST one, and
+ * lipmpc_grid_frontier_path_batch sends any number of robots down that field.  On a shared map one field serves every robot.
+ * Everything compared is an integer, as in the grid field planner.  Both calls: all pointers DEVICE pointers but origin / cell
+ * (HOST); asynchronous on hip_stream; no allocation and no host synchronisation, so they can be captured in a graph; every
+ * refusal is a return code decided on the host before anything is enqueued.
+ *
+ * lipmpc_grid_frontier_field_batch: F maps, one workgroup per map.
+ *  evidence   [F,W,H] int32, layout i * H + j, as lipmpc_map_update_batch leaves it (a shared map: F = 1)
+ *  t_free, t_occ  1..2^30 (a mapper's w_miss and w_hit);  r_inflate 0..16, in cells;  min_unknown 1..8
+ *  frontier   [F,W,H] uint8 or NULL;  field [F,W,H] uint32;  n_frontier [F] int32
+ * THE FIELD of one map, e = evidence[c]:
+ *  - solid(c) <=> e >= t_occ;  free(c) <=> e <= -t_free;  unknown(c) <=> neither.  Exact for every int32 value, INT32_MIN and
+ *    INT32_MAX included (two plain comparisons; with both thresholds >= 1 no cell is solid and free).
+ *  - blocked(i, j) <=> !free(i, j), or some solid cell (i', j') OF THE GRID has (i - i')^2 + (j - j')^2 <= r_inflate^2: the
+ *    inflation of lipmpc_grid_field_batch, applied to solid cells only.  Unknown cells are impassable but not inflated.
+ *  - frontier(c) <=> !blocked(c) and at least min_unknown of the cell's 8 neighbours INSIDE THE GRID are unknown.  Nothing
+ *    outside the grid counts: the grid's edge is no frontier.
+ *  - moves, the costs 5 / 7 and the no-corner-cut rule: lipmpc_grid_field_batch's, between unblocked cells.
+ *  - field[c] = the least total cost from c to ANY frontier cell: 0 on frontier cells, LIPMPC_FIELD_INF on blocked cells and on
+ *    cells from which no frontier can be reached.
+ *  - n_frontier[f] = the number of frontier cells.  With 0 the whole field is INF: nothing left to explore, not an error.
+ *  - frontier, if given: 1 on frontier cells, 0 elsewhere.
+ *  The least cost is unique for several sources as for one, so two calls give identical bits; n_frontier is an integer sum.
+ *  The field is kept in LDS, sized to the map, when 4 W H bytes beside three bitmaps (solid, unknown, blocked) fit the 160 KiB of
+ *  a workgroup: 4 (3 (2 ceil(W H / 64) + 2) + 2 + W H) + 256 <= 163840, up to about 37,300 cells; a larger map is relaxed in
+ *  `field`.
+ * LIPMPC_E_ARG: F < 0, W or H < 2, t_free or t_occ outside 1..2^30, r_inflate outside 0..16, min_unknown outside 1..8, a null
+ *  evidence / field / n_frontier (whatever F).  Then LIPMPC_E_UNSUPPORTED: W * H > 2^17, W > 4096 or H > 4096.  Then F = 0
+ *  enqueues nothing and returns 0. */
+int lipmpc_grid_frontier_field_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                     int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier, uint32_t* field,
+                                     int32_t* n_frontier, void* hip_stream);
+
+/* lipmpc_grid_frontier_path_batch: B robots, one lane per robot, each to the nearest frontier of its map.
+ *  F      1 or B: robot b uses map and field f = (F == 1 ? 0 : b)
+ *  W, H, evidence [F,W,H], t_occ, r_inflate: what the field call was given;  origin, cell: the grid's placement, as
+ *         lipmpc_grid_path_batch takes it;  field [F,W,H], n_frontier [F]: the field call's outputs;  start [B,2]
+ *  max_seg, S_max, sub_goals [B,S_max,2], n_sub [B], status [B] (LIPMPC_RRT_*), path_cost [B]: lipmpc_grid_path_batch's
+ *  target_cell [B] int32
+ * PER ROBOT this is lipmpc_grid_path_batch, passable(c) <=> field[c] != INF, with these differences and no others:
+ *  - status, the first that applies: the start cell (floor rule) is outside the grid (a NaN coordinate included) ->
+ *    LIPMPC_RRT_OUTSIDE_GRID; evidence[start cell] >= t_occ -> LIPMPC_RRT_START_OCCUPIED; n_frontier[f] == 0, or the snap finds
+ *    no finite cell -> LIPMPC_RRT_NO_PATH.
+ *  - the descent ends at the first cell c_L whose field is 0: a frontier cell.
+ *  - the LAST sub-goal is the CENTRE of c_L, (ox + (i + 0.5) * dx, oy + (j + 0.5) * dy) as written, no contraction.  A start
+ *    that is itself a frontier cell gives n_sub = 1, its own centre.
+ *  - target_cell[b] = the index i * H + j of c_L; -1 unless the status is FOUND or PATH_OVERFLOW.
+ *  The snap's window and key, the descent's order, the string pulling, max_seg, S_max, path_cost = field[start cell after the
+ *  snap] / 5.0 (NaN unless FOUND / PATH_OVERFLOW), n_sub = 0 unless FOUND and "rows from n_sub on untouched" are word for word
+ *  lipmpc_grid_path_batch's.
+ * Restated in numpy by tests/frontier_oracle.py (multi-source Dijkstra); the device's outputs equal it bit for bit.
+ * LIPMPC_E_ARG: B < 0, F neither 1 nor B, max_seg < 5, S_max < 1, t_occ outside 1..2^30, W or H < 2, a cell size that is not
+ *  positive and finite, an origin that is not finite, r_inflate outside 0..16, a null pointer.  LIPMPC_E_UNSUPPORTED as the field
+ *  call.  B = 0 enqueues nothing and returns 0. */
+int lipmpc_grid_frontier_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                    const double* cell, const int32_t* evidence, int32_t t_occ, const uint32_t* field,
+                                    const int32_t* n_frontier, const double* start, int32_t r_inflate, int32_t max_seg,
+                                    int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                    int32_t* target_cell, void* hip_stream);
 
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
