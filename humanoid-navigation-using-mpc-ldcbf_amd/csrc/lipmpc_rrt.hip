@@ -380,8 +380,26 @@ __device__ inline bool seg_free_lane(const uint32_t* bm, int H1, int ax, int ay,
   return true;
 }
 
+struct Red {                                               // reduction slots, two sets used alternately
+  uint64_t key[2][RRT_WAVES];
+  double c[2][RRT_WAVES];
+  int v[2][RRT_WAVES];
+};
+
+// OR over the workgroup through the reduction slots (__syncthreads_or would bring 256 bytes of static LDS of its own, which
+// the LDS limit of rrt_lds_bytes does not count)
+__device__ inline bool block_or(int x, Red* red, int& ph) {
+  const bool w_any = __ballot(x != 0) != 0;
+  if ((threadIdx.x & 63) == 0) red->v[ph][threadIdx.x >> 6] = w_any;
+  __syncthreads();
+  int r = red->v[ph][0];
+  for (int i = 1; i < RRT_WAVES; ++i) r |= red->v[ph][i];
+  ph ^= 1;
+  return r != 0;
+}
+
 // the same cells split over the workgroup (one segment, every lane a stride of its cells): true if free
-__device__ inline bool seg_free_block(const uint32_t* bm, int H1, int ax, int ay, int bx, int by) {
+__device__ inline bool seg_free_block(const uint32_t* bm, int H1, int ax, int ay, int bx, int by, Red* red, int& ph) {
   if (bx < ax || (bx == ax && by < ay)) {
     int t = ax; ax = bx; bx = t;
     t = ay; ay = by; by = t;
@@ -397,14 +415,8 @@ __device__ inline bool seg_free_block(const uint32_t* bm, int H1, int ax, int ay
       hit = occ_bit(bm, cx * H1 + cy);
     }
   }
-  return __syncthreads_or(hit) == 0;
+  return !block_or(hit, red, ph);
 }
-
-struct Red {                                               // reduction slots, two sets used alternately
-  uint64_t key[2][RRT_WAVES];
-  double c[2][RRT_WAVES];
-  int v[2][RRT_WAVES];
-};
 
 __device__ inline uint64_t block_min_u64(uint64_t x, Red* red, int& ph) {
   for (int o = 32; o >= 1; o >>= 1) {
@@ -508,7 +520,7 @@ __global__ void __launch_bounds__(RRT_THREADS) rrt_star_kernel(lipmpc_rrt_params
         k += l + 1;
         break;
       }
-      k += 64;
+      k = k + 64 < cap ? k + 64 : cap;                        // a window that straddles the cap holds cap - k draws
     }
     if (c < 0) break;
     ++samples;
@@ -522,7 +534,7 @@ __global__ void __launch_bounds__(RRT_THREADS) rrt_star_kernel(lipmpc_rrt_params
     key = block_min_u64(key, red, ph);
     const int vn = (int)(key & 0xffffffffu), dmin = (int)(key >> 32);
     if (dmin == 0) continue;
-    if (!seg_free_block(bm, H1, cell[vn] >> 16, cell[vn] & 0xffff, xi, xj)) continue;
+    if (!seg_free_block(bm, H1, cell[vn] >> 16, cell[vn] & 0xffff, xi, xj, red, ph)) continue;
     // parent: cheapest near vertex with a free segment; the cost test first, the segment only if it could win
     const double Cx = Cg[c];
     double bc = __builtin_inf();
@@ -549,7 +561,7 @@ __global__ void __launch_bounds__(RRT_THREADS) rrt_star_kernel(lipmpc_rrt_params
       if (nc < cost[u] && seg_free_lane(bm, H1, cell[u] >> 16, cell[u] & 0xffff, xi, xj)) { par[u] = xv; any = 1; }
     }
     nv += 1;
-    if (__syncthreads_or(any)) {
+    if (block_or(any, red, ph)) {
       // costs top-down through x's subtree, one level per pass: level L+1 = the vertices whose parent carries tag L
       for (;;) {
         int found = 0;
@@ -563,7 +575,7 @@ __global__ void __launch_bounds__(RRT_THREADS) rrt_star_kernel(lipmpc_rrt_params
           }
         }
         ++tag;
-        if (!__syncthreads_or(found)) break;
+        if (!block_or(found, red, ph)) break;
       }
     }
     ++tag;

@@ -44,7 +44,8 @@ def plan_grid(occ, origin, cell, goal, start=None, seed=1, n=R.N_SAMPLES, r_rewi
     start = (0.0, 0.0) if start is None else (float(start[0]), float(start[1]))
     tf = grid_transform(W, H, origin, cell)
     out = dict(status=None, sub_goals=np.zeros((0, 2)), n_sub=0, path_cost=float("nan"), tf=tf, og=None, d2=None, C=None,
-               cells=np.zeros((0, 2), np.int64), parent=np.zeros(0, np.int64), cost=np.zeros(0), goal_parent=-1, draws=0)
+               cells=np.zeros((0, 2), np.int64), parent=np.zeros(0, np.int64), cost=np.zeros(0), goal_parent=-1, draws=0,
+               samples=0)
     if W * H > max_cells or H > MAX_SIDE or W > MAX_SIDE:
         out["status"] = R.GRID_TOO_LARGE
         return out

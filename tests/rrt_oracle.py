@@ -166,13 +166,14 @@ def plan(rings, goal, start=None, seed=1, width=WIDTH, n=N_SAMPLES, r_rewire=R_R
          max_cells=MAX_CELLS, S_max=None, C=None):
     """One plan by the contract of lipmpc_rrt_plan_batch.  ``C``: the cost grid to plan on (default exp(-sqrt(d2)) in
     numpy).  Returns dict(status, sub_goals [n_sub,2], n_sub, path_cost, tf, og, d2, C, cells [V,2], parent [V],
-    cost [V], goal_parent, draws)."""
+    cost [V], goal_parent, draws, samples: the valid draws among them, 0 on the early statuses)."""
     start = (0.0, 0.0) if start is None else (float(start[0]), float(start[1]))
     rings = [np.asarray(r, float) for r in rings if len(r)]
     tf = transform(rings, goal, start, width, margin)
     W, H = tf["W"], tf["H"]
     out = dict(status=None, sub_goals=np.zeros((0, 2)), n_sub=0, path_cost=float("nan"), tf=tf, og=None, d2=None, C=None,
-               cells=np.zeros((0, 2), np.int64), parent=np.zeros(0, np.int64), cost=np.zeros(0), goal_parent=-1, draws=0)
+               cells=np.zeros((0, 2), np.int64), parent=np.zeros(0, np.int64), cost=np.zeros(0), goal_parent=-1, draws=0,
+               samples=0)
     ncells = (W + 1) * (H + 1)
     if ncells > max_cells or H + 1 > 4096:
         out["status"] = GRID_TOO_LARGE
@@ -254,7 +255,7 @@ def plan(rings, goal, start=None, seed=1, width=WIDTH, n=N_SAMPLES, r_rewire=R_R
                 cost[ch] = cost[p] + C[cells[ch, 0], cells[ch, 1]] * np.sqrt(e2.astype(np.float64))
                 front[:] = False
                 front[ch] = True
-    out.update(cells=cells[:nv].copy(), parent=parent[:nv].copy(), cost=cost[:nv].copy(), draws=k)
+    out.update(cells=cells[:nv].copy(), parent=parent[:nv].copy(), cost=cost[:nv].copy(), draws=k, samples=samples)
     # goal
     P = cells[:nv]
     dd = (P[:, 0] - gi) ** 2 + (P[:, 1] - gj) ** 2

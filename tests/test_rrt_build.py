@@ -36,7 +36,8 @@ def test_rrt_exports_and_defaults():
 
 def test_rrt_kernel_resource_report():
     """The five planner kernels compile without scratch (the tree kernel keeps tree and bitmap in LDS and every per-lane
-    walk in registers)."""
+    walk in registers), and the tree kernel without static LDS: the limit lipmpc_rrt_workspace_bytes accepts counts its dynamic
+    LDS alone, so any static byte would make the launch at that limit fail."""
     src = os.path.join(ROOT, "humanoid-navigation-using-mpc-ldcbf_amd", "csrc", "lipmpc_rrt.hip")
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-c", src,
                         "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=280)
@@ -50,4 +51,6 @@ def test_rrt_kernel_resource_report():
         found.add(name)
         scratch = int(re.search(r"ScratchSize[^:]*: (\d+)", b).group(1))
         assert scratch == 0, (name, scratch)
+        if name == "rrt_star_kernel":
+            assert int(re.search(r"LDS Size[^:]*: (\d+)", b).group(1)) == 0, b
     assert found == set(KERNELS), found

@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import lipmpc  # noqa: E402
 import rrt_oracle as R  # noqa: E402
+from rrt_checks import check_ring_plan  # noqa: E402
 from helpers import IPOPT_LIKE_TOL  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,24 +81,8 @@ def test_grid_and_distance_match_golden():
 
 
 def _check_against_oracle(res, b, prob, n, S_max, label):
-    W1, H1 = res["grid_dims"][b]
-    C = res["cost_grid"][b, : W1 * H1].reshape(W1, H1) if res["status"][b] not in (R.GRID_TOO_LARGE,
-                                                                                    R.NO_OBSTACLE_GRID) else None
-    o = R.plan(prob["rings"], prob["goal"], start=prob.get("start"), seed=prob["seed"], n=n, S_max=S_max, C=C)
-    assert res["status"][b] == o["status"], (label, R.STATUS_NAMES[res["status"][b]], R.STATUS_NAMES[o["status"]])
-    assert res["n_sub"][b] == o["n_sub"], label
-    t = res["tree"][b]
-    V = int(t[0, 0])
-    assert V == len(o["cells"]), (label, V, len(o["cells"]))
-    if V:
-        assert int(t[0, 1]) == o["goal_parent"], label
-        assert np.array_equal(t[1: V + 1, :2].astype(np.int64), o["cells"]), label
-        assert np.array_equal(t[1: V + 1, 2].astype(np.int64), o["parent"]), label
-        assert np.array_equal(t[1: V + 1, 3].view(np.int64), o["cost"].view(np.int64)), label
-    if o["status"] == R.FOUND:
-        assert np.array_equal(res["sub_goals"][b, : o["n_sub"]].view(np.int64), o["sub_goals"].view(np.int64)), label
-        assert res["path_cost"][b] == o["path_cost"], label
-    return o
+    """Problem b against the oracle on the device's C: everything tests/rrt_checks.py holds a plan to."""
+    return check_ring_plan(res, b, prob, label, S_max=S_max, n=n)
 
 
 def _random_problems(count, rng):

@@ -6,6 +6,7 @@ import pytest
 import grid_lidar_oracle as G
 import rrt_grid_oracle as RG
 import rrt_oracle as R
+from rrt_checks import check_grid_plan
 from test_rrt_grid_oracle import golden_scenes
 
 pytestmark = pytest.mark.gpu
@@ -22,30 +23,10 @@ def _np(out):
 
 
 def _check(res, b, occ, origin, cell, goal, start, seed, S_max=None, n=N, r_rewire=R_REWIRE, max_cells=MAX_CELLS, label=""):
-    """Problem b of a plan_grid_batch result against the oracle on the device's C: status, n_sub, vertex list, parents and costs
-    (bitwise), sub-goals and path cost (bitwise)."""
-    W, H = occ.shape
-    early = res["status"][b] in (R.GRID_TOO_LARGE, R.NO_OBSTACLE_GRID, RG.OUTSIDE_GRID)
-    C = None if early else res["cost_grid"][b, : W * H].reshape(W, H)
-    o = RG.plan_grid(occ, origin, cell, goal, start=start, seed=seed, n=n, r_rewire=r_rewire, max_cells=max_cells, S_max=S_max, C=C)
-    assert res["status"][b] == o["status"], (label, RG.STATUS_NAMES[res["status"][b]], RG.STATUS_NAMES[o["status"]])
-    assert tuple(res["grid_dims"][b]) == (W, H) and res["n_sub"][b] == o["n_sub"], label
-    t = res["tree"][b]
-    V = int(t[0, 0])
-    assert V == len(o["cells"]), (label, V, len(o["cells"]))
-    if V:
-        assert int(t[0, 1]) == o["goal_parent"], label
-        assert np.array_equal(t[1: V + 1, :2].astype(np.int64), o["cells"]), label
-        assert np.array_equal(t[1: V + 1, 2].astype(np.int64), o["parent"]), label
-        assert np.array_equal(t[1: V + 1, 3].view(np.int64), o["cost"].view(np.int64)), label
-    if o["d2"] is not None and not early:
-        assert np.array_equal(res["occ_d2"][b, : W * H].reshape(W, H), o["d2"]), label
-    if o["status"] == R.FOUND:
-        assert np.array_equal(res["sub_goals"][b, : o["n_sub"]].view(np.int64), o["sub_goals"].view(np.int64)), label
-        assert res["path_cost"][b] == o["path_cost"], label
-        gb = res["grid_bounds"][b]
-        assert (gb[0], gb[1], gb[2], gb[3]) == (o["tf"]["min_x"], o["tf"]["max_x"], o["tf"]["min_y"], o["tf"]["max_y"]), label
-    return o
+    """Problem b of a plan_grid_batch result against the oracle on the device's C: everything tests/rrt_checks.py holds a plan to
+    (status, n_sub, the tree bit for bit, draws and samples, d2, C, sub-goals, path cost, grid bounds, untouched cells)."""
+    return check_grid_plan(res, b, occ, origin, cell, dict(goal=goal, start=start, seed=seed), label, S_max=S_max, n=n,
+                           r_rewire=r_rewire, max_cells=max_cells)
 
 
 def test_gpu_plan_on_from_planner_grids_equals_the_ring_plan():
