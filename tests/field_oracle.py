@@ -19,6 +19,42 @@ NO_CAP = 0x7FFFFFFF                                           # max_seg = "no sp
 FIELD_OK, FIELD_GOAL_OUTSIDE, FIELD_GOAL_BLOCKED = 0, 1, 2
 FOUND, NO_PATH, START_OCCUPIED, GOAL_OCCUPIED, PATH_OVERFLOW, OUTSIDE_GRID = 0, 1, 2, 3, 6, 7      # the LIPMPC_RRT_* codes in use
 MOVES = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))                      # the descent's order
+LDS_LIMIT, LDS_SLACK = 160 * 1024, 256
+MAX_SIDE, MAX_CELLS = 4096, 1 << 17                           # the caps of every grid call
+
+
+def bitmap_words(ncells):
+    """32-bit words of a bitmap of ncells cells: whole 64-cell ballots, + 2 for a window that starts in the last word."""
+    return ((ncells + 63) // 64) * 2 + 2
+
+
+def field_lds_bytes(ncells):
+    """Dynamic LDS the field kernel asks for with the field in LDS: the blocked bitmap, then the field (the solid bitmap borrows
+    the field's first words)."""
+    return 4 * (bitmap_words(ncells) + ncells)
+
+
+def field_fits_lds(ncells):
+    """THE FIELD KERNEL'S LDS RULE (its own, not the frontier kernel's): the field, 4 bytes a cell, beside the blocked bitmap and
+    the workgroup reduction's slack within the 160 KiB of a workgroup."""
+    return field_lds_bytes(ncells) + LDS_SLACK <= LDS_LIMIT
+
+
+def shapes_of(ncells):
+    """Every (W, H) of exactly ncells cells that the grid calls accept: both sides in 2..4096."""
+    return [(w, ncells // w) for w in range(2, MAX_SIDE + 1) if ncells % w == 0 and 2 <= ncells // w <= MAX_SIDE]
+
+
+def lds_boundary(fits):
+    """(the largest cell count that ``fits`` and its shapes, the first count above it that has a shape at all and its shapes)."""
+    n = 4
+    while fits(n + 1):
+        n += 1
+    over = n + 1
+    while not shapes_of(over):
+        over += 1
+    assert fits(n) and not fits(over) and over <= MAX_CELLS
+    return (n, shapes_of(n)), (over, shapes_of(over))
 
 
 def blocked_cells(occ, r_inflate):
@@ -118,9 +154,10 @@ def snap(fld, c, r_inflate):
     return None if best is None else best[1]
 
 
-def descend(fld, c):
+def descend(fld, c, strict=True):
     """The path cells from c to the cell whose field is 0: each time the first neighbour in MOVES order with
-    field[n] + cost == field[c], side cells of a diagonal judged by ``passable``."""
+    field[n] + cost == field[c], side cells of a diagonal judged by ``passable``.  Where no neighbour satisfies that -- ``fld`` is
+    no cost-to-go field -- AssertionError, or None with ``strict=False`` (the contract's LIPMPC_RRT_NO_PATH)."""
     W, H = fld.shape
     path = [c]
     while fld[c] != 0:
@@ -135,6 +172,8 @@ def descend(fld, c):
                 c = (a, b)
                 break
         else:
+            if not strict:
+                return None
             raise AssertionError(f"no descent from {c}: not a cost-to-go field")
         path.append(c)
     return path
@@ -155,9 +194,11 @@ def string_pull(fld, path, max_seg):
     return out
 
 
-def plan(occ, origin, cell, goal, start, r_inflate=0, max_seg=None, S_max=64, fld=None, field_status=None):
+def plan(occ, origin, cell, goal, start, r_inflate=0, max_seg=None, S_max=64, fld=None, field_status=None, strict=True):
     """One robot by the contract of lipmpc_grid_path_batch.  ``fld`` / ``field_status``: the field of ``goal`` when the caller
-    has it (shared by many starts).  Returns dict(status, n_sub, sub_goals [n_sub,2], path_cost, cells (the descent), snapped)."""
+    has it (shared by many starts) -- or any field at all with ``strict=False``, where a descent that finds no neighbour ends
+    NO_PATH as the contract says instead of raising.  Returns dict(status, n_sub, sub_goals [n_sub,2], path_cost, cells (the
+    descent), snapped)."""
     solid = np.asarray(occ) != 0
     W, H = solid.shape
     if fld is None:
@@ -179,7 +220,10 @@ def plan(occ, origin, cell, goal, start, r_inflate=0, max_seg=None, S_max=64, fl
     if s is None:
         out["status"] = NO_PATH
         return out
-    path = descend(fld, s)
+    path = descend(fld, s, strict)
+    if path is None:
+        out.update(status=NO_PATH, snapped=s)
+        return out
     pulled = string_pull(fld, path, max_seg)
     out.update(cells=path, snapped=s, path_cost=float(np.float64(int(fld[s])) / 5.0))
     if len(pulled) + 1 > S_max:

@@ -17,18 +17,18 @@ import field_oracle as FO
 INF, NO_CAP = FO.INF, FO.NO_CAP
 FOUND, NO_PATH, START_OCCUPIED, PATH_OVERFLOW, OUTSIDE_GRID = FO.FOUND, FO.NO_PATH, FO.START_OCCUPIED, FO.PATH_OVERFLOW, FO.OUTSIDE_GRID
 THRESHOLD_MAX = 1 << 30
-LDS_LIMIT, LDS_SLACK = 160 * 1024, 256
+LDS_LIMIT, LDS_SLACK, bitmap_words = FO.LDS_LIMIT, FO.LDS_SLACK, FO.bitmap_words
 
 
-def bitmap_words(ncells):
-    """32-bit words of a bitmap of ncells cells: whole 64-cell ballots, + 2 for a window that starts in the last word."""
-    return ((ncells + 63) // 64) * 2 + 2
+def field_lds_bytes(ncells):
+    """Dynamic LDS the frontier kernel asks for with the field in LDS: three bitmaps, the frontier count's word pair, the field."""
+    return 4 * (3 * bitmap_words(ncells) + 2 + ncells)
 
 
 def field_fits_lds(ncells):
     """THE FRONTIER KERNEL'S LDS RULE (its own, not the grid field planner's): the field, 4 bytes a cell, beside three bitmaps
     (blocked, solid, unknown), the frontier count's word pair and the reduction's slack within the 160 KiB of a workgroup."""
-    return 4 * (3 * bitmap_words(ncells) + 2 + ncells) + LDS_SLACK <= LDS_LIMIT
+    return field_lds_bytes(ncells) + LDS_SLACK <= LDS_LIMIT
 
 
 def sizes_at_the_lds_switch(H=193):
@@ -82,9 +82,10 @@ def field(evidence, t_free, t_occ, r_inflate=2, min_unknown=2):
     return out, frontier.astype(np.uint8), int(frontier.sum())
 
 
-def plan(evidence, t_occ, fld, n_frontier, origin, cell, start, r_inflate=2, max_seg=None, S_max=64):
-    """One robot by the contract of lipmpc_grid_frontier_path_batch.  Returns dict(status, n_sub, sub_goals [n_sub,2], path_cost,
-    target_cell, cells (the descent), snapped)."""
+def plan(evidence, t_occ, fld, n_frontier, origin, cell, start, r_inflate=2, max_seg=None, S_max=64, strict=True):
+    """One robot by the contract of lipmpc_grid_frontier_path_batch.  ``strict=False``: ``fld`` may be any field, and a descent
+    that finds no neighbour ends NO_PATH as the contract says instead of raising.  Returns dict(status, n_sub, sub_goals
+    [n_sub,2], path_cost, target_cell, cells (the descent), snapped)."""
     ev = np.asarray(evidence)
     W, H = ev.shape
     max_seg = NO_CAP if max_seg is None else int(max_seg)
@@ -102,7 +103,10 @@ def plan(evidence, t_occ, fld, n_frontier, origin, cell, start, r_inflate=2, max
     if s is None:
         out["status"] = NO_PATH
         return out
-    path = FO.descend(fld, s)                                 # ends at the first cell whose field is 0
+    path = FO.descend(fld, s, strict)                         # ends at the first cell whose field is 0
+    if path is None:
+        out.update(status=NO_PATH, snapped=s)
+        return out
     pulled = FO.string_pull(fld, path, max_seg)
     last = path[-1]
     out.update(cells=path, snapped=s, path_cost=float(np.float64(int(fld[s])) / 5.0), target_cell=last[0] * H + last[1])

@@ -12,60 +12,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import lipmpc  # noqa: E402
 
-SENTINEL = -7.25
-ORIGIN, CELL = (-0.35, 0.2), (0.1, 0.125)                     # (anisotropic cells: the metric counts cells)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int64) if a.dtype == np.float64 else a
-
-
-def _buffers(B, F, W, H, S_max):
-    table = lipmpc.planner.field_plan_outputs(B, F, W, H, S_max)
-    out = {k: torch.empty(shape, dtype=dt, device="cuda") for k, (dt, shape, _) in table.items()}
-    out["sub_goals"].fill_(SENTINEL)
-    return out
-
-
-def _host(out):
-    h = {k: v.cpu().numpy() for k, v in out.items() if k != "field"}
-    h["field"] = out["field"].view(torch.int32).cpu().numpy().view(np.uint32)
-    return h
-
-
-def _run(occ, origin, cell, goal, start, r=0, max_seg=None, S_max=64):
-    occ, goal, start = np.asarray(occ, np.uint8), np.asarray(goal, np.float64).reshape(-1, 2), np.asarray(start, np.float64).reshape(-1, 2)
-    W, H = occ.shape[-2:]
-    out = _buffers(len(start), len(goal), W, H, S_max)
-    pl = lipmpc.GridFieldPlanner(r_inflate=r, max_seg=max_seg)
-    got = pl.plan_grid_batch(torch.as_tensor(goal, device="cuda"), lipmpc.GridMap(occ, origin, cell), torch.as_tensor(start, device="cuda"),
-                             S_max=S_max, out=out)
-    torch.cuda.synchronize()
-    assert got is out and pl.last is out
-    return _host(out)
-
-
-def _same(got, want, S_max):
-    """Every output of the device equals the oracle's, bit for bit; sub-goal rows from n_sub on still hold the sentinel."""
-    assert np.array_equal(got["field_status"], want["field_status"]), (got["field_status"], want["field_status"])
-    assert np.array_equal(got["field"], want["field"]), int((got["field"] != want["field"]).sum())
-    assert np.array_equal(got["status"], want["status"]), np.nonzero(got["status"] != want["status"])[0][:8]
-    assert np.array_equal(got["n_sub"], want["n_sub"]), np.nonzero(got["n_sub"] != want["n_sub"])[0][:8]
-    assert np.array_equal(_bits(got["path_cost"]), _bits(want["path_cost"]))           # (one NaN pattern: __builtin_nan = numpy's)
-    for b, sub in enumerate(want["sub_goals"]):
-        n = len(sub)
-        assert np.array_equal(_bits(got["sub_goals"][b, :n]), _bits(sub)), b
-        assert (got["sub_goals"][b, n:] == SENTINEL).all(), b
-    assert got["sub_goals"].shape[1] == S_max
-
-
-def _check(occ, origin, cell, goal, start, r=0, max_seg=None, S_max=64):
-    want = Fo.plan_batch(occ, origin, cell, np.asarray(goal, np.float64).reshape(-1, 2), np.asarray(start, np.float64).reshape(-1, 2),
-                         r, max_seg, S_max)
-    got = _run(occ, origin, cell, goal, start, r, max_seg, S_max)
-    _same(got, want, S_max)
-    return got, want
+from grid_checks import CELL, ORIGIN, SENTINEL, bits as _bits, check_field as _check, field_buffers as _buffers, host as _host, \
+    run_field as _run  # noqa: E402  (the helpers this file shares with the other grid planner tests)
 
 
 def _points(rng, W, H, n, origin=ORIGIN, cell=CELL, margin=0.0):

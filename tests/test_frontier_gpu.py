@@ -16,68 +16,10 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import lipmpc  # noqa: E402
 
-SENTINEL = -7.25
-ORIGIN, CELL = (-0.35, 0.2), (0.1, 0.125)                     # (anisotropic cells: the metric counts cells)
-T_FREE, T_OCC = 1, 3                                          # a mapper's default weights
+from grid_checks import CELL, ORIGIN, SENTINEL, T_FREE, T_OCC, bits as _bits, check_frontier as _check, frontier_buffers as _buffers, \
+    frontier_planner as _planner, host as _host, run_frontier as _run  # noqa: E402  (shared with the other grid planner tests)
+
 I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int64) if a.dtype == np.float64 else a
-
-
-def _buffers(B, F, W, H, S_max):
-    table = lipmpc.planner.frontier_outputs(B, F, W, H, S_max)
-    out = {k: torch.empty(shape, dtype=dt, device="cuda") for k, (dt, shape, _) in table.items()}
-    out["sub_goals"].fill_(SENTINEL)
-    return out
-
-
-def _host(out):
-    h = {k: v.cpu().numpy() for k, v in out.items() if k != "field"}
-    h["field"] = out["field"].view(torch.int32).cpu().numpy().view(np.uint32)
-    return h
-
-
-def _planner(r, mu, max_seg, t=(T_FREE, T_OCC)):
-    return lipmpc.FrontierPlanner(r_inflate=r, min_unknown=mu, t_free=t[0], t_occ=t[1], max_seg=max_seg)
-
-
-def _run(ev, start, r=2, mu=2, max_seg=None, S_max=64, t=(T_FREE, T_OCC), origin=ORIGIN, cell=CELL):
-    ev, start = np.ascontiguousarray(ev, np.int32), np.ascontiguousarray(np.asarray(start, np.float64).reshape(-1, 2))     # (a reversed view has negative strides)
-    W, H = ev.shape[-2:]
-    out = _buffers(len(start), 1 if ev.ndim == 2 else len(ev), W, H, S_max)
-    pl = _planner(r, mu, max_seg, t)
-    got = pl.plan(torch.as_tensor(ev, device="cuda"), torch.as_tensor(start, device="cuda"), origin=origin, cell=cell, S_max=S_max, out=out)
-    torch.cuda.synchronize()
-    assert got is out and pl.last is out
-    return _host(out)
-
-
-def _same(got, want, S_max):
-    """Every output of the device equals the oracle's, bit for bit; sub-goal rows from n_sub on still hold the sentinel."""
-    assert np.array_equal(got["n_frontier"], want["n_frontier"]), (got["n_frontier"], want["n_frontier"])
-    assert np.array_equal(got["frontier"], want["frontier"]), int((got["frontier"] != want["frontier"]).sum())
-    assert np.array_equal(got["field"], want["field"]), int((got["field"] != want["field"]).sum())
-    assert np.array_equal(got["status"], want["status"]), np.nonzero(got["status"] != want["status"])[0][:8]
-    assert np.array_equal(got["n_sub"], want["n_sub"]), np.nonzero(got["n_sub"] != want["n_sub"])[0][:8]
-    assert np.array_equal(got["target_cell"], want["target_cell"]), np.nonzero(got["target_cell"] != want["target_cell"])[0][:8]
-    assert np.array_equal(_bits(got["path_cost"]), _bits(want["path_cost"]))           # (one NaN pattern: __builtin_nan = numpy's)
-    found = want["target_cell"] >= 0
-    assert np.array_equal(_bits(got["target"][found]), _bits(want["target"][found])) and np.isnan(got["target"][~found]).all()
-    for b, sub in enumerate(want["sub_goals"]):
-        n = len(sub)
-        assert np.array_equal(_bits(got["sub_goals"][b, :n]), _bits(sub)), b
-        assert (got["sub_goals"][b, n:] == SENTINEL).all(), b
-    assert got["sub_goals"].shape[1] == S_max
-
-
-def _check(ev, start, r=2, mu=2, max_seg=None, S_max=64, t=(T_FREE, T_OCC), origin=ORIGIN, cell=CELL):
-    want = FR.plan_batch(ev, t[0], t[1], origin, cell, np.asarray(start, np.float64).reshape(-1, 2), r, mu, max_seg, S_max)
-    got = _run(ev, start, r, mu, max_seg, S_max, t, origin, cell)
-    _same(got, want, S_max)
-    return got, want
 
 
 def _points(rng, W, H, n, origin=ORIGIN, cell=CELL, margin=0.0):

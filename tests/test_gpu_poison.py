@@ -163,3 +163,255 @@ def test_lidar_kernel_is_independent_of_leftover_state(golden_dir):
             for j in range(int(o["n_inferred"][b])):
                 nv = int(o["obs_nv"][b, j])
                 assert np.array_equal(o["obs_xy"][b, j, :nv], outs[0]["obs_xy"][b, j, :nv])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The kernel families added since: grid field and path, frontier field and path, the map update, the grid scan, the neighbour
+# rows and the RRT* planner on a given grid.  Each runs under the three patterns on outputs filled with 0xA5 bytes (and, where
+# it has one, on a workspace filled with the pattern's own bytes: every workspace contract says "contents arbitrary on entry",
+# and fresh device memory is usually zero).  The outputs are bit-identical across the patterns and equal the oracle's.
+# ---------------------------------------------------------------------------------------------------------------------------
+A5 = float(np.frombuffer(b"\xa5" * 8, np.float64)[0])            # the double that 0xA5 bytes spell (finite, negative)
+
+
+def _fill_a5(out):
+    for t in out.values():
+        t.view(torch.uint8).fill_(0xA5)
+    return out
+
+
+def _fill_pattern(ws, pat):
+    """Every 32-bit word of a byte workspace = the pattern."""
+    n = ws.numel() // 4 * 4
+    ws[:n].view(torch.int32).fill_(pat - (1 << 32) if pat >> 31 else pat)
+    ws[n:].fill_(pat & 0xff)
+
+
+def _np(out):
+    return {k: (v.view(torch.int32) if v.dtype == torch.uint32 else v).cpu().numpy() for k, v in out.items()}
+
+
+def _under_patterns(run):
+    """[run(pattern, poison) -> dict of numpy outputs, after poisoning registers and LDS with each pattern]: bit-identical
+    throughout.  ``poison()``: the same poisoning again, for a run of more than one call."""
+    pz, outs = _poison_lib(), []
+    for pat in PATTERNS:
+        def poison(pat=pat):
+            torch.cuda.synchronize()
+            assert pz.lipmpc_poison(pat, 15) == 0
+        poison()
+        o = run(pat, poison)
+        torch.cuda.synchronize()
+        outs.append(_np(o))
+    for pat, o in zip(PATTERNS[1:], outs[1:]):
+        assert o.keys() == outs[0].keys()
+        for k in o:
+            assert np.array_equal(np.ascontiguousarray(o[k]).view(np.uint8), np.ascontiguousarray(outs[0][k]).view(np.uint8)), (hex(pat), k)
+    return outs[0]
+
+
+def _as_oracle_sees_it(got):
+    """The outputs of a planner run on 0xA5-filled buffers in the form tests/grid_checks.py compares: the field's words unsigned,
+    the rows behind n_sub -- still 0xA5 bytes -- as its sentinel."""
+    import grid_checks as K
+    got = dict(got, field=got["field"].view(np.uint32), sub_goals=got["sub_goals"].copy())
+    untouched = got["sub_goals"].view(np.uint8).reshape(*got["sub_goals"].shape, 8) == 0xA5
+    got["sub_goals"][untouched.all(-1)] = K.SENTINEL
+    return got
+
+
+@pytest.mark.parametrize("form", ["lds", "global"])
+def test_grid_field_and_path_are_independent_of_leftover_state(form):
+    """The 48 x 36 fleet case (field in LDS, 130 robots) and 35 x 1133, the first shape relaxed in global memory."""
+    import field_shape_cases as S
+    import grid_checks as K
+    if form == "lds":
+        occ, goal, start = S.field_fleet_case()
+        r, max_seg, S_max, want = 2, None, 64, None
+    else:
+        c = {c["id"]: c for c in S.all_cases()}["35x1133"]
+        occ, goal, start, r, max_seg, S_max, want = c["occ"], c["goal"], c["start"], c["r"], c["max_seg"], c["S_max"], S.oracle("35x1133", "field")
+    W, H = occ.shape
+    assert K.Fo.field_fits_lds(W * H) == (form == "lds")
+    want = K.Fo.plan_batch(occ, K.ORIGIN, K.CELL, goal, start, r, max_seg, S_max) if want is None else want
+    pl, grid = lipmpc.GridFieldPlanner(r_inflate=r, max_seg=max_seg), lipmpc.GridMap(occ, K.ORIGIN, K.CELL).to("cuda")
+    d_goal, d_start = _dev(goal, torch.float64), _dev(start, torch.float64)
+    got = _under_patterns(lambda pat, poison: pl.plan_grid_batch(d_goal, grid, d_start, S_max=S_max, out=_fill_a5(K.field_buffers(len(start), 1, W, H, S_max))))
+    K.same_field(_as_oracle_sees_it(got), want, S_max)
+
+
+@pytest.mark.parametrize("form", ["lds", "global"])
+def test_frontier_field_and_path_are_independent_of_leftover_state(form):
+    """The 48 x 36 fleet case (field in LDS) and 60 x 623, the first shape the frontier kernel relaxes in global memory."""
+    import field_shape_cases as S
+    import grid_checks as K
+    if form == "lds":
+        (ev, start), r, max_seg, S_max, want = S.frontier_fleet_case(), 2, None, 64, None
+    else:
+        c = {c["id"]: c for c in S.all_cases()}["60x623"]
+        ev, start, r, max_seg, S_max, want = c["ev"], c["start"], c["r"], c["max_seg"], c["S_max"], S.oracle("60x623", "frontier")
+    W, H = ev.shape
+    assert K.FR.field_fits_lds(W * H) == (form == "lds")
+    want = K.FR.plan_batch(ev, K.T_FREE, K.T_OCC, K.ORIGIN, K.CELL, start, r, S.MU, max_seg, S_max) if want is None else want
+    pl = K.frontier_planner(r, S.MU, max_seg)
+    d_ev, d_start = _dev(ev, torch.int32), _dev(start, torch.float64)
+    got = _under_patterns(lambda pat, poison: pl.plan(d_ev, d_start, origin=K.ORIGIN, cell=K.CELL, S_max=S_max,
+                                              out=_fill_a5(K.frontier_buffers(len(start), 1, W, H, S_max))))
+    K.same_frontier(_as_oracle_sees_it(got), want, S_max)
+
+
+def _fixture_scan(n_robots=8):
+    """The cell-aligned fixture of the grid tests with 8 robots: (fixture, sensor, state, noise)."""
+    import grid_lidar_oracle as G
+    fx = G.fixture(n_robots=n_robots)
+    st = np.zeros((n_robots, 5)); st[:, 0] = fx["pos"][:, 0]; st[:, 2] = fx["pos"][:, 1]
+    noise = 0.01 * np.random.default_rng(3).standard_normal((n_robots, 360, 2))
+    sensor = lipmpc.LidarSensor.from_grid(lipmpc.GridMap(fx["occ"], fx["origin"], fx["cell"]), lidar_range=1.5, n_obs_max=24, v_max=64)
+    return fx, sensor, _dev(st, torch.float64), noise
+
+
+def test_grid_scan_is_independent_of_leftover_state():
+    """LidarSensor.from_grid(...).sense with the debug outputs, and with the hulls kept inside the kernel (the fused c_eta)."""
+    import lidar_oracle as L
+    from lidar_grid_checks import check_chain, check_hits
+    fx, sensor, st, noise = _fixture_scan()
+    d_noise, B = _dev(noise, torch.float64), len(fx["pos"])
+
+    def run(pat, poison):
+        o = sensor.sense(st, d_noise, out=_fill_a5(sensor.alloc_outputs(B, with_debug=True, c_eta=True)))
+        poison()
+        oc = sensor.sense(st, d_noise, out=_fill_a5(sensor.alloc_outputs(B, rings=False, c_eta=True)))
+        return {**o, **{k + "_fused": v for k, v in oc.items()}}
+
+    g = _under_patterns(run)
+    n_hits, n_solid = check_hits(g, fx["pos"], lambda b: fx["occ"], fx["origin"], fx["cell"], 1.5, L.ray_table(360), noise)
+    assert n_hits > 20 * B and check_chain(g, fx["pos"]) > 0
+    for k in ("n_inferred", "overflow"):
+        assert np.array_equal(g[k + "_fused"], g[k]), k
+    # the fused form's half-spaces against the same oracle chain (the hulls it never wrote out are the unfused run's)
+    assert check_chain(dict(g, c_eta=g["c_eta_fused"]), fx["pos"]) > 0
+
+
+@pytest.mark.parametrize("per_robot", [True, False])
+def test_map_update_is_independent_of_leftover_state(per_robot):
+    """lipmpc_map_update_batch from zero evidence (the evidence is the call's input too: it is not filled), per-robot and shared."""
+    import lidar_oracle as L
+    import map_oracle as M
+    fx, sensor, st, noise = _fixture_scan()
+    B, (W, H), origin = len(fx["pos"]), (96, 80), (1.013, 0.77)
+    hits = sensor.sense(st, _dev(noise, torch.float64), with_debug=True, c_eta=True)["hits"]
+    mapper = lipmpc.OccupancyMapper(W, H, origin, fx["cell"], 1.5, per_robot=B if per_robot else None)
+
+    def run(pat, poison):
+        mapper.reset()
+        return {"evidence": mapper.update(st, hits)}
+
+    got = _under_patterns(run)["evidence"]
+    want = M.update(np.zeros((B, W, H), np.int64), fx["pos"], hits.cpu().numpy(), origin, mapper.cell, 1.5, L.ray_table(360),
+                    depth=mapper.depth, w_hit=mapper.w_hit, w_miss=mapper.w_miss, mask=None)
+    assert np.array_equal(got, want if per_robot else want.sum(0)) and (want != 0).any(axis=(1, 2)).sum() >= 3
+
+
+def _robots(B, seed):
+    rng = np.random.default_rng(seed)
+    st = np.zeros((B, 5)); st[:, 0], st[:, 2] = rng.uniform(0, 6 * (B / 257) ** 0.5, B), rng.uniform(0, 6 * (B / 257) ** 0.5, B)
+    return st, rng.integers(0, 3, B).astype(np.int32), rng.uniform(0.05, 0.3, B)
+
+
+def _neighbour_call(nb, st, first, n_obs_max, pat=None):
+    """One append on outputs and a c_eta of 0xA5 bytes, the workspace (when ``pat`` is given) filled with the pattern."""
+    B = len(st)
+    if pat is not None:
+        _fill_pattern(nb._workspace(B), pat)
+    ce = torch.full((B, n_obs_max, 4), A5, dtype=torch.float64, device="cuda")
+    out = nb.append(_dev(st, torch.float64), ce, _dev(first, torch.int32), None, out=_fill_a5(nb.alloc_outputs(B)))
+    return {**out, "c_eta": ce}
+
+
+@pytest.mark.parametrize("k_rows", [4, 16])
+def test_neighbour_rows_are_independent_of_leftover_state_and_of_their_workspace(k_rows):
+    import neighbour_oracle as NO
+    from neighbour_checks import assert_equals_oracle
+    B, n_obs_max = 257, 6 if k_rows == 4 else 20
+    st, first, radius = _robots(B, 257)
+    nb = lipmpc.NeighbourRows(_dev(radius, torch.float64), 1.0, k_rows, 0.5)
+    got = _under_patterns(lambda pat, poison: _neighbour_call(nb, st, first, n_obs_max, pat))
+    ref = NO.neighbour_rows(st, radius, 1.0, k_rows, n_obs_max, 0.5, None, first, c_eta=np.full((B, n_obs_max, 4), A5))
+    assert_equals_oracle(got, ref, f"k_rows={k_rows}")
+    assert got["n_near"].max() > 4 and (got["n_rows"] > 0).sum() > B // 2
+
+
+def _rrt_case():
+    import rrt_size_cases as Z
+    case = Z.replay_case()
+    probs = case["problems"]
+    return case, np.array([q["goal"] for q in probs], float), np.array([q["start"] for q in probs], float), [q["seed"] for q in probs]
+
+
+def test_rrt_planner_on_a_grid_is_independent_of_leftover_state_and_of_its_workspace():
+    """The B = 4 plan of the RRT* size tests on its 40 x 30 map: lipmpc_rrt_plan_grid_batch itself on outputs of 0xA5 bytes and a
+    workspace of the pattern.  The header leaves the rows a plan does not own untouched (sub_goals: "rows 0..n_sub[b]-1 written
+    (FOUND only), the rest untouched"; tree, occ_d2, cost_grid: the plan's own rows and cells), so against the oracle stands the
+    wrapper's plan on zeroed outputs, and the call on 0xA5 bytes must equal it in every element it wrote and have written no other.
+    THE LIMIT OF THAT: an element counts as untouched when all its bytes are still 0xA5, and an untouched element passes wherever the
+    zeroed run holds 0 -- so an element the kernel should write with a non-zero value and skips is caught, one whose right value is 0
+    is not told from one never written.  A tripwire for leftover state, not a proof of the write set.  (The call is made as the
+    wrapper makes it, through the planner's own workspace, seeds and grid arguments: plan_grid_batch takes no ``out=``.)"""
+    import rrt_oracle as R
+    from rrt_checks import check_grid_plan
+    case, goal, start, seeds = _rrt_case()
+    p, B = case["params"], len(goal)
+    planner = lipmpc.RrtStarPlanner(n=p["n"], r_rewire=p["r_rewire"], max_cells=p["max_cells"])
+    grid = lipmpc.GridMap(case["occ"], case["origin"], case["cell"]).to(planner.device)
+    want = _np(planner.plan_grid_batch(goal, grid, start, seeds=seeds, with_tree=True, with_grids=True))
+    for b, q in enumerate(case["problems"]):
+        check_grid_plan(want, b, case["occ"], case["origin"], case["cell"], q, ("zeroed", b), **p)
+    assert (want["status"] == R.FOUND).sum() >= 3
+    table = lipmpc.planner.plan_outputs(B, p["n"] + 1, p["max_cells"], p["n"])
+    d_goal, d_start, d_seeds = _dev(goal, torch.float64), _dev(start, torch.float64), planner._seeds(seeds, B)
+
+    def run(pat, poison):
+        out = _fill_a5({k: torch.empty(shape, dtype=dt, device=planner.device) for k, (dt, shape, _) in table.items()})
+        ws = planner._workspace(B)
+        _fill_pattern(ws, pat)
+        lipmpc._lib.call("lipmpc_rrt_plan_grid_batch", device=planner.device_index, p=C.byref(planner.params), B=B,
+                         **grid._args(B, planner.device), start=d_start, goal=d_goal, seed=d_seeds, workspace=ws, **out, S_max=p["n"] + 1,
+                         hip_stream=torch.cuda.current_stream(planner.device).cuda_stream)
+        return out
+
+    got = _under_patterns(run)
+    for k in table:
+        g, w = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        untouched = (g.view(np.uint8).reshape(*g.shape, g.itemsize) == 0xA5).all(-1)
+        assert np.array_equal(g[~untouched].view(np.uint8), w[~untouched].view(np.uint8)), k      # what it wrote: the checked plan's
+        assert not w[untouched].view(np.uint8).any(), k                                              # ... and it wrote nothing else
+
+
+def test_planner_and_neighbour_objects_reused_on_a_smaller_problem():
+    """One RrtStarPlanner and one NeighbourRows, each called on a large problem and then on a small one -- the small one runs in
+    the front of a workspace the large one has written all over -- give the small problem the bits a fresh object gives it."""
+    case, goal, start, seeds = _rrt_case()
+    p = case["params"]
+    grid = lipmpc.GridMap(case["occ"], case["origin"], case["cell"])
+    occ = np.ascontiguousarray(case["occ"][:17, :13])
+    occ[15, 11] = 0
+    small = lipmpc.GridMap(occ, case["origin"], case["cell"])
+    s_goal, s_start = np.array([[15.5, 11.5]]), np.array([[0.5, 0.5]])       # (unit cells at (0, 0): the centres of (15, 11) and (0, 0))
+    plan = lambda pl, *a: _np(pl.plan_grid_batch(*a, with_tree=True, with_grids=True))
+    new = lambda: lipmpc.RrtStarPlanner(n=p["n"], r_rewire=p["r_rewire"], max_cells=p["max_cells"])
+    used = new()
+    plan(used, goal, grid, start, seeds)
+    again, fresh = plan(used, s_goal, small, s_start, [11]), plan(new(), s_goal, small, s_start, [11])
+    torch.cuda.synchronize()
+    assert fresh["status"][0] == 0 and fresh["tree"][0, 0, 0] > 20             # FOUND, on a tree of some size
+    for k in fresh:
+        assert np.array_equal(again[k].view(np.uint8), fresh[k].view(np.uint8)), k
+
+    (st, first, _), (s_st, s_first, _) = _robots(257, 257), _robots(9, 9)         # (one radius for all here: 0.2)
+    used = lipmpc.NeighbourRows(0.2, 1.0, 4, 0.5)
+    _neighbour_call(used, st, first, 6)
+    again = _np(_neighbour_call(used, s_st, s_first, 6))
+    fresh = _np(_neighbour_call(lipmpc.NeighbourRows(0.2, 1.0, 4, 0.5), s_st, s_first, 6))
+    assert again["n_near"].max() >= 1
+    for k in fresh:
+        assert np.array_equal(again[k].view(np.uint8), fresh[k].view(np.uint8)), k

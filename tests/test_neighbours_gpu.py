@@ -15,6 +15,7 @@ import lipmpc  # noqa: E402
 import lipmpc_oracle as O  # noqa: E402
 import neighbour_oracle as NO  # noqa: E402
 from helpers import raw_call  # noqa: E402
+from neighbour_checks import assert_equals_oracle as _assert_equals_oracle, bits_equal as _bits_equal  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SENTINEL = -7.25
@@ -31,21 +32,6 @@ def _states(x, y):
     st[:, 0], st[:, 2] = x, y
     st[:, 1], st[:, 3], st[:, 4] = 0.3, -0.2, 0.7            # never read
     return st
-
-
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
-    nan = np.isnan(a)
-    return a.shape == b.shape and np.array_equal(nan, np.isnan(b)) and np.array_equal(a.view(np.int64)[~nan], b.view(np.int64)[~nan])
-
-
-def _assert_equals_oracle(got, ref, what=""):
-    for k in ("n_near", "n_rows", "neighbours"):
-        assert got[k].shape == ref[k].shape, (what, k)
-        bad = np.nonzero((got[k] != ref[k]).reshape(len(ref[k]), -1).any(1))[0]
-        assert not len(bad), (what, k, bad[:8], got[k][bad[:8]], ref[k][bad[:8]])
-    bad = [b for b in range(len(ref["c_eta"])) if not _bits_equal(got["c_eta"][b], ref["c_eta"][b])]
-    assert not bad, (what, "c_eta", bad[:8], got["c_eta"][bad[0]], ref["c_eta"][bad[0]])
 
 
 def _device_rows(st, radius, R, k_rows, n_obs_max, share=0.5, group=None, first_slot=None, prefill=SENTINEL):
