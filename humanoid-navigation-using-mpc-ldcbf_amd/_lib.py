@@ -71,6 +71,10 @@ SIGNATURES = {
                                                   f"c_eta n_inferred overflow schedule {_STEP_OUT} diag bounds hip_stream"),
     "lipmpc_lidar_grid_c_eta_batch": _sig(C.c_int, f"device:int B:i64 {_GRID_SCAN} n_obs_max:i32 v_max:i32 state occ ray_table noise "
                                                    "c_eta n_inferred overflow obs_xy obs_nv hits labels hip_stream"),
+    "lipmpc_lidar_c_eta_split_batch": _sig(C.c_int, f"device:int B:i64 {_SCAN} n_obs_max:i32 v_max:i32 state env_xy env_nv ray_table noise "
+                                                    "c_eta n_inferred overflow obs_xy obs_nv hits labels schedule split_rays:i32 pieces hip_stream"),
+    "lipmpc_lidar_grid_c_eta_split_batch": _sig(C.c_int, f"device:int B:i64 {_GRID_SCAN} n_obs_max:i32 v_max:i32 state occ ray_table noise "
+                                                         "c_eta n_inferred overflow obs_xy obs_nv hits labels split_rays:i32 pieces hip_stream"),
     "lipmpc_sense_grid_plan_step_batch": _sig(C.c_int, f"h B:i64 {_GRID_SCAN} state goal first_foot delta occ ray_table noise "
                                                        f"c_eta n_inferred overflow {_STEP_OUT} diag bounds hip_stream"),
     "lipmpc_rrt_default_params": _sig(C.c_int, "p:rrt_params"),

@@ -18,6 +18,9 @@
 //      neighbour" pointers + pointer jumping, then merging trees through ballot masks of tree membership — bit operations,
 //      no sweeps over neighbours' labels), clusters numbered by their smallest core index, border points to the smallest
 //      neighbouring cluster
+//   2b. (opt-in: lipmpc_lidar_c_eta_split_batch, split_rays > 0) every cluster cut into pieces of at most split_rays consecutive
+//      rays, in registers from the ballot masks of the cluster's members; the pieces take the clusters' place in 3 and 4 -- the
+//      walls of a room are one cluster whose hull holds the robot, the hulls of sectors of at most half a turn cannot
 //   3. hull per cluster: Jarvis march from the lexicographically smallest point, farthest point on collinear ties
 //      (= the CCW ring of extreme points Qhull / monotone chain return, same rotation as np.unique + monotone chain);
 //      four clusters march at once, one per 16-lane DPP row, every lane's candidates held in registers; a step's winner is
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const int32_t* __restrict__ env_nv, const double* __restrict__ ray_table, const double* __restrict__ noise,
     double* __restrict__ obs_xy, int32_t* __restrict__ obs_nv, double* __restrict__ c_eta, int32_t* __restrict__ n_inferred,
     int32_t* __restrict__ overflow, double* __restrict__ hits_out, int32_t* __restrict__ labels_out,
-    int32_t* __restrict__ sched, int dbg_stop) {
+    int32_t* __restrict__ sched, int dbg_stop, int split_rays, int32_t* __restrict__ pieces_out) {
 #define LIDAR_GRID 0
 #include "lipmpc_lidar_body.inc"
 #undef LIDAR_GRID
@@ -151,7 +154,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     long B, int R, double lidar_range, double eps, int min_samples, int n_obs_max, int v_max, const double* __restrict__ state,
     const double* __restrict__ ray_table, const double* __restrict__ noise, double* __restrict__ obs_xy,
     int32_t* __restrict__ obs_nv, double* __restrict__ c_eta, int32_t* __restrict__ n_inferred, int32_t* __restrict__ overflow,
-    double* __restrict__ hits_out, int32_t* __restrict__ labels_out, int dbg_stop, GridArg gm) {
+    double* __restrict__ hits_out, int32_t* __restrict__ labels_out, int dbg_stop, GridArg gm, int split_rays,
+    int32_t* __restrict__ pieces_out) {
 #define LIDAR_GRID 1
 #include "lipmpc_lidar_body.inc"
 #undef LIDAR_GRID
@@ -291,8 +295,11 @@ static int lidar_launch(int device, int64_t B, int32_t resolution, int32_t n_env
                         double lidar_range, double eps, int32_t min_samples, int32_t n_obs_max, int32_t v_max,
                         const double* state, const double* env_xy, const int32_t* env_nv, const double* ray_table,
                         const double* noise, double* obs_xy, int32_t* obs_nv, double* c_eta, int32_t* n_inferred,
-                        int32_t* overflow, double* hits, int32_t* labels, int32_t* schedule, void* hip_stream) {
-  if (B < 0 || resolution < 1 || resolution > RMAX || n_env < 0 || v_env < 1 || n_obs_max < 1 || v_max < 3 || v_max > VSTAGE) return LIPMPC_E_ARG;
+                        int32_t* overflow, double* hits, int32_t* labels, int32_t* schedule, int32_t split_rays, int32_t* pieces,
+                        void* hip_stream) {
+  if (B < 0 || resolution < 1 || resolution > RMAX || n_env < 0 || v_env < 1 || n_obs_max < 1 || v_max < 3 || v_max > VSTAGE ||
+      split_rays < 0 || split_rays > resolution / 2)
+    return LIPMPC_E_ARG;
   if (n_env > 65535) return LIPMPC_E_UNSUPPORTED;      // obstacle indices are kept as 16 bits in LDS
   if (B == 0) return LIPMPC_OK;
   if (!state || !ray_table || !n_inferred || !overflow || (n_env > 0 && (!env_xy || !env_nv)) || (!obs_xy != !obs_nv) ||
@@ -310,7 +317,7 @@ static int lidar_launch(int device, int64_t B, int32_t resolution, int32_t n_env
   }
   hipLaunchKernelGGL(lidar_sense_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)hip_stream, (long)B, resolution, n_env,
                      v_env, (long)(env_shared ? 0 : 1), lidar_range, eps, min_samples, n_obs_max, v_max, state, env_xy, env_nv,
-                     ray_table, noise, obs_xy, obs_nv, c_eta, n_inferred, overflow, hits, labels, schedule, dbg_stop);
+                     ray_table, noise, obs_xy, obs_nv, c_eta, n_inferred, overflow, hits, labels, schedule, dbg_stop, split_rays, pieces);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
@@ -322,7 +329,21 @@ extern "C" int lipmpc_lidar_sense_batch(int device, int64_t B, int32_t resolutio
                                         double* hits, int32_t* labels, void* hip_stream) {
   if (!obs_xy || !obs_nv) return LIPMPC_E_ARG;
   return lidar_launch(device, B, resolution, n_env, v_env, env_shared, lidar_range, eps, min_samples, n_obs_max, v_max, state,
-                      env_xy, env_nv, ray_table, noise, obs_xy, obs_nv, nullptr, n_inferred, overflow, hits, labels, nullptr, hip_stream);
+                      env_xy, env_nv, ray_table, noise, obs_xy, obs_nv, nullptr, n_inferred, overflow, hits, labels, nullptr, 0, nullptr, hip_stream);
+}
+
+extern "C" int lipmpc_lidar_c_eta_split_batch(int device, int64_t B, int32_t resolution, int32_t n_env, int32_t v_env,
+                                              int32_t env_shared, double lidar_range, double eps, int32_t min_samples,
+                                              int32_t n_obs_max, int32_t v_max, const double* state, const double* env_xy,
+                                              const int32_t* env_nv, const double* ray_table, const double* noise,
+                                              double* c_eta, int32_t* n_inferred, int32_t* overflow, double* obs_xy,
+                                              int32_t* obs_nv, double* hits, int32_t* labels, int32_t* schedule,
+                                              int32_t split_rays, int32_t* pieces, void* hip_stream) {
+  if (!c_eta) return LIPMPC_E_ARG;
+  if (schedule && B > 0x3fffffff) return LIPMPC_E_UNSUPPORTED;
+  return lidar_launch(device, B, resolution, n_env, v_env, env_shared, lidar_range, eps, min_samples, n_obs_max, v_max, state,
+                      env_xy, env_nv, ray_table, noise, obs_xy, obs_nv, c_eta, n_inferred, overflow, hits, labels, schedule,
+                      split_rays, pieces, hip_stream);
 }
 
 extern "C" int lipmpc_lidar_c_eta_batch(int device, int64_t B, int32_t resolution, int32_t n_env, int32_t v_env,
@@ -332,20 +353,20 @@ extern "C" int lipmpc_lidar_c_eta_batch(int device, int64_t B, int32_t resolutio
                                         double* c_eta, int32_t* n_inferred, int32_t* overflow, double* obs_xy,
                                         int32_t* obs_nv, double* hits, int32_t* labels, int32_t* schedule,
                                         void* hip_stream) {
-  if (!c_eta) return LIPMPC_E_ARG;
-  if (schedule && B > 0x3fffffff) return LIPMPC_E_UNSUPPORTED;
-  return lidar_launch(device, B, resolution, n_env, v_env, env_shared, lidar_range, eps, min_samples, n_obs_max, v_max, state,
-                      env_xy, env_nv, ray_table, noise, obs_xy, obs_nv, c_eta, n_inferred, overflow, hits, labels, schedule, hip_stream);
+  return lipmpc_lidar_c_eta_split_batch(device, B, resolution, n_env, v_env, env_shared, lidar_range, eps, min_samples, n_obs_max,
+                                        v_max, state, env_xy, env_nv, ray_table, noise, c_eta, n_inferred, overflow, obs_xy, obs_nv,
+                                        hits, labels, schedule, 0, nullptr, hip_stream);
 }
 
-extern "C" int lipmpc_lidar_grid_c_eta_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
-                                             const double* origin, const double* cell, double lidar_range, double eps,
-                                             int32_t min_samples, int32_t n_obs_max, int32_t v_max, const double* state,
-                                             const uint8_t* occ, const double* ray_table, const double* noise, double* c_eta,
-                                             int32_t* n_inferred, int32_t* overflow, double* obs_xy, int32_t* obs_nv, double* hits,
-                                             int32_t* labels, void* hip_stream) {
+extern "C" int lipmpc_lidar_grid_c_eta_split_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H,
+                                                   int32_t grid_shared, const double* origin, const double* cell, double lidar_range,
+                                                   double eps, int32_t min_samples, int32_t n_obs_max, int32_t v_max,
+                                                   const double* state, const uint8_t* occ, const double* ray_table,
+                                                   const double* noise, double* c_eta, int32_t* n_inferred, int32_t* overflow,
+                                                   double* obs_xy, int32_t* obs_nv, double* hits, int32_t* labels, int32_t split_rays,
+                                                   int32_t* pieces, void* hip_stream) {
   if (B < 0 || resolution < 1 || resolution > RMAX || W < 1 || H < 1 || n_obs_max < 1 || v_max < 3 || v_max > VSTAGE || !origin ||
-      !cell || !c_eta)
+      !cell || !c_eta || split_rays < 0 || split_rays > resolution / 2)
     return LIPMPC_E_ARG;
   const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
   if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY) ||
@@ -360,8 +381,19 @@ extern "C" int lipmpc_lidar_grid_c_eta_batch(int device, int64_t B, int32_t reso
   const GridArg gm{W, H, grid_shared ? 0L : (long)W * H, ox, oy, dx, dy, (int)nx, (int)ny, occ};
   hipLaunchKernelGGL(lidar_grid_scan_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)hip_stream, (long)B, resolution, lidar_range, eps,
                      min_samples, n_obs_max, v_max, state, ray_table, noise, obs_xy, obs_nv, c_eta, n_inferred, overflow, hits, labels,
-                     lidar_dbg_stop(), gm);
+                     lidar_dbg_stop(), gm, split_rays, pieces);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_lidar_grid_c_eta_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                                             const double* origin, const double* cell, double lidar_range, double eps,
+                                             int32_t min_samples, int32_t n_obs_max, int32_t v_max, const double* state,
+                                             const uint8_t* occ, const double* ray_table, const double* noise, double* c_eta,
+                                             int32_t* n_inferred, int32_t* overflow, double* obs_xy, int32_t* obs_nv, double* hits,
+                                             int32_t* labels, void* hip_stream) {
+  return lipmpc_lidar_grid_c_eta_split_batch(device, B, resolution, W, H, grid_shared, origin, cell, lidar_range, eps, min_samples,
+                                             n_obs_max, v_max, state, occ, ray_table, noise, c_eta, n_inferred, overflow, obs_xy, obs_nv,
+                                             hits, labels, 0, nullptr, hip_stream);
 }
 
 extern "C" int64_t lipmpc_lidar_schedule_words(int64_t B) { return B < 0 ? LIPMPC_E_ARG : SCHED_ORDER + 2L * B; }

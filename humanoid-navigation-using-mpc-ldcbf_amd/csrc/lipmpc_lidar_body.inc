@@ -85,6 +85,7 @@
   const int NW = (n_pts + 63) >> 6;                      // words / passes actually in use (wave-uniform)
   const int npad = NW << 6;
   if (labels_out) for (int i = lane; i < R; i += 64) labels_out[b * R + i] = -2;      // -2 = no reading
+  if (pieces_out) for (int i = lane; i < R; i += 64) pieces_out[b * R + i] = -2;
   const double eps2 = eps * eps;
   unsigned long long vmask[WORDS];                  // which points exist
 #pragma unroll
@@ -138,6 +139,11 @@
   }
 
   LIDAR_PHASE_END(3);
+  // 2b. (opt-in) clusters cut into pieces of at most split_rays rays, which take the clusters' place -> rootr, roots_, n_clusters
+  if (split_rays > 0 || pieces_out) {                    // wave-uniform
+    const int split = split_rays > 0 ? split_rays : R;   // (pieces asked for without splitting: every cluster is one piece)
+#include "lipmpc_lidar_pieces.inc"
+  }
   // 3 + 4. hull per cluster, constraint assembly -> obs_xy / obs_nv / c_eta, n_out, ovf
 #include "lipmpc_lidar_hulls.inc"
   if (lane == 0) { n_inferred[b] = n_out; overflow[b] = ovf; }

@@ -31,10 +31,12 @@ def sensor_outputs(B, n_obs_max, v_max, resolution):
     f64, i32 = torch.float64, torch.int32
     return {"n_inferred": (i32, (B,), True), "overflow": (i32, (B,), True), "obs_xy": (f64, (B, n_obs_max, v_max, 2), False),
             "obs_nv": (i32, (B, n_obs_max), False), "c_eta": (f64, (B, n_obs_max, 4), False),
-            "hits": (f64, (B, resolution, 2), False), "labels": (i32, (B, resolution), False)}
+            "hits": (f64, (B, resolution, 2), False), "labels": (i32, (B, resolution), False),
+            "pieces": (i32, (B, resolution), False)}
 
 
-SENSOR_OUTPUTS = tuple(sensor_outputs(0, 0, 0, 0))                           # the names
+_SPLIT_SCAN_OUTPUTS = tuple(sensor_outputs(0, 0, 0, 0))                      # the names: what the *_split_batch entry points write
+SENSOR_OUTPUTS = tuple(k for k in _SPLIT_SCAN_OUTPUTS if k != "pieces")      # what their parents write (no pieces)
 _RING_SCAN_OUTPUTS = tuple(k for k in SENSOR_OUTPUTS if k != "c_eta")       # lipmpc_lidar_sense_batch has no c_eta
 
 
@@ -97,23 +99,29 @@ class GridMap:
 
 class LidarSensor:
     """Batched range_finder(): scan -> noise -> DBSCAN -> hulls, one wavefront per robot, rings in the layout
-    BatchedLipMpc.plan_step_batch consumes.  ``LidarSensor.from_grid``: the same sensor over an occupancy grid."""
+    BatchedLipMpc.plan_step_batch consumes.  ``LidarSensor.from_grid``: the same sensor over an occupancy grid.
+    ``split_rays`` > 0 (at most resolution / 2; scans with ``c_eta=True``): every cluster is cut into pieces of at most that many
+    consecutive rays, each with its own hull and (c, eta) row (include/lipmpc.h, lipmpc_lidar_c_eta_split_batch) -- one hull
+    around the walls of a room holds the robot standing in it, the hulls of sectors of at most half a turn cannot."""
 
     @classmethod
-    def from_grid(cls, grid, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32, device=None):
+    def from_grid(cls, grid, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32, device=None, split_rays=0):
         """A sensor whose true map is the GridMap ``grid`` (shared, or one map per robot of the batches it will scan): ``sense``
         (with ``c_eta=True``), ``sense_plan_step`` and ``alloc_outputs`` as for rings, same return dicts.  The robots are scanned
         in index order (no ``schedule``).  A robot standing in a solid cell gets no scan: n_inferred = 0, overflow = 1.  A
         (range, cell) pair whose window of cells within range exceeds 49152 cells is refused (RuntimeError, code -2)."""
-        sn = cls([], lidar_range, resolution, n_obs_max, v_max, device)
+        sn = cls([], lidar_range, resolution, n_obs_max, v_max, device, split_rays)
         sn.grid = grid.to(sn.device)
         return sn
 
     grid = None                # the GridMap of a sensor made by from_grid
 
-    def __init__(self, env_rings, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32, device=None):
+    def __init__(self, env_rings, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32, device=None, split_rays=0):
+        if not 0 <= int(split_rays) <= int(resolution) // 2:
+            raise ValueError("split_rays: 0 (off) .. resolution / 2")
         if not torch.cuda.is_available():
             raise RuntimeError("lipmpc needs a HIP device; there is no CPU path")
+        self.split_rays = int(split_rays)
         self.lib = _lib.load()
         self.device_index = torch.cuda.current_device() if device is None else int(device)
         self.device = torch.device("cuda", self.device_index)
@@ -135,7 +143,7 @@ class LidarSensor:
         names = ("n_inferred", "overflow") + (("obs_xy", "obs_nv") if rings else ()) + (("c_eta",) if c_eta else ())
         out = _alloc(table, names, self.device, torch.zeros)
         if with_debug:
-            out.update(_alloc(table, ("hits", "labels"), self.device))
+            out.update(_alloc(table, ("hits", "labels") + (("pieces",) if self.split_rays and c_eta else ()), self.device))
         return out
 
     def make_schedule(self, B):
@@ -147,7 +155,8 @@ class LidarSensor:
     def sense(self, state, noise=None, with_debug=False, out=None, env_xy=None, env_nv=None, c_eta=False, rings=True,
               schedule="auto", grid=None):
         """state [B,5] device tensor; noise [B,resolution,2] or None -> dict(n_inferred, overflow[, obs_xy, obs_nv][, c_eta]
-        [, hits, labels]).  ``c_eta=True``: the constraint assembly runs in the same launch (lipmpc_lidar_c_eta_batch) and
+        [, hits, labels][, pieces]).  ``pieces`` [B,resolution] (-2 no reading, -1 noise, else the number of the reading's piece)
+        comes with ``with_debug`` from a sensor with ``split_rays`` > 0; such a sensor scans with ``c_eta=True`` only.  ``c_eta=True``: the constraint assembly runs in the same launch (lipmpc_lidar_c_eta_batch) and
         the dict carries c_eta [B,n_obs_max,4] = (c, eta) of every inferred hull at the robot's CoM -- what
         ``BatchedLipMpc.plan_step_batch_c_eta`` solves against; with ``rings=False`` the hulls never leave the kernel.
         ``schedule``: a buffer of ``make_schedule(B)``, None (robots scanned in index order), or "auto" (default): with
@@ -170,12 +179,18 @@ class LidarSensor:
         _check(noise, (B, self.resolution, 2), torch.float64, dev, "noise")
         stream = torch.cuda.current_stream(dev).cuda_stream
         grid = self.grid if grid is None else grid
+        # the *_split_batch twins only where they are needed: the parents keep receiving exactly their own arguments
+        split = self.split_rays > 0 or out.get("pieces") is not None
+        if split and not want_ce:
+            raise ValueError("split_rays / pieces: the split scans assemble the half-spaces (c_eta=True)")
+        suffix, outputs = ("_split_batch", dict(_named(out, _SPLIT_SCAN_OUTPUTS), split_rays=self.split_rays)) if split else \
+            ("_batch", _named(out, SENSOR_OUTPUTS))
         if grid is not None:
             if not want_ce or env_xy is not None or not (schedule is None or schedule == "auto"):
                 raise ValueError("a grid scan assembles the half-spaces (c_eta=True), takes no rings as its map and no schedule")
-            _lib.call("lipmpc_lidar_grid_c_eta_batch", device=self.device_index, B=B, resolution=self.resolution, **grid._args(B, dev),
+            _lib.call("lipmpc_lidar_grid_c_eta" + suffix, device=self.device_index, B=B, resolution=self.resolution, **grid._args(B, dev),
                       lidar_range=self.lidar_range, eps=DBSCAN_EPS, min_samples=DBSCAN_MIN_SAMPLES, n_obs_max=self.n_obs_max,
-                      v_max=self.v_max, state=state, ray_table=self.table, noise=noise, **_named(out, SENSOR_OUTPUTS), hip_stream=stream)
+                      v_max=self.v_max, state=state, ray_table=self.table, noise=noise, **outputs, hip_stream=stream)
             return out
         n_env, v_env, shared, exy, env = self.n_env, self.v_env, 1, self.env_xy, self.env_nv
         if env_xy is not None:
@@ -200,7 +215,7 @@ class LidarSensor:
                                      or schedule.numel() != int(self.lib.lipmpc_lidar_schedule_words(B))):
             raise ValueError("schedule: a buffer of make_schedule(B) for this B, with c_eta=True")
         if want_ce:
-            entry, outputs = "lipmpc_lidar_c_eta_batch", dict(_named(out, SENSOR_OUTPUTS), schedule=schedule)
+            entry, outputs = "lipmpc_lidar_c_eta" + suffix, dict(outputs, schedule=schedule)
         else:
             entry, outputs = "lipmpc_lidar_sense_batch", _named(out, _RING_SCAN_OUTPUTS)
         _lib.call(entry, device=self.device_index, B=B, resolution=self.resolution, n_env=n_env, v_env=v_env, env_shared=shared,
@@ -213,7 +228,8 @@ class LidarSensor:
         """One MPC step of the unknown-environment variant in one C call (lipmpc_sense_plan_step_batch): scan + constraint
         assembly, then ``solver``'s step against the assembled half-spaces.  ``solver``: a BatchedLipMpc whose
         n_obs_max / v_max are this sensor's.  Returns (sen, out) as ``sense(..., c_eta=True, rings=False)`` and
-        ``plan_step_batch_c_eta`` would -- the same bits, whatever the solver served before: the step takes the split launch
+        ``plan_step_batch_c_eta`` would -- the same bits, whatever the solver served before (a sensor with ``split_rays`` > 0
+        issues exactly those two calls on the current stream: the one-call entry points have no split twin): the step takes the split launch
         with the workspace of the current stream exactly as ``plan_step_batch_c_eta`` does (streams and graphs: as
         ``BatchedLipMpc.plan_step_batch``).  A ``schedule`` buffer, like the solver's schedule and warm-start records, is
         shared by every launch it is given to: those must be ordered on one stream."""
@@ -237,9 +253,13 @@ class LidarSensor:
                                      or schedule.numel() != int(self.lib.lipmpc_lidar_schedule_words(B))):
             raise ValueError("schedule: a buffer of make_schedule(B) for this B")
         solver._ensure_workspace(B)
+        if self.grid is not None and schedule is not None:
+            raise ValueError("a grid scan takes no schedule")
+        if self.split_rays > 0:
+            self.sense(state, noise, out=sen, c_eta=True, rings=False, schedule=schedule)
+            solver.plan_step_batch_c_eta(state, goal, first_foot, sen["c_eta"], delta, out=out, overflow=sen["overflow"], bounds=bounds)
+            return sen, out
         if self.grid is not None:
-            if schedule is not None:
-                raise ValueError("a grid scan takes no schedule")
             _lib.call("lipmpc_sense_grid_plan_step_batch", h=solver._h, B=B, resolution=self.resolution, **self.grid._args(B, self.device),
                       lidar_range=self.lidar_range, eps=DBSCAN_EPS, min_samples=DBSCAN_MIN_SAMPLES, state=state, goal=goal,
                       first_foot=first_foot, delta=delta, ray_table=self.table, noise=noise, **_named(sen, handed_over),
@@ -257,18 +277,19 @@ class LidarSensor:
 class HumanoidMPCUnknownEnvironment(HumanoidMPC):
     """The robot only perceives obstacles through its LiDAR (HumanoidMPCUnknownEnvironment.py:13-28): every sample the
     obstacle set is re-inferred on the GPU and handed to the step solver.  ``noise_seed`` seeds the readings' noise
-    (the reference's is unseeded); ``noise_seed=None`` = noiseless readings."""
+    (the reference's is unseeded); ``noise_seed=None`` = noiseless readings.  ``split_rays``: as ``LidarSensor``'s (0 = one hull
+    per cluster, as the reference)."""
 
     def __init__(self, goal, obstacles, N_horizon=3, N_mpc_timesteps=100, sampling_time=1e-3, init_state=None,
                  start_with_right_foot: bool = True, verbosity: int = 1, lidar_range: float = 3.0,
-                 lidar_resolution: int = 360, noise_seed: int | None = 0, **kw):
-        self.lidar_range, self.lidar_resolution = lidar_range, lidar_resolution
+                 lidar_resolution: int = 360, noise_seed: int | None = 0, split_rays: int = 0, **kw):
+        self.lidar_range, self.lidar_resolution, self.split_rays = lidar_range, lidar_resolution, int(split_rays)
         super().__init__(goal, obstacles, N_horizon, N_mpc_timesteps, sampling_time,
                          np.zeros(5) if init_state is None else init_state, start_with_right_foot, verbosity, **kw)
         # the reference scans `ch.points` (raw input order), HumanoidMPCUnknownEnvironment.py:46
         env = [np.asarray(o.points, float) if hasattr(o, "points") else np.asarray(o, float) for o in obstacles]
         self._env = env
-        self._sensor = LidarSensor(env, lidar_range, lidar_resolution, device=self._device)
+        self._sensor = LidarSensor(env, lidar_range, lidar_resolution, device=self._device, split_rays=self.split_rays)
         self._big_sensor = None
         self._gen = None if noise_seed is None else torch.Generator(device=self._sensor.device).manual_seed(int(noise_seed))
         self.list_inferred_obstacles = []
@@ -290,7 +311,7 @@ class HumanoidMPCUnknownEnvironment(HumanoidMPC):
             # still does not fit is an error, not a truncated obstacle list
             if self._big_sensor is None:
                 self._big_sensor = LidarSensor(self._env, self.lidar_range, self.lidar_resolution, n_obs_max=50, v_max=32,
-                                               device=self._device)
+                                               device=self._device, split_rays=self.split_rays)
             out = self._big_sensor.sense(st, noise, c_eta=True, with_debug=True)
             torch.cuda.synchronize(dev)
             if int(out["overflow"][0]):
@@ -333,17 +354,19 @@ class UnknownEnvFleet:
     integrated into the mapper's evidence grid (lipmpc_map_update_batch) between the scan and the solve, inside the captured
     graph; the loop itself is not disturbed (same X_pred / U_pred, bit for bit).  A run adds to the evidence the mapper holds
     (``mapper.reset()`` forgets it).  ``run_replanning`` plans on that map toward given goals; ``run_exploring`` needs no goals:
-    the robots walk to the map's frontiers until none is left."""
+    the robots walk to the map's frontiers until none is left.
+    ``split_rays`` > 0: the scans cut their clusters into sectors of at most that many rays (``LidarSensor``) -- what lets a robot
+    walk INSIDE a room, whose walls are one cluster around it (tests/golden/EXPLORATION_ROOMS.md)."""
 
     def __init__(self, env_rings=None, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
-                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None, mapper=None):
+                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None, mapper=None, split_rays=0):
         from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR, FLAG_WARM_START
         if (env_rings is None) == (grid is None):
             raise ValueError("the true map: env_rings or grid")
         if grid is not None:
-            self.sensor = LidarSensor.from_grid(grid, lidar_range, resolution, n_obs_max, v_max, device)
+            self.sensor = LidarSensor.from_grid(grid, lidar_range, resolution, n_obs_max, v_max, device, split_rays)
         else:
-            self.sensor = LidarSensor(env_rings, lidar_range, resolution, n_obs_max, v_max, device)
+            self.sensor = LidarSensor(env_rings, lidar_range, resolution, n_obs_max, v_max, device, split_rays)
         self.warm_start = bool(warm_start)
         self.solver = BatchedLipMpc(LipMpcParams(N=N_horizon, n_obs_max=n_obs_max, v_max=v_max,
                                                  flags=(0 if exact else FLAG_INTERIOR) | (FLAG_WARM_START if warm_start else 0),

@@ -38,7 +38,8 @@ extern "C" {
                                 *    + lipmpc_neighbour_workspace_bytes / lipmpc_neighbour_c_eta_batch;
                                 *    + lipmpc_map_update_batch; + lipmpc_rrt_plan_grid_batch, LIPMPC_RRT_OUTSIDE_GRID;
                                 *    + lipmpc_grid_field_batch / lipmpc_grid_path_batch;
-                                *    + lipmpc_grid_frontier_field_batch / lipmpc_grid_frontier_path_batch */
+                                *    + lipmpc_grid_frontier_field_batch / lipmpc_grid_frontier_path_batch;
+                                *    + lipmpc_lidar_c_eta_split_batch / lipmpc_lidar_grid_c_eta_split_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -345,8 +346,9 @@ int lipmpc_sense_plan_step_batch(lipmpc_handle* h, int64_t B, int32_t resolution
 
 /* The unknown-environment front end on an OCCUPANCY GRID (backward-compatible addition): lipmpc_lidar_c_eta_batch with the true
  * map given as cells instead of vertex rings.  Only the ray casting differs; the readings then go through the same clustering,
- * hulls and constraint assembly in the same launch, and every output means what it means there.  (Convex hulls of clusters
- * over-cover concave walls, as they do on adjoining polygons.)
+ * hulls and constraint assembly in the same launch, and every output means what it means there.  (One convex hull per cluster
+ * over-covers a concave wall, and the hull of a room's walls holds the robot standing in the room: such a robot gets a flipped
+ * half-space and no feasible step.  lipmpc_lidar_grid_c_eta_split_batch cuts the clusters into sectors first.)
  *  occ    uint8, [W,H] if grid_shared else [B,W,H], DEVICE: cell (i, j) at occ[i * H + j], solid if nonzero
  *  origin (ox, oy), cell (dx, dy): two doubles each, HOST pointers read during the call; dx, dy > 0.  Cell (i, j) is the
  *         rectangle [ox + i dx, ox + (i+1) dx) x [oy + j dy, oy + (j+1) dy); everything outside the grid is free (a robot
@@ -380,6 +382,44 @@ int lipmpc_lidar_grid_c_eta_batch(int device, int64_t B, int32_t resolution, int
                                   const uint8_t* occ, const double* ray_table, const double* noise, double* c_eta,
                                   int32_t* n_inferred, int32_t* overflow, double* obs_xy, int32_t* obs_nv, double* hits,
                                   int32_t* labels, void* hip_stream);
+
+/* CLUSTERS SPLIT INTO SECTORS (backward-compatible addition): lipmpc_lidar_c_eta_batch / lipmpc_lidar_grid_c_eta_batch with a stage
+ * between clustering and hulls, in the same launch, that cuts every cluster into PIECES of at most split_rays consecutive rays.
+ * Every piece gets its own hull and its own (c, eta) row; wherever the two parents say "cluster" about hulls, slots and
+ * overflow, these say "piece".  Why: the walls of a room the robot stands in are ONE cluster whose hull contains the robot.
+ * For split_rays <= resolution / 2 the rays of a piece lie in an open half-plane through the robot, so the robot is an extreme
+ * point of the cone that holds the piece's noise-free readings and cannot lie in their hull.
+ *  split_rays  0: off -- every output bit-identical to the parent entry point's (which IS this call with 0 and NULL).
+ *              < 0 or > resolution / 2: LIPMPC_E_ARG.
+ *  pieces      [B,resolution] int32 or NULL: -2 no reading, -1 noise, else the number of the reading's piece in the order below,
+ *              counted before any piece is dropped (with split_rays = 0 every cluster is one piece: the cluster's label).
+ *  the rest as the parent entry point.
+ * THE RULE, in integers, R = resolution.  For one cluster take the rays of its readings in ascending order, r_1 < ... < r_n
+ * (DBSCAN noise belongs to no cluster and to no piece; border readings belong to their cluster):
+ *  - gaps: g_t = (r_t - r_{t-1}) mod R with r_0 = r_n; for n = 1 the gap is R.
+ *  - anchor: a = the r_t with the largest g_t, the smallest such r_t on a tie (a cluster holding every ray anchors at ray 0).
+ *  - offsets: o_t = (r_t - a) mod R;  extent: E = max o_t + 1;  piece count: n_p = ceil(E / split_rays).
+ *  - piece of reading t: p_t = floor(o_t * n_p / E) -- balanced pieces, each within split_rays consecutive rays; a cluster
+ *    with E <= split_rays stays whole.
+ * Pieces are numbered cluster by cluster (clusters in label order) and inside a cluster by ascending p.  Each piece then goes
+ * through the hull and the constraint assembly as a cluster does: a piece with fewer than 3 extreme points takes no slot, the
+ * others fill the slots in piece order, and overflow = 1 if more than 64 pieces exist (the kernel stages 64; then, as with more
+ * than 64 clusters, nothing but the flag is defined about slots and `pieces`) or if the pieces do not fit n_obs_max / v_max.
+ * Reproduced bit for bit in numpy by tests/lidar_split_oracle.py.
+ * There is no split twin of the lipmpc_sense_*plan_step_batch calls: issue the scan and lipmpc_plan_step_batch_c_eta. */
+int lipmpc_lidar_c_eta_split_batch(int device, int64_t B, int32_t resolution, int32_t n_env, int32_t v_env,
+                                   int32_t env_shared, double lidar_range, double eps, int32_t min_samples,
+                                   int32_t n_obs_max, int32_t v_max, const double* state, const double* env_xy,
+                                   const int32_t* env_nv, const double* ray_table, const double* noise,
+                                   double* c_eta, int32_t* n_inferred, int32_t* overflow, double* obs_xy,
+                                   int32_t* obs_nv, double* hits, int32_t* labels, int32_t* schedule,
+                                   int32_t split_rays, int32_t* pieces, void* hip_stream);
+int lipmpc_lidar_grid_c_eta_split_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                                        const double* origin, const double* cell, double lidar_range, double eps,
+                                        int32_t min_samples, int32_t n_obs_max, int32_t v_max, const double* state,
+                                        const uint8_t* occ, const double* ray_table, const double* noise, double* c_eta,
+                                        int32_t* n_inferred, int32_t* overflow, double* obs_xy, int32_t* obs_nv, double* hits,
+                                        int32_t* labels, int32_t split_rays, int32_t* pieces, void* hip_stream);
 
 /* lipmpc_sense_plan_step_batch on an occupancy grid: lipmpc_lidar_grid_c_eta_batch (n_obs_max / v_max from the handle), then on
  * the same stream lipmpc_plan_step_batch_c_eta against those half-spaces and the scan's overflow flags -- a robot whose
