@@ -60,6 +60,9 @@ SIGNATURES = {
     "lipmpc_advance_batch": _sig(C.c_int, "h B:i64 state first_foot U theta status hip_stream"),
     "lipmpc_fleet_update_batch": _sig(C.c_int, "h B:i64 k_max:i32 stop_obj:f64 state first_foot walking last_obj n_steps last_status n_overflow "
                                                "sample X_pred U_pred U theta omega obj status overflow hip_stream"),
+    "lipmpc_fleet_recover_update_batch": _sig(C.c_int, "h B:i64 k_max:i32 stop_obj:f64 state first_foot walking last_obj n_steps last_status "
+                                                       "n_overflow sample X_pred U_pred U theta omega obj status overflow goal c_eta delta "
+                                                       "max_recover:i32 recover_run n_recover recover_margin hip_stream"),
     "lipmpc_rollout_batch": _sig(C.c_int, "h B:i64 k_max:i32 mpc_step:i32 stop_obj:f64 state0 goal first_foot delta obs_xy obs_nv "
                                           "X_pred U_pred n_steps last_status total_iters bounds hip_stream"),
     "lipmpc_lidar_sense_batch": _sig(C.c_int, f"device:int B:i64 {_SCAN} n_obs_max:i32 v_max:i32 state env_xy env_nv ray_table noise "

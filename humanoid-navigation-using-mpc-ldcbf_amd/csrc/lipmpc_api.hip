@@ -59,6 +59,94 @@ __global__ void fleet_update_kernel(long B, int k_max, double stop_obj, double c
 }
 __global__ void fleet_next_sample_kernel(int32_t* sample) { *sample += 1; }
 
+// The capture step of a robot whose solve failed (include/lipmpc.h: lipmpc_fleet_recover_update_batch), every expression as the
+// contract writes it: the capture point, the least margin of the sample's rows at it, the heading rule of the step at k = 0.
+struct CaptureStep { double cpx, cpy, margin, omega, theta; };
+__device__ __forceinline__ CaptureStep capture_step(const double* __restrict__ x, double beta, double omega_max, double tau,
+                                                    const double* __restrict__ goal, const double* __restrict__ rows, int n_obs,
+                                                    double delta) {
+#pragma clang fp contract(off)
+  CaptureStep s;
+  s.cpx = x[0] + x[1] / beta;
+  s.cpy = x[2] + x[3] / beta;
+  double margin = INFINITY;
+  bool nan_row = false;
+  for (int j = 0; j < n_obs; ++j) {
+    const double cx = rows[4 * j], cy = rows[4 * j + 1], ex = rows[4 * j + 2], ey = rows[4 * j + 3];
+    if (ex == 0.0 && ey == 0.0) continue;                  // an empty slot (a NaN in eta is a used row)
+    const double m = (ex * (s.cpx - cx) + ey * (s.cpy - cy)) - delta;
+    nan_row = nan_row || m != m;
+    margin = fmin(margin, m);
+  }
+  s.margin = nan_row ? -INFINITY : margin;           // (NaN is kept for "not evaluated")
+  s.omega = fmin(fmax(atan2(goal[1] - x[2], goal[0] - x[0]) - x[4], -omega_max), omega_max);
+  s.theta = x[4] + s.omega * tau;
+  return s;
+}
+
+// one sample of a host-driven fleet loop in which a failed solve costs a capture step instead of the robot
+// (include/lipmpc.h: lipmpc_fleet_recover_update_batch); fleet_update_kernel's rule around it
+__global__ void fleet_recover_update_kernel(long B, int k_max, double stop_obj, double ch, double sh_over_beta, double beta_sh,
+                                            double beta, double omega_max, double tau, int N, int n_obs,
+                                            double* __restrict__ state, int8_t* __restrict__ foot, int8_t* __restrict__ walking,
+                                            double* __restrict__ last_obj, int32_t* __restrict__ n_steps,
+                                            int32_t* __restrict__ last_status, int32_t* __restrict__ n_overflow,
+                                            const int32_t* __restrict__ sample, double* __restrict__ X_pred,
+                                            double* __restrict__ U_pred, const double* __restrict__ U,
+                                            const double* __restrict__ theta, const double* __restrict__ omega,
+                                            const double* __restrict__ obj, const int32_t* __restrict__ status,
+                                            const int32_t* __restrict__ overflow, const double* __restrict__ goal,
+                                            const double* __restrict__ c_eta, const double* __restrict__ delta, int max_recover,
+                                            int32_t* __restrict__ recover_run, int32_t* __restrict__ n_recover,
+                                            double* __restrict__ recover_margin) {
+  const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int k = *sample;
+  if (k >= k_max) return;
+  bool w = walking[b] != 0 && last_obj[b] >= stop_obj;
+  const int st = (overflow && overflow[b]) ? LIPMPC_STATUS_SENSOR_OVERFLOW : status[b];
+  if (w && overflow) n_overflow[b] += overflow[b];
+  if (w) last_status[b] = st;
+  const bool solved = st == LIPMPC_STATUS_SOLVED || st == LIPMPC_STATUS_UNCERTIFIED;
+  double* x = state + b * 5;
+  double margin = NAN;
+  bool recover = false;
+  CaptureStep cs{};
+  if (w && (st == LIPMPC_STATUS_INFEASIBLE || st == LIPMPC_STATUS_MAX_ITER) && recover_run[b] < max_recover &&
+      isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]) && isfinite(x[3])) {
+    cs = capture_step(x, beta, omega_max, tau, goal + b * 2, c_eta ? c_eta + b * (long)n_obs * 4 : nullptr, c_eta ? n_obs : 0,
+                      delta ? delta[b] : 0.0);
+    margin = cs.margin;
+    recover = margin >= 0.0;
+  }
+  double ux, uy, om;
+  if (recover) {                                           // (the failed solve's outputs are NaN: not read)
+    ux = cs.cpx; uy = cs.cpy; om = cs.omega;
+    lip_advance(ch, sh_over_beta, beta_sh, ux, uy, x[0], x[1], x[2], x[3]);
+    x[4] = cs.theta;
+    foot[b] = (int8_t)(-foot[b]);
+    recover_run[b] += 1;
+    n_recover[b] += 1;
+  } else {
+    ux = U[b * N * 2 + 0]; uy = U[b * N * 2 + 1]; om = omega[b * N];
+    w = w && solved;
+    if (w) {
+      last_obj[b] = obj[b];
+      lip_advance(ch, sh_over_beta, beta_sh, ux, uy, x[0], x[1], x[2], x[3]);
+      x[4] = theta[b * (N + 1) + 1];
+      foot[b] = (int8_t)(-foot[b]);
+      n_steps[b] += 1;
+      if (max_recover > 0) recover_run[b] = 0;
+    }
+  }
+  walking[b] = w ? 1 : 0;
+  recover_margin[b] = margin;
+  double* up = U_pred + (b * (long)k_max + k) * 3;
+  up[0] = ux; up[1] = uy; up[2] = om;
+  double* xp = X_pred + (b * (long)(k_max + 1) + k + 1) * 5;
+  for (int i = 0; i < 5; ++i) xp[i] = x[i];
+}
+
 // The order of the NEXT step launch on a schedule from the costs this launch left: problems by descending cost (counting
 // sort, one workgroup; which of two equally costly problems comes first is immaterial).
 __global__ __launch_bounds__(1024) void order_by_cost_kernel(long B, int32_t* __restrict__ sched) {
@@ -475,6 +563,28 @@ int lipmpc_fleet_update_batch(lipmpc_handle* h, int64_t B, int32_t k_max, double
   hipLaunchKernelGGL(fleet_update_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, (long)B,
                      k_max, stop_obj, h->k.ch, h->k.sh_over_beta, h->k.beta_sh, h->k.N, state, first_foot, walking, last_obj,
                      n_steps, last_status, n_overflow, sample, X_pred, U_pred, U, theta, omega, obj, status, overflow);
+  hipLaunchKernelGGL(fleet_next_sample_kernel, dim3(1), dim3(1), 0, (hipStream_t)hip_stream, sample);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+int lipmpc_fleet_recover_update_batch(lipmpc_handle* h, int64_t B, int32_t k_max, double stop_obj, double* state,
+                                      int8_t* first_foot, int8_t* walking, double* last_obj, int32_t* n_steps,
+                                      int32_t* last_status, int32_t* n_overflow, int32_t* sample, double* X_pred,
+                                      double* U_pred, const double* U, const double* theta, const double* omega,
+                                      const double* obj, const int32_t* status, const int32_t* overflow, const double* goal,
+                                      const double* c_eta, const double* delta, int32_t max_recover, int32_t* recover_run,
+                                      int32_t* n_recover, double* recover_margin, void* hip_stream) {
+  if (!h || B < 0 || k_max < 1 || max_recover < 0) return LIPMPC_E_ARG;
+  if (B == 0) return LIPMPC_OK;
+  if (!state || !first_foot || !walking || !last_obj || !n_steps || !last_status || !sample || !X_pred || !U_pred || !U ||
+      !theta || !omega || !obj || !status || (overflow && !n_overflow) || !goal || !recover_run || !n_recover || !recover_margin)
+    return LIPMPC_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(fleet_recover_update_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
+                     (long)B, k_max, stop_obj, h->k.ch, h->k.sh_over_beta, h->k.beta_sh, sqrt(h->p.g / h->p.h_com), h->k.omega_max,
+                     h->k.tau, h->k.N, h->k.n_obs, state, first_foot, walking, last_obj, n_steps, last_status, n_overflow, sample,
+                     X_pred, U_pred, U, theta, omega, obj, status, overflow, goal, c_eta, delta, max_recover, recover_run,
+                     n_recover, recover_margin);
   hipLaunchKernelGGL(fleet_next_sample_kernel, dim3(1), dim3(1), 0, (hipStream_t)hip_stream, sample);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

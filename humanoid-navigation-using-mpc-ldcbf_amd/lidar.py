@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .compat import HumanoidMPC, _ring_of
-from .solver import _STEP_OUTPUTS_GIVEN_C_ETA, _alloc, _check, _check_table, _named, fleet_state
+from .solver import _STEP_OUTPUTS_GIVEN_C_ETA, _alloc, _check, _check_table, _named, fleet_state, recover_state
 
 NOISE_STD = 0.01           # range_finder_wth_polygons_dbscan.py:163
 DBSCAN_EPS = 0.3           # :100
@@ -356,13 +356,23 @@ class UnknownEnvFleet:
     (``mapper.reset()`` forgets it).  ``run_replanning`` plans on that map toward given goals; ``run_exploring`` needs no goals:
     the robots walk to the map's frontiers until none is left.
     ``split_rays`` > 0: the scans cut their clusters into sectors of at most that many rays (``LidarSensor``) -- what lets a robot
-    walk INSIDE a room, whose walls are one cluster around it (tests/golden/EXPLORATION_ROOMS.md)."""
+    walk INSIDE a room, whose walls are one cluster around it (tests/golden/EXPLORATION_ROOMS.md).
+    ``recover`` = n > 0: a failed solve no longer ends the robot -- a robot whose solve ends INFEASIBLE or MAX_ITER takes a capture
+    step (foot on p + v / beta, heading turned toward its working goal) and solves again on the next sample, for at most n
+    samples in a row and only if the capture point respects every half-space the sample's solve was given, neighbour rows
+    included (lipmpc_fleet_recover_update_batch; DESIGN.md has the argument).  A recovering robot is walking.  6 is a sensible
+    value: on the recorded scenes a robot that recovery keeps needs one in a row (tests/golden/EXPLORATION_RECOVER.md).  0 (the default): every
+    call and every bit as before."""
 
     def __init__(self, env_rings=None, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
-                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None, mapper=None, split_rays=0):
+                 exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None, mapper=None, split_rays=0,
+                 recover=0):
         from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR, FLAG_WARM_START
         if (env_rings is None) == (grid is None):
             raise ValueError("the true map: env_rings or grid")
+        if isinstance(recover, bool) or not isinstance(recover, int) or recover < 0:
+            raise ValueError("recover: the most capture steps in a row, an int >= 0 (0 = a failed solve is final)")
+        self.recover = recover
         if grid is not None:
             self.sensor = LidarSensor.from_grid(grid, lidar_range, resolution, n_obs_max, v_max, device, split_rays)
         else:
@@ -409,6 +419,12 @@ class UnknownEnvFleet:
             # the scan hands its readings over, and `walking` (int8) goes to the update as the int32 mask the C call takes
             pl["sen"].update(_alloc(sensor_outputs(B, sn.n_obs_max, sn.v_max, sn.resolution), ("hits",), dev, torch.zeros))
             pl["mask"] = torch.zeros((B,), dtype=torch.int32, device=dev)
+        if self.recover:
+            # the counters of lipmpc_fleet_recover_update_batch, and the margin of each robot's last evaluated safety test
+            table = recover_state(B)
+            pl["rec"] = _alloc(table, table, dev, torch.zeros)
+            pl["last_margin"] = torch.zeros((B,), **f64)
+            pl["not_evaluated"] = torch.zeros((B,), dtype=torch.bool, device=dev)
         self._plan = pl
         return pl
 
@@ -418,7 +434,9 @@ class UnknownEnvFleet:
         seeded with noise_seed), None (noiseless) or a tensor [k_max,B,resolution,2].  Returns dict(X_pred
         [B,k_max+1,5], U_pred [B,k_max,3], n_steps [B] solved samples, last_status [B] (STATUS_SENSOR_OVERFLOW = 5: the
         robot was stopped because a scan's clusters did not fit the obstacle slots, or -- on a grid -- because it stands in a solid
-        cell), overflow [B] number of such scans).  With ``avoid`` also n_crowded [B]: the number of samples in which a
+        cell), overflow [B] number of such scans).  In a fleet with ``recover`` > 0 also n_recover [B] int32 recovery samples
+        taken, recover_run [B] int32 those in a row at the end, and recover_margin [B] the margin of the robot's last evaluated
+        safety test (NaN: never evaluated); a fleet without it returns exactly the entries it always did.  With ``avoid`` also n_crowded [B]: the number of samples in which a
         neighbour in range of the robot got no row (n_near > n_rows: more neighbours than k_rows or than free slots).
         One sample = noise draw (seeded mode), scan + constraint assembly, step solve, fleet update; with ``use_graph``
         it is captured once per run shape in a HIP graph (kept by the object) and replayed k_max times back to back.
@@ -431,7 +449,7 @@ class UnknownEnvFleet:
         B = state0.shape[0]
         mode = "none" if noise is None else ("seeded" if isinstance(noise, str) else "given")
         pl = self._plan_for(B, int(k_max), mode, delta is not None, stop_obj, use_graph)
-        fl, sen, out, nbuf, gen = pl["fl"], pl["sen"], pl["out"], pl["nbuf"], pl["gen"]
+        fl, sen, out, nbuf, gen, rec = pl["fl"], pl["sen"], pl["out"], pl["nbuf"], pl["gen"], pl.get("rec")
         pl["goal"].copy_(goal)
         if delta is not None:
             pl["delta"].copy_(delta)
@@ -444,6 +462,9 @@ class UnknownEnvFleet:
             fl["X_pred"].zero_(); fl["U_pred"].zero_(); fl["X_pred"][:, 0] = state0
             if avoid is not None:
                 pl["n_crowded"].zero_()
+            if rec is not None:
+                rec["recover_run"].zero_(); rec["n_recover"].zero_()
+                rec["recover_margin"].fill_(float("nan")); pl["last_margin"].fill_(float("nan"))
             sv.reset_warm_start()                            # every run starts cold (no-op without a record)
             if gen is not None:
                 gen.manual_seed(int(noise_seed))
@@ -467,7 +488,15 @@ class UnknownEnvFleet:
                     mapper.update(fl["state"], sen["hits"], mask=pl["mask"])
                 sv.plan_step_batch_c_eta(fl["state"], pl["goal"], fl["first_foot"], sen["c_eta"], pl["delta"], out=out,
                                          overflow=sen["overflow"])
-            sv.fleet_update(fl, out, overflow=sen["overflow"], stop_obj=stop_obj)
+            if rec is None:
+                sv.fleet_update(fl, out, overflow=sen["overflow"], stop_obj=stop_obj)
+            else:
+                # the rows the solve was given (the scan's, then the neighbours') vouch for the capture step
+                sv.fleet_update(fl, out, overflow=sen["overflow"], stop_obj=stop_obj,
+                                recover=dict(rec, goal=pl["goal"], c_eta=sen["c_eta"], delta=pl["delta"], max_recover=self.recover))
+                # NaN = not evaluated in this sample (an evaluated margin is never NaN): keep the robot's last evaluated one
+                torch.ne(rec["recover_margin"], rec["recover_margin"], out=pl["not_evaluated"])
+                torch.where(pl["not_evaluated"], pl["last_margin"], rec["recover_margin"], out=pl["last_margin"])
 
         if use_graph and pl["graph"] is None:
             reset()
@@ -499,6 +528,8 @@ class UnknownEnvFleet:
                 sample()
         res = dict(X_pred=fl["X_pred"], U_pred=fl["U_pred"], n_steps=fl["n_steps"], last_status=fl["last_status"],
                    overflow=fl["n_overflow"])
+        if rec is not None:
+            res.update(n_recover=rec["n_recover"], recover_run=rec["recover_run"], recover_margin=pl["last_margin"])
         if avoid is not None:
             res["n_crowded"] = pl["n_crowded"]
         return res
@@ -564,7 +595,8 @@ class UnknownEnvFleet:
           - a robot whose plan is not FOUND is parked (walking = 0; it keeps its working goal).
         After the last sample one closing plan on the final map and positions parks likewise and sets no goal; it is not counted.
         The model's limits: every robot goes to ITS nearest frontier (no task assignment), and the walker cannot turn on the
-        spot -- a working goal that jumps behind a robot can end its run in an INFEASIBLE solve.
+        spot while walking -- a working goal that jumps behind a robot can make its solve INFEASIBLE.  That ends the robot's run
+        only in a fleet without ``recover``: with it the robot takes a capture step and solves again (EXPLORATION_RECOVER.md).
         Returns what ``run`` returns, plus n_replans (int), explore_status [B] (RRT_*) of the closing plan, working_goal [B,2],
         walking [B] (int8), n_frontier and known_free [n_replans,F] (device tensors: per replan the frontier cells, and the cells
         with evidence <= -t_free, of every map), and done [B] (bool): not walking, not stopped by a failed solve, and the closing

@@ -315,7 +315,9 @@ class FrontierPlanner:
     are impassable but not inflated).  ``t_free`` / ``t_occ``: None = the mapper's ``w_miss`` / ``w_hit``.  ``max_seg``: as
     ``GridFieldPlanner``'s.
     The model's limits: every robot heads for ITS nearest frontier -- there is no task assignment, two robots side by side pick
-    the same cell -- and n_frontier == 0 (status RRT_NO_PATH for everybody) is how "nothing left to explore" is told."""
+    the same cell -- and n_frontier == 0 (status RRT_NO_PATH for everybody) is how "nothing left to explore" is told.  The
+    walker that follows these goals cannot turn on the spot while walking: a goal that jumps behind it can make its solve
+    INFEASIBLE, which costs the robot a capture step in a fleet with ``recover`` and its run in one without."""
 
     def __init__(self, r_inflate: int = 2, min_unknown: int = 2, t_free: int | None = None, t_occ: int | None = None,
                  max_seg: int | None = None, device: int | None = None):

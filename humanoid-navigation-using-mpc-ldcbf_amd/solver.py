@@ -115,6 +115,13 @@ def fleet_state(B, k_max):
             "X_pred": (f64, (B, k_max + 1, 5), True), "U_pred": (f64, (B, k_max, 3), True)}
 
 
+def recover_state(B):
+    """The recovery counters of a fleet loop (fleet_update(..., recover=)): consecutive recovery samples, their total, and the
+    safety margin of the last call (NaN where the safety test was not evaluated)."""
+    f64, i32 = torch.float64, torch.int32
+    return {"recover_run": (i32, (B,), True), "n_recover": (i32, (B,), True), "recover_margin": (f64, (B,), True)}
+
+
 def rollout_outputs(B, k_max):
     """Outputs of the on-device closed loop of at most ``k_max`` samples (rollout)."""
     f64, i32 = torch.float64, torch.int32
@@ -123,6 +130,7 @@ def rollout_outputs(B, k_max):
 
 
 STEP_OUTPUTS, FLEET_STATE = tuple(step_outputs(0, LipMpcParams())), tuple(fleet_state(0, 0))             # the names
+RECOVER_STATE = tuple(recover_state(0))
 _STEP_OUTPUTS_GIVEN_C_ETA = tuple(k for k in STEP_OUTPUTS if k != "c_eta")      # the entry points that take the half-spaces as input
 
 
@@ -354,16 +362,38 @@ class BatchedLipMpc:
         _lib.call("lipmpc_advance_batch", h=self._h, B=B, state=state, first_foot=first_foot, **_named(out, ("U", "theta", "status")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
-    def fleet_update(self, fleet, out, overflow=None, stop_obj=0.05):
+    def fleet_update(self, fleet, out, overflow=None, stop_obj=0.05, recover=None):
         """One sample of a host-driven fleet loop after ``plan_step_batch(..., out=out)`` on the same stream:
         stop rule, stop on a failed solve, state advance, counters and the trajectory row, in one launch
         (lipmpc_fleet_update_batch).  ``fleet`` = dict(state, first_foot, walking int8, last_obj, n_steps, last_status,
         n_overflow, sample int32[1], X_pred [B,k_max+1,5], U_pred [B,k_max,3]); the device-side sample counter
-        advances by one per call."""
+        advances by one per call.
+        ``recover`` = dict(goal [B,2], c_eta [B,n_obs_max,4] or None, delta [B] or None, max_recover int >= 0, recover_run,
+        n_recover int32 [B], recover_margin float64 [B] -- the buffers of ``recover_state``): the same launch with recovery
+        (lipmpc_fleet_recover_update_batch).  A robot whose solve ended INFEASIBLE or MAX_ITER takes a capture step -- foot on
+        p + v / beta, heading turned toward ``goal`` -- instead of stopping, if that point respects every row of ``c_eta`` (the
+        rows the solve was given) and the robot has taken fewer than ``max_recover`` such samples in a row; include/lipmpc.h
+        has the rule.  ``max_recover`` = 0 leaves ``fleet`` exactly as the call without ``recover`` does."""
         B, k_max = fleet["state"].shape[0], fleet["U_pred"].shape[1]
         _check_table(fleet_state(B, k_max), fleet, self.device, "fleet")
         self._check_outputs(out, B)
         _check(overflow, (B,), torch.int32, self.device, "overflow")
+        if recover is not None:
+            names = ("goal", "c_eta", "delta", "max_recover") + RECOVER_STATE
+            if not isinstance(recover, dict) or set(recover) - set(names):
+                raise ValueError(f"recover: a dict with the entries {names}")
+            max_recover = recover.get("max_recover")
+            if not isinstance(max_recover, int) or isinstance(max_recover, bool) or max_recover < 0:
+                raise ValueError("recover['max_recover']: an int >= 0")
+            _check(recover.get("goal"), (B, 2), torch.float64, self.device, "recover['goal']", required=True)
+            _check(recover.get("c_eta"), (B, self.params.n_obs_max, 4), torch.float64, self.device, "recover['c_eta']")
+            _check(recover.get("delta"), (B,), torch.float64, self.device, "recover['delta']")
+            _check_table(recover_state(B), recover, self.device, "recover")
+            _lib.call("lipmpc_fleet_recover_update_batch", h=self._h, B=B, k_max=int(k_max), stop_obj=float(stop_obj),
+                      **_named(fleet, FLEET_STATE), **_named(out, ("U", "theta", "omega", "obj", "status")), overflow=overflow,
+                      **_named(recover, ("goal", "c_eta", "delta")), max_recover=max_recover, **_named(recover, RECOVER_STATE),
+                      hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+            return
         _lib.call("lipmpc_fleet_update_batch", h=self._h, B=B, k_max=int(k_max), stop_obj=float(stop_obj), **_named(fleet, FLEET_STATE),
                   **_named(out, ("U", "theta", "omega", "obj", "status")), overflow=overflow,
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)

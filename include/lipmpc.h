@@ -39,7 +39,8 @@ extern "C" {
                                 *    + lipmpc_map_update_batch; + lipmpc_rrt_plan_grid_batch, LIPMPC_RRT_OUTSIDE_GRID;
                                 *    + lipmpc_grid_field_batch / lipmpc_grid_path_batch;
                                 *    + lipmpc_grid_frontier_field_batch / lipmpc_grid_frontier_path_batch;
-                                *    + lipmpc_lidar_c_eta_split_batch / lipmpc_lidar_grid_c_eta_split_batch */
+                                *    + lipmpc_lidar_c_eta_split_batch / lipmpc_lidar_grid_c_eta_split_batch;
+                                *    + lipmpc_fleet_recover_update_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -257,6 +258,56 @@ int lipmpc_fleet_update_batch(lipmpc_handle* h, int64_t B, int32_t k_max, double
                               double* X_pred, double* U_pred,
                               const double* U, const double* theta, const double* omega, const double* obj,
                               const int32_t* status, const int32_t* overflow, void* hip_stream);
+
+/* lipmpc_fleet_update_batch WITH RECOVERY (backward-compatible addition): a failed solve need not end the robot's run.  A robot
+ * whose solve failed takes one CAPTURE STEP -- the foot goes on the instantaneous capture point cp = p + v / beta,
+ * beta = sqrt(g / h_com) -- and tries the solve again on the next sample.  Why that step: cp is a fixed point of the LIP step
+ * (cp+ = cp), the velocity falls by v+ = (ch - sh) v = e^(-beta dt) v, and the CoM moves on the straight segment from p towards
+ * cp without passing it.  The sample's LDCBF rows are half-planes that hold p, so the whole motion respects row j if and only
+ * if cp does: one dot product per row decides exactly whether the manoeuvre is safe against everything the sample sensed.
+ * One lane per robot, *sample read on the device and advanced by the call, no allocation and no host synchronisation (the call
+ * can be captured in a graph); every refusal is decided on the host before anything is enqueued.
+ *  every argument of lipmpc_fleet_update_batch, and
+ *  goal           [B,2]  the goal the sample's solve was given
+ *  c_eta          [B,n_obs_max,4] or NULL (no rows): the rows the sample's solve was given (c_x, c_y, eta_x, eta_y), neighbour rows
+ *                 included; n_obs_max is the handle's; eta = (0,0) marks an empty slot
+ *  delta          [B] or NULL (= 0)
+ *  max_recover    >= 0: the most consecutive recovery samples a robot may take; 0 = lipmpc_fleet_update_batch
+ *  recover_run    [B] int32, in/out: consecutive recovery samples so far
+ *  n_recover      [B] int32, in/out: recovery samples in all
+ *  recover_margin [B] double, out
+ * PER ROBOT the rule of lipmpc_fleet_update_batch word for word -- stop rule, overflow, last_status, counters, the U_pred / X_pred
+ * rows -- except where walking would become 0 because of the status:
+ *   solved (SOLVED, UNCERTIFIED): as there, and recover_run = 0 (left as it is with max_recover = 0).
+ *   otherwise the safety test is EVALUATED if the robot is walking after the stop rule, the status (SENSOR_OVERFLOW where
+ *     overflow[b] != 0) is INFEASIBLE or MAX_ITER, recover_run < max_recover and the four LIP state words (p_x, v_x, p_y, v_y)
+ *     are finite.  DEGENERATE (NaN rows) and SENSOR_OVERFLOW (the truncated rows cannot vouch for anything) never recover.
+ *   THE SAFETY TEST, IEEE double, no contraction, evaluated as written: cp = (p_x + v_x / beta, p_y + v_y / beta);
+ *     margin = min over the slots j with eta_j != (0,0) of (eta_jx * (cp_x - c_jx) + eta_jy * (cp_y - c_jy)) - delta,
+ *     +inf with no such slot or a NULL c_eta, -inf if the margin of any such slot is NaN (a NaN in a used row fails the test: an
+ *     evaluated margin is never NaN).  It passes iff margin >= 0.
+ *   recover_margin[b] = that margin if the test was evaluated, NaN otherwise (written for every robot on every sample < k_max).
+ *   RECOVER, if the test was evaluated and passed: omega_r = min(max(atan2(g_y - p_y, g_x - p_x) - theta, -omega_max), omega_max)
+ *     (the step's own heading rule at k = 0, no wrapping, HumanoidMpc.py:137-160: the recovery turns the way the next solve
+ *     will; omega_max is the handle's); state <- (A_l x + B_l cp, theta + omega_r * sampling_time); first_foot <- -first_foot;
+ *     recover_run += 1; n_recover += 1; walking stays 1; last_obj and n_steps (solved samples) are unchanged; last_status keeps
+ *     the failed status until a later solve succeeds; the U_pred row is (cp_x, cp_y, omega_r), the X_pred row the new state.
+ *     The failed solve's U / theta / omega / obj are not read for that robot.
+ *   in every other case: as lipmpc_fleet_update_batch, final (recover_run and n_recover are left as they are).
+ * With max_recover = 0 every buffer of lipmpc_fleet_update_batch is left exactly as that call leaves it; the counters are
+ * unchanged and recover_margin is NaN.
+ * WARM START: nothing to do here.  A step that ends INFEASIBLE or MAX_ITER has already written word 0 = 0.0 into the robot's
+ * warm-start record (lipmpc_set_warm_start), so the solve after a recovery sample starts cold; this call does not touch records.
+ * Refusals (LIPMPC_E_ARG): max_recover < 0, a null goal / recover_run / n_recover / recover_margin, and whatever
+ * lipmpc_fleet_update_batch refuses.  B = 0 enqueues nothing.  Restated in numpy by tests/recover_oracle.py. */
+int lipmpc_fleet_recover_update_batch(lipmpc_handle* h, int64_t B, int32_t k_max, double stop_obj,
+                                      double* state, int8_t* first_foot, int8_t* walking, double* last_obj,
+                                      int32_t* n_steps, int32_t* last_status, int32_t* n_overflow, int32_t* sample,
+                                      double* X_pred, double* U_pred,
+                                      const double* U, const double* theta, const double* omega, const double* obj,
+                                      const int32_t* status, const int32_t* overflow,
+                                      const double* goal, const double* c_eta, const double* delta, int32_t max_recover,
+                                      int32_t* recover_run, int32_t* n_recover, double* recover_margin, void* hip_stream);
 
 /* Closed loop on the device: HumanoidMPC.run_simulation (HumanoidMpc.py:345-459) for B robots, one group of
  * lanes per robot for the whole run, no host round trip.  Per sample k < k_max: stop when the previous
