@@ -40,10 +40,11 @@ def in_solid_cell(position, occ, origin, cell):
     return c is not None and 0 <= c[0] < W and 0 <= c[1] < H and bool(occ[c[0], c[1]])
 
 
-def grid_hits(position, occ, origin, cell, lidar_range, table):
+def grid_hits(position, occ, origin, cell, lidar_range, table, counts=False):
     """(hits [R,2], valid [R]) of one robot on the grid ``occ`` [W,H] (nonzero = solid): per ray the point where it enters the
     first solid cell -- on the boundary crossed, the other coordinate that of x0 + t d --, kept if strictly closer than
-    lidar_range.  A robot in a solid cell has no scan (all invalid)."""
+    lidar_range.  A robot in a solid cell has no scan (all invalid).  ``counts``: a third value, dict(ties = steps of live rays
+    taken with t_x == t_y, t0 = live rays whose first crossing has t == 0); the first two are the same either way."""
     occ = np.asarray(occ) != 0
     W, H = occ.shape
     R = len(table)
@@ -51,9 +52,10 @@ def grid_hits(position, occ, origin, cell, lidar_range, table):
     ox, oy, dx, dy = (np.float64(v) for v in (origin[0], origin[1], cell[0], cell[1]))
     rng = np.float64(lidar_range)
     hits, valid = np.zeros((R, 2)), np.zeros(R, bool)
+    n = dict(ties=0, t0=0)
     c0 = robot_cell(position, origin, cell)
     if c0 is None or in_solid_cell(position, occ, origin, cell):
-        return hits, valid
+        return (hits, valid, n) if counts else (hits, valid)
     nx, ny = window_half(lidar_range, cell)
     table = np.asarray(table, np.float64)
     with np.errstate(all="ignore"):
@@ -68,9 +70,13 @@ def grid_hits(position, occ, origin, cell, lidar_range, table):
         t_hit = np.zeros(R)
         b_hit, x_hit = np.zeros(R), np.zeros(R, bool)     # the boundary the solid cell was entered through, and its axis
         found = np.zeros(R, bool)
+        first = True
         while live.any():
             xs = tx <= ty                                   # a tie goes to x
             t = np.where(xs, tx, ty)
+            n["ties"] += int((live & (tx == ty) & np.isfinite(tx)).sum())
+            n["t0"] += int((live & (t == 0.0)).sum()) if first else 0
+            first = False
             bnd = np.where(xs, ox + (ci + upx).astype(np.float64) * dx, oy + (cj + upy).astype(np.float64) * dy)      # the one being crossed
             ci = np.where(live & xs, ci + 2 * upx - 1, ci)
             cj = np.where(live & ~xs, cj + 2 * upy - 1, cj)
@@ -90,7 +96,7 @@ def grid_hits(position, occ, origin, cell, lidar_range, table):
         dist = np.sqrt((qx - x0) * (qx - x0) + (qy - y0) * (qy - y0))
     valid = found & (dist < rng)
     hits[valid, 0], hits[valid, 1] = qx[valid], qy[valid]
-    return hits, valid
+    return (hits, valid, n) if counts else (hits, valid)
 
 
 def fixture(seed=0, n_robots=60):

@@ -14,11 +14,12 @@ def same_ring(a, b):
     return np.array_equal(np.roll(b, -k, axis=0), a)
 
 
-def check_hits(g, pos, occ_of, origin, cell, lidar_range, table, noise):
-    """Device hits == oracle hits (+ noise), bit for bit; a robot in a solid cell: no reading, overflow, nothing inferred."""
+def check_hits(g, pos, occ_of, origin, cell, lidar_range, table, noise, scan_of=None):
+    """Device hits == oracle hits (+ noise), bit for bit; a robot in a solid cell: no reading, overflow, nothing inferred.
+    ``scan_of(b)``: robot b's (hits, valid) by G.grid_hits on these very inputs, where a caller has computed them already."""
     n_hits = n_solid = 0
     for b in range(len(pos)):
-        hits, valid = G.grid_hits(pos[b], occ_of(b), origin, cell, lidar_range, table)
+        hits, valid = G.grid_hits(pos[b], occ_of(b), origin, cell, lidar_range, table) if scan_of is None else scan_of(b)
         if noise is not None:
             hits = hits + np.where(valid[:, None], noise[b], 0.0)
         gv = ~np.isnan(g["hits"][b, :, 0])

@@ -33,9 +33,11 @@ def window_fits(lidar_range, depth, cell):
     return (2 * nx + 1) * (2 * ny + 1) <= WINDOW_CELLS
 
 
-def robot_marks(position, hits, origin, cell, lidar_range, table, depth):
+def robot_marks(position, hits, origin, cell, lidar_range, table, depth, counts=False):
     """One robot's scan as window bitmaps: (passed [ww,wh], hit [ww,wh], (wi0, wj0)) with window cell (li, lj) = grid cell
-    (wi0 + li, wj0 + lj), or None when the robot cannot be given a cell.  ``hits`` [R,2], NaN = no reading."""
+    (wi0 + li, wj0 + lj), or None when the robot cannot be given a cell.  ``hits`` [R,2], NaN = no reading.  ``counts``: a fourth
+    value, dict(ties = steps of live rays taken with t_x == t_y, t0 = live rays whose first crossing has t == 0); the first three
+    are the same either way."""
     c0 = G.robot_cell(position, origin, cell)
     if c0 is None:
         return None
@@ -72,9 +74,13 @@ def robot_marks(position, hits, origin, cell, lidar_range, table, depth):
         own = live & ~((hli == nx) & (hlj == ny))
         if own.any():
             passed[nx, ny] = True
+        n, first = dict(ties=0, t0=0), True
         while live.any():
             xs = tx <= ty                                   # a tie goes to x
             t = np.where(xs, tx, ty)
+            n["ties"] += int((live & (tx == ty) & np.isfinite(tx)).sum())
+            n["t0"] += int((live & (t == 0.0)).sum()) if first else 0
+            first = False
             ci = np.where(live & xs, ci + 2 * upx - 1, ci)
             cj = np.where(live & ~xs, cj + 2 * upy - 1, cj)
             tnx = ((ox + (ci + upx).astype(np.float64) * dx) - x0) * ivx
@@ -86,7 +92,7 @@ def robot_marks(position, hits, origin, cell, lidar_range, table, depth):
             passed[ri[go], rj[go]] = True
             live = go
         hit[hli[has_hit], hlj[has_hit]] = True
-    return passed, hit, (c0[0] - nx, c0[1] - ny)
+    return (passed, hit, (c0[0] - nx, c0[1] - ny)) + ((n,) if counts else ())
 
 
 def robot_delta(position, hits, W, H, origin, cell, lidar_range, table, depth, w_hit, w_miss):
