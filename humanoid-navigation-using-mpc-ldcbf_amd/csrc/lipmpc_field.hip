@@ -10,6 +10,8 @@
 //                            frontier = unblocked with enough unknown neighbours, then the same relaxation from EVERY frontier
 //                            cell at once: the cost-to-go to the nearest frontier.
 //   frontier_path_kernel     grid_path_kernel's snap, descent and string pulling, ending at the first frontier cell reached.
+//   frontier_assign_*_kernel ONE workgroup for a fleet on a shared map (lipmpc_grid_frontier_assign_batch): round by round the
+//                            relaxation from what is left of the frontier, the nearest robot's claim and path, its disc cleared.
 // Everything the two kernels compare is an integer but the two floors that name a cell; the cell centres are one multiply and
 // one add, contraction off.  tests/field_oracle.py restates both contracts (Dijkstra) and the GPU tests hold every output to it
 // bit for bit.
@@ -448,6 +450,246 @@ __global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, 
   done(LIPMPC_RRT_FOUND, n, cost, last_cell);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// the coordinated claim (lipmpc_grid_frontier_assign_batch): ONE workgroup for the whole call, a sequential round per claim.
+// Its field is relaxed anew every round, in LDS or in `work`, so the path functions above come once more in a form that takes
+// whatever pointer the field lives behind and reads it with the sweeps' own loads: the same rules, word for word.
+template <typename FieldPtr> __device__ __forceinline__ bool los_in(FieldPtr fld, int H, int a, int b) {
+  if (b < a) { const int t = a; a = b; b = t; }
+  const int ai = a / H, aj = a - ai * H, bi = b / H, bj = b - bi * H;
+  const int di = bi - ai, dj = bj - aj;
+  const int m = max(abs(di), abs(dj)), two_m = 2 * m;
+  if (m == 0) return ld(fld + a) != INF;
+  int qi = 0, ri = m, qj = 0, rj = m;
+  for (int k = 0; k <= m; ++k) {
+    if (ld(fld + ((ai + qi) * H + aj + qj)) == INF) return false;
+    ri += 2 * di; rj += 2 * dj;
+    if (ri >= two_m) { ri -= two_m; ++qi; } else if (ri < 0) { ri += two_m; --qi; }
+    if (rj >= two_m) { rj -= two_m; ++qj; } else if (rj < 0) { rj += two_m; --qj; }
+  }
+  return true;
+}
+
+template <typename FieldPtr> __device__ __forceinline__ int descend_in(FieldPtr fld, int W, int H, int c) {
+  const int i = c / H, j = c - i * H;
+  const uint32_t fc = ld(fld + c);
+  // (not unrolled: eight neighbours' conditions at once fill the scalar file, and one lane walks)
+#pragma unroll 1
+  for (int di = -1; di <= 1; ++di)
+#pragma unroll 1
+    for (int dj = -1; dj <= 1; ++dj) {
+      if ((di == 0 && dj == 0) || (unsigned)(i + di) >= (unsigned)W || (unsigned)(j + dj) >= (unsigned)H) continue;
+      const int n = c + di * H + dj;
+      const uint32_t v = ld(fld + n);
+      if (v == INF) continue;
+      const bool diag = di != 0 && dj != 0;
+      if (diag && (ld(fld + (c + di * H)) == INF || ld(fld + (c + dj)) == INF)) continue;
+      if (v < fc && fc - v == (diag ? DIAGONAL : AXIAL)) return n;
+    }
+  return -1;
+}
+
+template <typename FieldPtr> __device__ __forceinline__ int snap_in(FieldPtr fld, int W, int H, int si, int sj, int r_inflate) {
+  const int n = r_inflate + 1;
+  uint64_t best = ~0ull;
+  int at = -1;
+  for (int i = max(si - n, 0); i <= min(si + n, W - 1); ++i)
+    for (int j = max(sj - n, 0); j <= min(sj + n, H - 1); ++j) {
+      const uint32_t v = ld(fld + (i * H + j));
+      if (v == INF) continue;
+      const uint64_t key = ((uint64_t)(uint32_t)((i - si) * (i - si) + (j - sj) * (j - sj)) << 32) | v;
+      if (key < best) { best = key; at = i * H + j; }
+    }
+  return at;
+}
+
+template <typename FieldPtr>
+__device__ __forceinline__ int walk_in(FieldPtr fld, int W, int H, int s, int max_seg, double ox, double oy, double dx, double dy, double* sg,
+                              int& last_cell) {
+  int count = 0;
+  auto emit = [&](int c) {
+    if (sg) centre(c, H, ox, oy, dx, dy, sg + 2 * count);
+    ++count;
+  };
+  last_cell = s;
+  if (ld(fld + s) != 0) {
+    int a = s, prev = s, cur = descend_in(fld, W, H, s);
+    while (cur >= 0) {
+      const bool last = ld(fld + cur) == 0;
+      if (!los_in(fld, H, a, cur) || ld(fld + a) - ld(fld + cur) >= (uint32_t)max_seg) {
+        if (prev != a) { emit(prev); a = prev; continue; }
+        if (last) break;
+        emit(cur); a = cur;
+      }
+      if (last) break;
+      prev = cur;
+      cur = descend_in(fld, W, H, cur);
+    }
+    if (cur < 0) return -1;
+    last_cell = cur;
+  }
+  return count + 1;
+}
+
+// LDS of the assign kernels: two bitmaps (impassable, sources), then ASSIGN_WORDS words -- the winner's key (64 bits: 2
+// bitmap_words() is even, so it is 8-byte aligned), the winner's target cell (a word pair), and what only the winner's lane needs,
+// the placement's four doubles and the five pointers of its output rows: held in scalar registers through every loop of the
+// rounds they would overfill that file (the bar is no spill of either kind); the lane that walks reads them from here -- then
+// the field (8-byte aligned), or bitmaps and words alone with the field in `work`
+constexpr int ASSIGN_WORDS = 22;
+__host__ __device__ inline int64_t assign_bitmap_words(int64_t ncells) { return 2 * bitmap_words(ncells) + ASSIGN_WORDS; }
+__host__ __device__ inline int64_t assign_lds_bytes(int64_t ncells, bool in_lds) {
+  return 4 * (assign_bitmap_words(ncells) + (in_lds ? ncells : 0));
+}
+
+inline bool assign_fits_lds(int64_t ncells) { return assign_lds_bytes(ncells, true) + LDS_SLACK <= LDS_LIMIT; }
+
+// where a robot whose start cell is (si, sj) enters the round's field: that cell if finite there, else the snap; -1 if neither
+template <typename FieldPtr> __device__ __forceinline__ int claim_cell(FieldPtr fld, int W, int H, int cell, int r_inflate) {
+  if (ld(fld + cell) != INF) return cell;
+  const int si = cell / H;
+  return snap_in(fld, W, H, si, cell - si * H, r_inflate);
+}
+
+// The whole call.  `fld`: the round's field ([W*H], LDS or `work`); `bm`: the two bitmaps and the ASSIGN_WORDS, apart from fld.
+// While the rounds run, claim_round[b] of a robot of U holds -2 - (its start cell): the floor rule's two divisions are done once
+// and a round reads one word per robot.  It is read back after the winner's lane wrote it: every barrier orders the workgroup's
+// global accesses.
+template <typename FieldPtr>
+__device__ __forceinline__ void assign_body(FieldPtr fld, uint32_t* bm, int64_t B, int W, int H, double ox, double oy, double dx, double dy,
+                                            const uint8_t* __restrict__ frontier, const uint32_t* __restrict__ field,
+                                            const double* __restrict__ start, const int8_t* __restrict__ may_claim, int r_inflate,
+                                            int r_claim, int max_claims, int max_seg, int S_max, double* __restrict__ sub_goals,
+                                            int32_t* __restrict__ n_sub, int32_t* __restrict__ status, double* __restrict__ path_cost,
+                                            int32_t* __restrict__ target_cell, int32_t* claim_round, int32_t* __restrict__ n_claims) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  uint32_t *blk = bm, *src = bm + words, *tgt = bm + 2 * words + 2;
+  unsigned long long* key = (unsigned long long*)(bm + 2 * words);
+  uint32_t* parked = bm + 2 * words + 4;                  // 64-bit values as word pairs
+  auto park = [&](int slot, unsigned long long v) { parked[2 * slot] = (uint32_t)v; parked[2 * slot + 1] = (uint32_t)(v >> 32); };
+  auto unpark = [&](int slot) { return ((unsigned long long)parked[2 * slot + 1] << 32) | parked[2 * slot]; };
+
+  // U_0, each robot with its start cell
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+    const int sb = status[b];
+    int si = 0, sj = 0, v = -1;
+    if (max_claims > 0 && (sb == LIPMPC_RRT_FOUND || sb == LIPMPC_RRT_PATH_OVERFLOW) && (!may_claim || may_claim[b]) &&
+        cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
+      v = -2 - (si * H + sj);
+    claim_round[b] = v;
+  }
+  int claims = 0;
+  if (max_claims > 0) {
+    // impassable = the given field is INF; sources = the given frontier, on passable cells
+    for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+      const int c = c0 + lane;
+      const bool pass = c < ncells && field[c] != INF;
+      const uint64_t mb = __ballot(c < ncells && !pass), ms = __ballot(pass && frontier[c] != 0);
+      if (lane == 0) {
+        blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32);
+        src[c0 >> 5] = (uint32_t)ms; src[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      }
+    }
+    if (tid < 2) { blk[words - 2 + tid] = 0; src[words - 2 + tid] = 0; }
+    if (tid == 0) {
+      *key = ~0ull;
+      park(0, __double_as_longlong(ox)); park(1, __double_as_longlong(oy)); park(2, __double_as_longlong(dx));
+      park(3, __double_as_longlong(dy));
+      park(4, (unsigned long long)sub_goals); park(5, (unsigned long long)n_sub); park(6, (unsigned long long)status);
+      park(7, (unsigned long long)path_cost); park(8, (unsigned long long)target_cell);
+    }
+    __syncthreads();
+
+    for (int k = 0;; ++k) {
+      // field_k: 0 on what is left of the sources, relaxed to the fixed point
+      int any = 0;
+      for (int c = tid; c < ncells; c += FIELD_THREADS) {
+        const bool s = bit_of(src, c);
+        st(fld + c, s ? 0u : INF);
+        any |= s;
+      }
+      if (!__syncthreads_or(any)) break;
+      relax(fld, blk, W, H);
+      // the candidates of U_k, and the least (cost, b) among them
+      unsigned long long mine = ~0ull;
+      int eligible = 0;
+      for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+        const int v = claim_round[b];
+        if (v > -2) continue;
+        ++eligible;
+        const int s = claim_cell(fld, W, H, -2 - v, r_inflate);
+        if (s >= 0) mine = min(mine, ((unsigned long long)ld(fld + s) << 32) | (unsigned long long)b);
+      }
+      for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
+      if (lane == 0 && mine != ~0ull) atomicMin(key, mine);
+      __syncthreads();
+      const unsigned long long win = *key;
+      if (win == ~0ull) break;                            // no candidate: the rounds end
+      const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
+      if (tid == 0) {
+        // one lane walks the winner's path, twice: count, then -- if the sub-goals fit -- write (rows past n_sub stay untouched)
+        const int s = claim_cell(fld, W, H, -2 - claim_round[wb], r_inflate);
+        const double wox = __longlong_as_double(unpark(0)), woy = __longlong_as_double(unpark(1));
+        const double wdx = __longlong_as_double(unpark(2)), wdy = __longlong_as_double(unpark(3));
+        double* sg = (double*)unpark(4) + wb * (int64_t)S_max * 2;
+        int last_cell = s, n = 0;
+        for (int pass = 0; pass < 2 && n >= 0 && n <= S_max; ++pass)
+          n = walk_in(fld, W, H, s, max_seg, wox, woy, wdx, wdy, pass ? sg : nullptr, last_cell);
+        if (n > 0) {
+          if (n <= S_max) centre(last_cell, H, wox, woy, wdx, wdy, sg + 2 * (n - 1));
+          ((int32_t*)unpark(6))[wb] = n <= S_max ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+          ((int32_t*)unpark(5))[wb] = n <= S_max ? n : 0;
+          ((double*)unpark(7))[wb] = (double)ld(fld + s) / 5.0;
+          ((int32_t*)unpark(8))[wb] = last_cell;
+          claim_round[wb] = k;
+        }
+        *tgt = n > 0 ? (uint32_t)last_cell : INF;         // (a fixed point always has a descent: INF cannot happen)
+      }
+      if ((wb & (FIELD_THREADS - 1)) == tid) --eligible;
+      const int more = __syncthreads_or(eligible);
+      const uint32_t t = *tgt;
+      if (tid == 0) *key = ~0ull;                         // (everybody has read it; the next minimum comes two barriers on)
+      if (t == INF) break;
+      ++claims;
+      if (!more || k + 1 >= max_claims) break;            // U or the allowance is used up
+      // S_{k+1}: the sources outside the winner's disc, clipped to the grid
+      const int ti = (int)t / H, tj = (int)t - ti * H, r2 = r_claim * r_claim;
+      const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
+      for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+        const int i = c / H, j = c - i * H;
+        if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+      }
+      __syncthreads();
+    }
+    // the followers: still in U
+    __syncthreads();
+    for (int64_t b = tid; b < B; b += FIELD_THREADS)
+      if (claim_round[b] < -1) claim_round[b] = -1;
+  }
+  if (tid == 0) n_claims[0] = claims;
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_lds_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const double* __restrict__ start, const int8_t* __restrict__ may_claim, int r_inflate, int r_claim,
+    int max_claims, int max_seg, int S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+    int32_t* claim_round, int32_t* __restrict__ n_claims) {
+  extern __shared__ uint32_t field_lds[];
+  assign_body(field_lds + assign_bitmap_words((int64_t)W * H), field_lds, B, W, H, ox, oy, dx, dy, frontier, field, start, may_claim,
+              r_inflate, r_claim, max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_global_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const double* __restrict__ start, const int8_t* __restrict__ may_claim, int r_inflate, int r_claim,
+    int max_claims, int max_seg, int S_max, uint32_t* work, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+    int32_t* target_cell, int32_t* claim_round, int32_t* __restrict__ n_claims) {
+  extern __shared__ uint32_t field_lds[];
+  assign_body(work, field_lds, B, W, H, ox, oy, dx, dy, frontier, field, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max,
+              sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims);
+}
+
 // what both entry points refuse about the grid: E_ARG, then the caps
 int grid_refusal(int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate) {
   if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
@@ -540,5 +782,36 @@ extern "C" int lipmpc_grid_frontier_path_batch(int device, int64_t B, int64_t F,
   hipLaunchKernelGGL(frontier_path_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
                      (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, field,
                      n_frontier, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                                 const uint8_t* frontier, const uint32_t* field, const double* start,
+                                                 const int8_t* may_claim, int32_t r_inflate, int32_t r_claim, int32_t max_claims,
+                                                 int32_t max_seg, int32_t S_max, uint32_t* work, double* sub_goals, int32_t* n_sub,
+                                                 int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                                 int32_t* n_claims, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      !frontier || !field || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round || !n_claims)
+    return LIPMPC_E_ARG;
+  if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t ncells = (int64_t)W * H;
+  const bool in_lds = assign_fits_lds(ncells);
+  const size_t lds = (size_t)assign_lds_bytes(ncells, in_lds);
+  if (in_lds) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+      return LIPMPC_E_HIP;
+    hipLaunchKernelGGL(frontier_assign_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0], cell[1],
+                       frontier, field, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max, sub_goals, n_sub, status,
+                       path_cost, target_cell, claim_round, n_claims);
+  } else {
+    hipLaunchKernelGGL(frontier_assign_global_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
+                       cell[1], frontier, field, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max, work, sub_goals,
+                       n_sub, status, path_cost, target_cell, claim_round, n_claims);
+  }
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

@@ -594,15 +594,21 @@ class UnknownEnvFleet:
             the stop rule stopped and robots parked earlier (a robot stopped by a failed solve stays stopped, as everywhere);
           - a robot whose plan is not FOUND is parked (walking = 0; it keeps its working goal).
         After the last sample one closing plan on the final map and positions parks likewise and sets no goal; it is not counted.
-        The model's limits: every robot goes to ITS nearest frontier (no task assignment), and the walker cannot turn on the
-        spot while walking -- a working goal that jumps behind a robot can make its solve INFEASIBLE.  That ends the robot's run
-        only in a fleet without ``recover``: with it the robot takes a capture step and solves again (EXPLORATION_RECOVER.md).
+        With a ``CoordinatedFrontierPlanner`` as ``explorer`` the robots claim frontier targets apart in every replan: the robots
+        that may claim are those whose last_status is SOLVED or UNCERTIFIED -- a robot stopped for good by a failed solve must
+        never hold a frontier, or the fleet never finishes -- and a robot in a capture step (``recover``) is a follower for that
+        replan: it keeps its nearest-frontier plan.  The result then gains n_claims [n_replans] (device tensor: the claims of
+        every replan; the closing plan's are not counted).  With any other explorer nothing changes.
+        The model's limits: with a plain ``FrontierPlanner`` every robot goes to ITS nearest frontier (no task assignment:
+        ``CoordinatedFrontierPlanner`` adds it), and the walker cannot turn on the spot while walking -- a working goal that
+        jumps behind a robot can make its solve INFEASIBLE.  That ends the robot's run only in a fleet without ``recover``: with
+        it the robot takes a capture step and solves again (EXPLORATION_RECOVER.md).
         Returns what ``run`` returns, plus n_replans (int), explore_status [B] (RRT_*) of the closing plan, working_goal [B,2],
         walking [B] (int8), n_frontier and known_free [n_replans,F] (device tensors: per replan the frontier cells, and the cells
         with evidence <= -t_free, of every map), and done [B] (bool): not walking, not stopped by a failed solve, and the closing
         plan said RRT_NO_PATH -- for the robot nothing is left to explore.  The tensors are the object's or fresh ones; the
         next run of the same shape overwrites the former."""
-        from .planner import RRT_FOUND, RRT_NO_PATH
+        from .planner import RRT_FOUND, RRT_NO_PATH, CoordinatedFrontierPlanner
         from .solver import STATUS_SOLVED, STATUS_UNCERTIFIED
         mapper = self.mapper
         if mapper is None:
@@ -620,6 +626,8 @@ class UnknownEnvFleet:
         n_frontier = torch.zeros((rows, F), dtype=torch.int32, device=dev)
         known_free = torch.zeros((rows, F), dtype=torch.int64, device=dev)
         plan_out = [None]                                    # the plan's buffers: made by the first plan, reused by every later one
+        coordinated = isinstance(explorer, CoordinatedFrontierPlanner)
+        n_claims = torch.zeros((rows,), dtype=torch.int32, device=dev) if coordinated else None
         info = dict(n_replans=0)
 
         def replan(k, pl, closing=False):
@@ -631,9 +639,10 @@ class UnknownEnvFleet:
                 self.sensor.sense(fl["state"], None, out=pl["sen"], c_eta=True, rings=False, schedule=pl["sched"])
                 mapper.update(fl["state"], pl["sen"]["hits"])
             pos = fl["state"][:, (0, 2)].contiguous()
-            plan = plan_out[0] = explorer.plan(mapper, pos, S_max=64 if S_max is None else S_max, out=plan_out[0])
-            found = plan["status"] == RRT_FOUND
             solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
+            claim = dict(may_claim=solved.to(torch.int8)) if coordinated else {}
+            plan = plan_out[0] = explorer.plan(mapper, pos, S_max=64 if S_max is None else S_max, out=plan_out[0], **claim)
+            found = plan["status"] == RRT_FOUND
             if not closing:
                 resume = (fl["walking"] == 0) & solved & found
                 fl["walking"].masked_fill_(resume, 1)
@@ -642,6 +651,8 @@ class UnknownEnvFleet:
                 working.copy_(torch.where(found[:, None], picked, working))
                 n_frontier[info["n_replans"]].copy_(plan["n_frontier"])
                 known_free[info["n_replans"]].copy_((ev <= -t_free).sum((1, 2)))
+                if coordinated:
+                    n_claims[info["n_replans"]].copy_(plan["n_claims"][0])
                 info["n_replans"] += 1
             fl["walking"].masked_fill_(~found, 0)
             info["explore_status"] = plan["status"]
@@ -652,6 +663,8 @@ class UnknownEnvFleet:
         solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
         res.update(info, working_goal=self._plan["goal"], walking=fl["walking"], n_frontier=n_frontier, known_free=known_free,
                    done=(fl["walking"] == 0) & solved & (info["explore_status"] == RRT_NO_PATH))
+        if coordinated:
+            res["n_claims"] = n_claims
         return res
 
 

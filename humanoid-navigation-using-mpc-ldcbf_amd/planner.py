@@ -10,6 +10,9 @@
 ``FrontierPlanner`` needs no goal: on the evidence grid an ``OccupancyMapper`` builds it finds the frontier of the known free
 space, the cost-to-go to the nearest frontier cell (``lipmpc_grid_frontier_field_batch``) and sub-goals down it
 (``lipmpc_grid_frontier_path_batch``).
+
+``CoordinatedFrontierPlanner`` is ``FrontierPlanner`` for a fleet on one shared map: after the two calls the robots claim frontier
+targets apart, nearest claim first (``lipmpc_grid_frontier_assign_batch``).
 """
 from __future__ import annotations
 
@@ -44,6 +47,14 @@ def frontier_outputs(B, F, W, H, S_max):
     return {"sub_goals": (f64, (B, S_max, 2), True), "n_sub": (i32, (B,), True), "status": (i32, (B,), True), "path_cost": (f64, (B,), True),
             "target": (f64, (B, 2), True), "target_cell": (i32, (B,), True), "field": (torch.uint32, (F, W, H), True),
             "frontier": (torch.uint8, (F, W, H), True), "n_frontier": (i32, (F,), True)}
+
+
+def assign_outputs(B, W, H, S_max):
+    """Outputs of CoordinatedFrontierPlanner.plan, in the order it returns them: FrontierPlanner.plan's on a shared map, the claim
+    rounds, and the call's scratch field (``work``: it lives with the outputs so that a captured graph replays into one memory)."""
+    i32 = torch.int32
+    return dict(frontier_outputs(B, 1, W, H, S_max), claim_round=(i32, (B,), True), n_claims=(i32, (1,), True),
+                work=(torch.uint32, (W, H), True))
 
 
 def plan_outputs(B, S_max, max_cells, n_samples):
@@ -314,10 +325,11 @@ class FrontierPlanner:
     field serves every robot.  ``r_inflate``: free cells within this many cells of a solid one are blocked, 0..16 (unknown cells
     are impassable but not inflated).  ``t_free`` / ``t_occ``: None = the mapper's ``w_miss`` / ``w_hit``.  ``max_seg``: as
     ``GridFieldPlanner``'s.
-    The model's limits: every robot heads for ITS nearest frontier -- there is no task assignment, two robots side by side pick
-    the same cell -- and n_frontier == 0 (status RRT_NO_PATH for everybody) is how "nothing left to explore" is told.  The
-    walker that follows these goals cannot turn on the spot while walking: a goal that jumps behind it can make its solve
-    INFEASIBLE, which costs the robot a capture step in a fleet with ``recover`` and its run in one without."""
+    The model's limits: every robot heads for ITS nearest frontier -- there is no task assignment here, two robots side by side
+    pick the same cell (``CoordinatedFrontierPlanner`` lets them claim targets apart) -- and n_frontier == 0 (status RRT_NO_PATH
+    for everybody) is how "nothing left to explore" is told.  The walker that follows these goals cannot turn on the spot while
+    walking: a goal that jumps behind it can make its solve INFEASIBLE, which costs the robot a capture step in a fleet with
+    ``recover`` and its run in one without."""
 
     def __init__(self, r_inflate: int = 2, min_unknown: int = 2, t_free: int | None = None, t_occ: int | None = None,
                  max_seg: int | None = None, device: int | None = None):
@@ -381,10 +393,7 @@ class FrontierPlanner:
         PATH_OVERFLOW), target_cell [B] (its index i * H + j, else -1), n_frontier [F], field and frontier [F,W,H].
         ``out``: that dict, to write into (a captured graph replays into the same buffers; nothing is allocated then)."""
         ev, t_free, t_occ, origin, cell = self._map(mapper_or_evidence, origin, cell)
-        if origin is None or cell is None:
-            raise ValueError("an evidence tensor has no placement: give origin and cell")
-        cell = (float(cell), float(cell)) if isinstance(cell, (int, float)) else (float(cell[0]), float(cell[1]))
-        origin = (float(origin[0]), float(origin[1]))
+        origin, cell, org_c, cell_c = self._placement(origin, cell)
         start = torch.as_tensor(start).to(device=self.device, dtype=torch.float64).contiguous()
         if start.dim() != 2 or start.shape[1] != 2:
             raise ValueError("start must be [B,2]")
@@ -399,20 +408,89 @@ class FrontierPlanner:
             _check_table(table, out, self.device, "out")
         if B == 0:
             return out
-        key = (origin, cell)
-        if key not in self._placed:
-            self._placed[key] = (C.c_double * 2)(*origin), (C.c_double * 2)(*cell)
-        org_c, cell_c = self._placed[key]
         self._field(ev, t_free, t_occ, out)
         _lib.call("lipmpc_grid_frontier_path_batch", device=self.device_index, B=B, F=F, W=W, H=H, origin=C.addressof(org_c),
                   cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ, field=out["field"], n_frontier=out["n_frontier"], start=start,
                   r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
-        # the target's centre by the contract's expression (double, one multiply and one add per axis: torch does not contract)
+        self._target(out, origin, cell, H)
+        self.last = out
+        return out
+
+    def _placement(self, origin, cell):
+        """(origin, cell) as pairs of floats, and the two host arrays the C calls read (kept: one pair per placement)."""
+        if origin is None or cell is None:
+            raise ValueError("an evidence tensor has no placement: give origin and cell")
+        cell = (float(cell), float(cell)) if isinstance(cell, (int, float)) else (float(cell[0]), float(cell[1]))
+        origin = (float(origin[0]), float(origin[1]))
+        key = (origin, cell)
+        if key not in self._placed:
+            self._placed[key] = (C.c_double * 2)(*origin), (C.c_double * 2)(*cell)
+        return (origin, cell) + self._placed[key]
+
+    @staticmethod
+    def _target(out, origin, cell, H):
+        """out["target"] from out["target_cell"]: the centre by the contract's expression (double, one multiply and one add per
+        axis: torch does not contract); NaN where the cell is -1."""
         tc = out["target_cell"]
         i, j = torch.div(tc, H, rounding_mode="floor"), torch.remainder(tc, H)
         xy = torch.stack([origin[0] + (i.double() + 0.5) * cell[0], origin[1] + (j.double() + 0.5) * cell[1]], 1)
         out["target"].copy_(torch.where((tc >= 0)[:, None], xy, torch.full_like(xy, float("nan"))))
+
+
+class CoordinatedFrontierPlanner(FrontierPlanner):
+    """``FrontierPlanner`` with task assignment on ONE shared map (include/lipmpc.h, lipmpc_grid_frontier_assign_batch): after
+    the nearest-frontier plan the robots claim frontier targets apart by the greedy rule of coordinated exploration (Burgard et
+    al. 2005, the utility discount taken as "within the claim radius = already taken").  Round by round the robot that is
+    nearest to what is left of the frontier wins (ties to the lower index), gets its path to that cell, and every frontier cell
+    within ``r_claim`` cells (Euclidean, 0..4096) of its target is taken out for the robots that follow; at most ``max_claims``
+    rounds (0..4096).  Everything is an integer comparison: two calls give identical bits.
+    The model's limits: a round is sequential by nature -- one relaxation of the whole map per claim, in one workgroup; robots
+    that are left when the frontier or ``max_claims`` is used up are FOLLOWERS, who keep their plain nearest-frontier plan and so
+    share a target; there is no memory between plans, so a replan may hand a robot another target than the last one."""
+
+    def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
+        self.r_claim, self.max_claims = int(r_claim), int(max_claims)
+        if not 0 <= self.r_claim <= 4096 or not 0 <= self.max_claims <= 4096:
+            raise ValueError(f"invalid claim parameters (r_claim {r_claim}: 0..4096, max_claims {max_claims}: 0..4096)")
+        super().__init__(**frontier_planner_kwargs)
+
+    def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None):
+        """``FrontierPlanner.plan`` on a shared map (anything else: ValueError), then the claims.  ``may_claim`` [B] (bool or
+        integers, None = everybody): the robots that may claim; the others keep their nearest-frontier plan and take nothing
+        from anybody.  Returns the parent's dict -- a robot that claimed has the sub_goals, n_sub, status, path_cost, target_cell
+        and target of its path to the cell it claimed -- plus claim_round [B] (the round a robot won, -1 for everyone else),
+        n_claims [1] and ``work`` [W,H] (the call's scratch).  ``out``: that dict, to write into."""
+        ev = self._map(mapper_or_evidence, origin, cell)[0]
+        if ev.shape[0] != 1:
+            raise ValueError(f"{ev.shape[0]} maps: the robots claim on ONE shared map")
+        start = torch.as_tensor(start).to(device=self.device, dtype=torch.float64).contiguous()
+        if start.dim() != 2 or start.shape[1] != 2:
+            raise ValueError("start must be [B,2]")
+        B, (_, W, H), S_max = start.shape[0], ev.shape, int(S_max)
+        if may_claim is not None:
+            may_claim = torch.as_tensor(may_claim).to(device=self.device)
+            if tuple(may_claim.shape) != (B,):
+                raise ValueError("may_claim must be [B]")
+            may_claim = (may_claim != 0).to(torch.int8)
+        table = assign_outputs(B, W, H, S_max)
+        if out is None:
+            out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost", "target", "target_cell"), self.device, torch.zeros)
+            out.update(_alloc(table, ("field", "frontier", "n_frontier", "work"), self.device))
+            out.update(claim_round=torch.full((B,), -1, dtype=torch.int32, device=self.device),
+                       n_claims=torch.zeros((1,), dtype=torch.int32, device=self.device))
+        else:
+            _check_table(table, out, self.device, "out")
+        super().plan(mapper_or_evidence, start, origin, cell, S_max, out)      # (its table is part of this one)
+        if B == 0:
+            return out
+        origin, cell, org_c, cell_c = self._placement(*self._map(mapper_or_evidence, origin, cell)[3:])
+        _lib.call("lipmpc_grid_frontier_assign_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
+                  cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], start=start, may_claim=may_claim,
+                  r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims, max_seg=self.max_seg, S_max=S_max,
+                  work=out["work"], **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self._target(out, origin, cell, H)
         self.last = out
         return out

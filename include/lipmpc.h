@@ -40,7 +40,7 @@ extern "C" {
                                 *    + lipmpc_grid_field_batch / lipmpc_grid_path_batch;
                                 *    + lipmpc_grid_frontier_field_batch / lipmpc_grid_frontier_path_batch;
                                 *    + lipmpc_lidar_c_eta_split_batch / lipmpc_lidar_grid_c_eta_split_batch;
-                                *    + lipmpc_fleet_recover_update_batch */
+                                *    + lipmpc_fleet_recover_update_batch; + lipmpc_grid_frontier_assign_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -741,6 +741,58 @@ int lipmpc_grid_frontier_path_batch(int device, int64_t B, int64_t F, int32_t W,
                                     const int32_t* n_frontier, const double* start, int32_t r_inflate, int32_t max_seg,
                                     int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                     int32_t* target_cell, void* hip_stream);
+
+/* lipmpc_grid_frontier_assign_batch (backward-compatible addition): COORDINATED exploration.  The path call sends every robot
+ * to ITS nearest frontier cell, so robots side by side pick the same one.  This call runs after it on ONE shared map and lets
+ * the robots claim frontier targets apart: the classic greedy rule (Burgard et al. 2005) with the utility discount taken as
+ * "within r_claim cells of a claimed target = already taken", stated in integers.  One workgroup does the whole call.
+ *  B robots, one map (F = 1);  W, H, origin, cell, r_inflate, max_seg, S_max, start [B,2]: what the path call was given
+ *  frontier [W,H] uint8, field [W,H] uint32: the outputs of lipmpc_grid_frontier_field_batch (F = 1); both are only read
+ *  may_claim [B] int8 or NULL (= every robot may);  r_claim 0..4096, in cells;  max_claims 0..4096
+ *  work [W,H] uint32: scratch, contents arbitrary on entry and on return; it overlaps nothing else
+ *  sub_goals, n_sub, status, path_cost, target_cell: the outputs of lipmpc_grid_frontier_path_batch (F = 1) for the same map and
+ *    start -- read, and rewritten for the robots that claim
+ *  claim_round [B] int32, n_claims [1] int32: written whole
+ * THE RULE:
+ *  - passable(c) <=> the given field[c] != LIPMPC_FIELD_INF.  Moves go between passable cells at the costs 5 / 7 with the
+ *    no-corner-cut rule of lipmpc_grid_field_batch.  For every cell that any subset of the frontier can reach this IS "unblocked"
+ *    of the frontier field call: a cell that is unblocked and INF there reaches no frontier cell at all.
+ *  - S_0 = the (passable) cells with frontier[c] != 0.  U_0 = the robots b with may_claim[b] != 0 and status[b] FOUND or
+ *    PATH_OVERFLOW.
+ *  - round k = 0, 1, ... runs while k < max_claims, U_k is not empty and S_k is not empty:
+ *      field_k = the least cost to any cell of S_k, relaxed by the call itself (round 0 included; the given field is read for
+ *        passability only).
+ *      every b in U_k: s_b = its start cell (floor rule) if field_k is finite there, else the SNAP of lipmpc_grid_path_batch in
+ *        field_k (window r_inflate + 1, key (d^2, field, index)); cost_b = field_k[s_b].  A robot with no such cell is no
+ *        candidate in this round.  With no candidate the rounds end.
+ *      the winner is the candidate with the least (cost_b, b).  Its rows are written by the path rule of
+ *        lipmpc_grid_frontier_path_batch on field_k -- descent order, string pulling, max_seg, S_max, the last sub-goal the
+ *        centre of c_L, as written, no contraction: status (FOUND, or PATH_OVERFLOW with nothing written to sub_goals), n_sub,
+ *        sub_goals rows below n_sub (rows from n_sub on untouched), path_cost = field_k[s_b] / 5.0, target_cell = c_L, and
+ *        claim_round[b] = k.
+ *      S_{k+1} = S_k without the cells (i, j) with (i - i_t)^2 + (j - j_t)^2 <= r_claim^2, t = c_L (the disc clipped to the
+ *        grid); U_{k+1} = U_k without the winner.  A PATH_OVERFLOW winner claims like any other.
+ *  - every other robot keeps every output the path call gave it and gets claim_round = -1: robots that are not eligible, and
+ *    robots still in U when the rounds end -- FOLLOWERS, who keep their plain nearest-frontier plan and so share a target.
+ *  - n_claims[0] = the number of rounds that had a winner.
+ *  Hence: max_claims = 0 writes only claim_round = -1 and n_claims = 0; the round-0 winner's rows equal what the path call
+ *  wrote; the targets of two winners are more than r_claim apart; the winners' costs do not decrease from round to round.  The
+ *  outputs are a function of the inputs alone -- every comparison is an integer with a total order -- so two calls give
+ *  identical bits.  There is no memory between calls: a replan may hand a robot another target.
+ *  COST: the rounds are sequential, one relaxation of the whole map per claim.  field_k is kept in LDS when 4 W H bytes beside two
+ *  bitmaps (impassable, sources) and 22 words fit the 160 KiB of a workgroup: 4 (2 (2 ceil(W H / 64) + 2) + 22 + W H) + 256 <=
+ *  163840, up to about 38,400 cells; a larger map is relaxed in `work`.
+ * Restated in numpy by tests/assign_oracle.py (multi-source Dijkstra per round); the device's outputs equal it bit for bit.
+ * All pointers DEVICE pointers but origin / cell (HOST); asynchronous on hip_stream; no allocation and no host synchronisation,
+ * so the call can be captured in a graph; every refusal is decided on the host before anything is enqueued.
+ * LIPMPC_E_ARG: B outside 0..2^31-1, W or H < 2, a cell size that is not positive and finite, an origin that is not finite,
+ *  r_inflate outside 0..16, r_claim outside 0..4096, max_claims outside 0..4096, max_seg < 5, S_max < 1, any null pointer but
+ *  may_claim.  Then LIPMPC_E_UNSUPPORTED: W * H > 2^17, W > 4096 or H > 4096.  Then B = 0 enqueues nothing and returns 0. */
+int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                      const uint8_t* frontier, const uint32_t* field, const double* start, const int8_t* may_claim,
+                                      int32_t r_inflate, int32_t r_claim, int32_t max_claims, int32_t max_seg, int32_t S_max,
+                                      uint32_t* work, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                      int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, void* hip_stream);
 
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
