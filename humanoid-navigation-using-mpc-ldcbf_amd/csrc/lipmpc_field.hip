@@ -12,7 +12,12 @@
 //   frontier_path_kernel     grid_path_kernel's snap, descent and string pulling, ending at the first frontier cell reached.
 //   frontier_assign_*_kernel ONE workgroup for a fleet on a shared map (lipmpc_grid_frontier_assign_batch): round by round the
 //                            relaxation from what is left of the frontier, the nearest robot's claim and path, its disc cleared.
-// Everything the two kernels compare is an integer but the two floors that name a cell; the cell centres are one multiply and
+// and the informed explorer (lipmpc_grid_frontier_gain_batch, lipmpc_grid_frontier_utility_field_batch,
+// lipmpc_grid_frontier_utility_path_batch):
+//   frontier_gain_kernel          a wave per frontier cell, a lane per ray of the fan: the distinct unknown cells seen from it.
+//   frontier_utility_*_kernel     one workgroup per map: the same relaxation from sources that start at a gain-dependent seed.
+//   frontier_utility_path_kernel  frontier_path_kernel down that field, ending at the first source that holds its own seed.
+// Everything the kernels compare is an integer but the two floors that name a cell; the cell centres are one multiply and
 // one add, contraction off.  tests/field_oracle.py restates both contracts (Dijkstra) and the GPU tests hold every output to it
 // bit for bit.
 //
@@ -690,6 +695,252 @@ __global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_global_kernel(
               sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// the informed explorer (lipmpc_grid_frontier_gain_batch, lipmpc_grid_frontier_utility_field_batch,
+// lipmpc_grid_frontier_utility_path_batch): what a robot would see from a frontier cell, the cost-to-go field whose sources start
+// ahead by what they reveal, and the paths down it.
+constexpr int R_VIEW_MAX = 64;
+constexpr int W_GAIN_MAX = 65535, G_CAP_MAX = 16384;
+constexpr int GAIN_THREADS = 1024, GAIN_WAVES = GAIN_THREADS / 64;
+constexpr int GAIN_CHUNK = 2048;                      // cells of a map per workgroup: blockIdx.x = map, blockIdx.y = chunk
+
+// words of a wave's visibility window, (2 r + 1)^2 bits, kept even
+__host__ __device__ inline int64_t gain_window_words(int r_view) {
+  const int64_t side = 2 * (int64_t)r_view + 1;
+  return ((side * side + 63) / 64) * 2;
+}
+
+// LDS of the gain kernel: the whole map's solid and unknown bitmaps, the chunk's frontier count (a word pair), the chunk's
+// frontier cells, one window per wave
+__host__ __device__ inline int64_t gain_lds_bytes(int64_t ncells, int r_view) {
+  return 4 * (2 * bitmap_words(ncells) + 2 + GAIN_CHUNK + GAIN_WAVES * gain_window_words(r_view));
+}
+
+// Work follows the frontier: the workgroup of a chunk compacts the chunk's frontier cells into a list (everything else gets its 0
+// on the way), then a wave takes one frontier cell at a time and its lanes the 8 r rays of the fan, 64 at a time.  A ray walks
+// outward by the planners' LOS expression -- quotient and remainder per axis, as los() -- and ORs the unknown cells it crosses
+// into the wave's window; the gain is the window's popcount: a set's size, whatever order lanes and rays fell in.
+__global__ void __launch_bounds__(GAIN_THREADS) frontier_gain_kernel(int W, int H, const int32_t* __restrict__ evidence, int t_free,
+                                                                     int t_occ, const uint8_t* __restrict__ frontier, int r_view,
+                                                                     int32_t* __restrict__ gain) {
+  extern __shared__ uint32_t field_lds[];
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  const int ww = (int)gain_window_words(r_view);
+  uint32_t *solid = field_lds, *unk = field_lds + words, *count = field_lds + 2 * words, *list = count + 2;
+  uint32_t* win = list + GAIN_CHUNK + wave * ww;
+  const int32_t* ev = evidence + f * (int64_t)ncells;
+  const uint8_t* fr = frontier + f * (int64_t)ncells;
+  int32_t* out = gain + f * (int64_t)ncells;
+
+  // evidence -> solid and unknown bitmaps, as the frontier field kernel classifies
+  for (int c0 = tid - lane; c0 < padded; c0 += GAIN_THREADS) {
+    const int c = c0 + lane;
+    const int e = c < ncells ? ev[c] : 0;
+    const bool is_solid = c < ncells && e >= t_occ, is_free = e <= -t_free;
+    const uint64_t ms = __ballot(is_solid), mu = __ballot(c < ncells && !is_solid && !is_free);
+    if (lane == 0) {
+      solid[c0 >> 5] = (uint32_t)ms; solid[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      unk[c0 >> 5] = (uint32_t)mu; unk[(c0 >> 5) + 1] = (uint32_t)(mu >> 32);
+    }
+  }
+  if (tid < 2) { solid[words - 2 + tid] = 0; unk[words - 2 + tid] = 0; }
+  if (tid == 0) *count = 0;
+  __syncthreads();
+  // the chunk's frontier cells (in whatever order: each cell's gain is its own)
+  const int c_lo = (int)blockIdx.y * GAIN_CHUNK, c_hi = min(c_lo + GAIN_CHUNK, ncells);
+  for (int c = c_lo + tid; c < c_hi; c += GAIN_THREADS) {
+    if (fr[c] != 0) list[atomicAdd(count, 1u)] = (uint32_t)c;
+    else out[c] = 0;
+  }
+  __syncthreads();
+  const int n = (int)*count, r = r_view, r2 = r * r, two_r = 2 * r, side = two_r + 1, n_rays = 8 * r;
+  for (int k = wave; k < n; k += GAIN_WAVES) {
+    const int s = (int)list[k], si = s / H, sj = s - si * H;
+    for (int w = lane; w < ww; w += 64) win[w] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int q = lane; q < n_rays; q += 64) {
+      // the end cell: the ring of Chebyshev radius r, side by side
+      const int edge = q / two_r, t = q - edge * two_r;
+      const int di = edge == 0 ? -r : edge == 1 ? t - r : edge == 2 ? r : r - t;
+      const int dj = edge == 0 ? t - r : edge == 1 ? r : edge == 2 ? r - t : -r;
+      int qi = 0, ri = r, qj = 0, rj = r;
+      for (int step = 1; step <= r; ++step) {
+        ri += 2 * di; rj += 2 * dj;
+        if (ri >= two_r) { ri -= two_r; ++qi; } else if (ri < 0) { ri += two_r; --qi; }
+        if (rj >= two_r) { rj -= two_r; ++qj; } else if (rj < 0) { rj += two_r; --qj; }
+        const int i = si + qi, j = sj + qj;
+        if (qi * qi + qj * qj > r2 || (unsigned)i >= (unsigned)W || (unsigned)j >= (unsigned)H) break;
+        const int c = i * H + j;
+        if (bit_of(solid, c)) break;
+        if (bit_of(unk, c)) {
+          const int b = (qi + r) * side + qj + r;
+          atomicOr(win + (b >> 5), 1u << (b & 31));
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    int seen = 0;
+    for (int w = lane; w < ww; w += 64) seen += __popc(win[w]);
+    for (int o = 32; o; o >>= 1) seen += __shfl_xor(seen, o);
+    if (lane == 0) out[s] = seen;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the window is read before the next cell clears it)
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// what a source starts with: sixteenths of a cost unit per cell it reveals less than g_cap (at most 2^26: no sum wraps)
+__device__ inline uint32_t gain_seed(int g, int w_gain, int g_cap) {
+  return ((uint32_t)w_gain * (uint32_t)(g_cap - min(max(g, 0), g_cap))) >> 4;
+}
+
+// LDS of the utility field kernels: the impassable bitmap, the source count (a word pair: the field stays 8-byte aligned), then
+// the field -- or bitmap and count alone
+__host__ __device__ inline int64_t utility_bitmap_words(int64_t ncells) { return bitmap_words(ncells) + 2; }
+__host__ __device__ inline int64_t utility_lds_bytes(int64_t ncells, bool in_lds) {
+  return 4 * (utility_bitmap_words(ncells) + (in_lds ? ncells : 0));
+}
+
+inline bool utility_fits_lds(int64_t ncells) { return utility_lds_bytes(ncells, true) + LDS_SLACK <= LDS_LIMIT; }
+
+// blockIdx.x = map.  `fld`: the field's working copy ([W*H], LDS or the output itself); `bm`: the bitmap and the count's word.
+// The sweeps converge from any seeds by monotone minimum: a value is the cost of a real path to some source plus that source's
+// seed, values only fall, and the fixed point is the least such sum -- unique, whatever order the races fell in.
+template <bool COPY_OUT, typename FieldPtr>
+__device__ inline void utility_body(FieldPtr fld, uint32_t* bm, int W, int H, const uint8_t* __restrict__ frontier,
+                                    const uint32_t* __restrict__ field, const int32_t* __restrict__ gain, int w_gain, int g_cap,
+                                    int min_gain, uint32_t* ufield, int32_t* __restrict__ n_sources) {
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  uint32_t *blk = bm, *n_src = bm + words;
+  const uint8_t* fr = frontier + f * (int64_t)ncells;
+  const uint32_t* given = field + f * (int64_t)ncells;
+  const int32_t* gn = gain + f * (int64_t)ncells;
+  uint32_t* out = ufield + f * (int64_t)ncells;
+
+  if (tid < 2) blk[words - 2 + tid] = 0;
+  if (tid == 0) *n_src = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+    const int c = c0 + lane;
+    const bool pass = c < ncells && given[c] != INF;
+    bool src = false;
+    if (pass && fr[c] != 0) {
+      const int g = gn[c];
+      src = g >= min_gain;
+      if (src) st(fld + c, gain_seed(g, w_gain, g_cap));
+    }
+    if (c < ncells && !src) st(fld + c, INF);
+    const uint64_t mb = __ballot(c < ncells && !pass);
+    if (lane == 0) { blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32); }
+    mine += __popcll(__ballot(src));
+  }
+  if (lane == 0 && mine) atomicAdd(n_src, (uint32_t)mine);
+  __syncthreads();
+  const int n = (int)*n_src;
+  if (tid == 0) n_sources[f] = n;
+  if (n) relax(fld, blk, W, H);                          // (no source: the field is INF as it stands)
+  if (COPY_OUT)
+    for (int c = tid; c < ncells; c += FIELD_THREADS) out[c] = ld(fld + c);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_utility_lds_kernel(int W, int H, const uint8_t* __restrict__ frontier,
+                                                                             const uint32_t* __restrict__ field,
+                                                                             const int32_t* __restrict__ gain, int w_gain, int g_cap,
+                                                                             int min_gain, uint32_t* __restrict__ ufield,
+                                                                             int32_t* __restrict__ n_sources) {
+  extern __shared__ uint32_t field_lds[];
+  utility_body<true>(field_lds + utility_bitmap_words((int64_t)W * H), field_lds, W, H, frontier, field, gain, w_gain, g_cap, min_gain,
+                     ufield, n_sources);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_utility_global_kernel(int W, int H, const uint8_t* __restrict__ frontier,
+                                                                                const uint32_t* __restrict__ field,
+                                                                                const int32_t* __restrict__ gain, int w_gain, int g_cap,
+                                                                                int min_gain, uint32_t* ufield,
+                                                                                int32_t* __restrict__ n_sources) {
+  extern __shared__ uint32_t field_lds[];
+  utility_body<false>(ufield + (int64_t)blockIdx.x * W * H, field_lds, W, H, frontier, field, gain, w_gain, g_cap, min_gain, ufield,
+                      n_sources);
+}
+
+// walk() down a utility field: the same descent and string pulling, ending at the first TERMINAL cell -- a source that holds its
+// own seed -- instead of the first 0; the test comes before a descending neighbour is looked for
+template <typename Terminal>
+__device__ inline int walk_to(const uint32_t* __restrict__ fld, int W, int H, int s, int max_seg, double ox, double oy, double dx, double dy,
+                              double* sg, int& last_cell, Terminal terminal) {
+  int count = 0;
+  auto emit = [&](int c) {
+    if (sg) centre(c, H, ox, oy, dx, dy, sg + 2 * count);
+    ++count;
+  };
+  last_cell = s;
+  if (!terminal(s)) {
+    int a = s, prev = s, cur = descend(fld, W, H, s);
+    while (cur >= 0) {
+      const bool last = terminal(cur);
+      if (!los(fld, H, a, cur) || fld[a] - fld[cur] >= (uint32_t)max_seg) {
+        if (prev != a) { emit(prev); a = prev; continue; }          // cur is looked at again from the new anchor
+        if (last) break;
+        emit(cur); a = cur;
+      }
+      if (last) break;
+      prev = cur;
+      cur = descend(fld, W, H, cur);
+    }
+    if (cur < 0) return -1;
+    last_cell = cur;
+  }
+  return count + 1;
+}
+
+// One lane per robot: frontier_path_kernel down a utility field, to the centre of the first terminal cell reached.
+__global__ void __launch_bounds__(PATH_THREADS) frontier_utility_path_kernel(
+    int64_t B, int one_field, int W, int H, double ox, double oy, double dx, double dy, const int32_t* __restrict__ evidence, int t_occ,
+    const uint8_t* __restrict__ frontier, const int32_t* __restrict__ gain, const uint32_t* __restrict__ ufield,
+    const int32_t* __restrict__ n_sources, int w_gain, int g_cap, int min_gain, const double* __restrict__ start, int r_inflate, int max_seg,
+    int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub, int32_t* __restrict__ status, double* __restrict__ path_cost,
+    int32_t* __restrict__ target_cell, int32_t* __restrict__ target_gain) {
+  const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const int64_t f = one_field ? 0 : b;
+  const int ncells = W * H;
+  const uint32_t* fld = ufield + f * (int64_t)ncells;
+  const uint8_t* fr = frontier + f * (int64_t)ncells;
+  const int32_t* gn = gain + f * (int64_t)ncells;
+  auto done = [&](int st_, int n, double cost, int target) {
+    status[b] = st_; n_sub[b] = n; path_cost[b] = cost; target_cell[b] = target; target_gain[b] = target >= 0 ? gn[target] : -1;
+  };
+  // (a source is passable: its field is finite, which the comparison with a seed says too)
+  auto terminal = [&](int c) {
+    if (fr[c] == 0) return false;
+    const int g = gn[c];
+    return g >= min_gain && fld[c] == gain_seed(g, w_gain, g_cap);
+  };
+  const double nan = __builtin_nan("");
+  int si = 0, sj = 0;
+  if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan, -1);
+  int s = si * H + sj;
+  if (evidence[f * (int64_t)ncells + s] >= t_occ) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan, -1);
+  if (n_sources[f] == 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
+  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  double* sg = sub_goals + b * (int64_t)S_max * 2;
+  int last_cell;
+  const int n = walk_to(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell, terminal);
+  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);             // (a `ufield` that is no utility field of this map)
+  const double cost = (double)(fld[s] - fld[last_cell]) / 5.0;
+  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, cost, last_cell);
+  walk_to(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell, terminal);
+  centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
+  done(LIPMPC_RRT_FOUND, n, cost, last_cell);
+}
+
 // what both entry points refuse about the grid: E_ARG, then the caps
 int grid_refusal(int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate) {
   if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
@@ -813,5 +1064,70 @@ extern "C" int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t 
                        cell[1], frontier, field, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max, work, sub_goals,
                        n_sub, status, path_cost, target_cell, claim_round, n_claims);
   }
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_gain_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                               int32_t t_occ, const uint8_t* frontier, int32_t r_view, int32_t* gain, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
+      r_view < 1 || r_view > R_VIEW_MAX || !evidence || !frontier || !gain)
+    return LIPMPC_E_ARG;
+  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  const int64_t ncells = (int64_t)W * H;
+  const size_t lds = (size_t)gain_lds_bytes(ncells, r_view);
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)frontier_gain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(frontier_gain_kernel, dim3((unsigned)F, (unsigned)((ncells + GAIN_CHUNK - 1) / GAIN_CHUNK)), dim3(GAIN_THREADS), lds,
+                     (hipStream_t)hip_stream, W, H, evidence, t_free, t_occ, frontier, r_view, gain);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_utility_field_batch(int device, int64_t F, int32_t W, int32_t H, const uint8_t* frontier,
+                                                        const uint32_t* field, const int32_t* gain, int32_t w_gain, int32_t g_cap,
+                                                        int32_t min_gain, uint32_t* ufield, int32_t* n_sources, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 ||
+      min_gain > G_CAP_MAX || !frontier || !field || !gain || !ufield || !n_sources)
+    return LIPMPC_E_ARG;
+  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t ncells = (int64_t)W * H;
+  const bool in_lds = utility_fits_lds(ncells);
+  const size_t lds = (size_t)utility_lds_bytes(ncells, in_lds);
+  if (in_lds) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_utility_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+      return LIPMPC_E_HIP;
+    hipLaunchKernelGGL(frontier_utility_lds_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, frontier, field, gain, w_gain,
+                       g_cap, min_gain, ufield, n_sources);
+  } else {
+    hipLaunchKernelGGL(frontier_utility_global_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, frontier, field, gain, w_gain,
+                       g_cap, min_gain, ufield, n_sources);
+  }
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                                       const double* cell, const int32_t* evidence, int32_t t_occ, const uint8_t* frontier,
+                                                       const int32_t* gain, const uint32_t* ufield, const int32_t* n_sources,
+                                                       int32_t w_gain, int32_t g_cap, int32_t min_gain, const double* start,
+                                                       int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
+                                                       int32_t* status, double* path_cost, int32_t* target_cell, int32_t* target_gain,
+                                                       void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX || w_gain < 0 ||
+      w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !evidence || !frontier || !gain ||
+      !ufield || !n_sources || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !target_gain)
+    return LIPMPC_E_ARG;
+  if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(frontier_utility_path_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier,
+                     gain, ufield, n_sources, w_gain, g_cap, min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
+                     path_cost, target_cell, target_gain);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

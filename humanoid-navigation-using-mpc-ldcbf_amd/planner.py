@@ -13,6 +13,10 @@ space, the cost-to-go to the nearest frontier cell (``lipmpc_grid_frontier_field
 
 ``CoordinatedFrontierPlanner`` is ``FrontierPlanner`` for a fleet on one shared map: after the two calls the robots claim frontier
 targets apart, nearest claim first (``lipmpc_grid_frontier_assign_batch``).
+
+``InformedFrontierPlanner`` is ``FrontierPlanner`` with a utility from expected visibility: the unknown cells a robot would see
+from every frontier cell (``lipmpc_grid_frontier_gain_batch``), a cost-to-go field whose sources start ahead by that gain
+(``lipmpc_grid_frontier_utility_field_batch``) and sub-goals down it (``lipmpc_grid_frontier_utility_path_batch``).
 """
 from __future__ import annotations
 
@@ -55,6 +59,14 @@ def assign_outputs(B, W, H, S_max):
     i32 = torch.int32
     return dict(frontier_outputs(B, 1, W, H, S_max), claim_round=(i32, (B,), True), n_claims=(i32, (1,), True),
                 work=(torch.uint32, (W, H), True))
+
+
+def informed_outputs(B, F, W, H, S_max):
+    """Outputs of InformedFrontierPlanner.plan, in the order it returns them: FrontierPlanner.plan's (field, frontier and n_frontier
+    stay the nearest-frontier ones), then the gain, the utility field, its source count and the gain of every robot's target."""
+    i32 = torch.int32
+    return dict(frontier_outputs(B, F, W, H, S_max), gain=(i32, (F, W, H), True), ufield=(torch.uint32, (F, W, H), True),
+                n_sources=(i32, (F,), True), target_gain=(i32, (B,), True))
 
 
 def plan_outputs(B, S_max, max_cells, n_samples):
@@ -326,7 +338,8 @@ class FrontierPlanner:
     are impassable but not inflated).  ``t_free`` / ``t_occ``: None = the mapper's ``w_miss`` / ``w_hit``.  ``max_seg``: as
     ``GridFieldPlanner``'s.
     The model's limits: every robot heads for ITS nearest frontier -- there is no task assignment here, two robots side by side
-    pick the same cell (``CoordinatedFrontierPlanner`` lets them claim targets apart) -- and n_frontier == 0 (status RRT_NO_PATH
+    pick the same cell (``CoordinatedFrontierPlanner`` lets them claim targets apart), and the nearest cell may reveal next to
+    nothing (``InformedFrontierPlanner`` weighs what a cell would show) -- and n_frontier == 0 (status RRT_NO_PATH
     for everybody) is how "nothing left to explore" is told.  The walker that follows these goals cannot turn on the spot while
     walking: a goal that jumps behind it can make its solve INFEASIBLE, which costs the robot a capture step in a fleet with
     ``recover`` and its run in one without."""
@@ -494,3 +507,99 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         self._target(out, origin, cell, H)
         self.last = out
         return out
+
+
+class InformedFrontierPlanner(FrontierPlanner):
+    """``FrontierPlanner`` with a utility from expected visibility (include/lipmpc.h, INFORMED EXPLORER): the GAIN of a frontier cell
+    is the number of distinct unknown cells that a fan of 8 ``r_view`` rays from it reaches within ``r_view`` cells (1..64) before a
+    solid cell; the UTILITY FIELD is the cost-to-go to the frontier in which a source starts at
+    (``w_gain`` * (``g_cap`` - min(gain, ``g_cap``))) >> 4 instead of 0 -- ``w_gain`` (0..65535) sixteenths of a cost unit (5 per
+    cell) for every cell it reveals less than ``g_cap`` (1..16384) -- and only frontier cells with gain >= ``min_gain`` (0..16384)
+    are sources.  One field per shared map still serves every robot.  With ``g_cap`` well below the disc's cell count every cell that
+    reveals enough starts at 0: robots go to the nearest good-enough frontier rather than all to the single best one.  With
+    ``min_gain`` > 0 slivers are nobody's target, and a fleet stops (RRT_NO_PATH) when nothing worth seeing is left.  ``w_gain`` = 0
+    with ``min_gain`` = 0 is ``FrontierPlanner``, bit for bit.  None of the three gain parameters has a default: nobody has measured
+    one.  The other arguments are ``FrontierPlanner``'s.
+    The model's limits: unknown cells do not occlude; there is no memory between plans (no hysteresis), so a replan may hand a robot
+    another target; a shared field sends robots that stand together to the same cell, as the parent does."""
+
+    def __init__(self, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, **frontier_planner_kwargs):
+        self.r_view, self.w_gain, self.g_cap, self.min_gain = int(r_view), int(w_gain), int(g_cap), int(min_gain)
+        if not 1 <= self.r_view <= 64 or not 0 <= self.w_gain <= 65535 or not 1 <= self.g_cap <= 16384 or not 0 <= self.min_gain <= 16384:
+            raise ValueError(f"invalid gain parameters (r_view {r_view}: 1..64, w_gain {w_gain}: 0..65535, g_cap {g_cap}: 1..16384, "
+                             f"min_gain {min_gain}: 0..16384)")
+        super().__init__(**frontier_planner_kwargs)
+
+    def _gain(self, ev, t_free, t_occ, out):
+        F, W, H = ev.shape
+        _lib.call("lipmpc_grid_frontier_gain_batch", device=self.device_index, F=F, W=W, H=H, evidence=ev, t_free=t_free, t_occ=t_occ,
+                  frontier=out["frontier"], r_view=self.r_view, gain=out["gain"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _ufield(self, ev, out):
+        F, W, H = ev.shape
+        _lib.call("lipmpc_grid_frontier_utility_field_batch", device=self.device_index, F=F, W=W, H=H, frontier=out["frontier"],
+                  field=out["field"], gain=out["gain"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, ufield=out["ufield"],
+                  n_sources=out["n_sources"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _fields(self, mapper_or_evidence, out, names):
+        ev, t_free, t_occ, _, _ = self._map(mapper_or_evidence)
+        table = informed_outputs(0, *ev.shape, 1)
+        if out is None:
+            out = _alloc(table, names, self.device)
+        else:
+            _check_table({k: table[k] for k in names}, out, self.device, "out")
+        self._field(ev, t_free, t_occ, out)
+        self._gain(ev, t_free, t_occ, out)
+        if "ufield" in names:
+            self._ufield(ev, out)
+        return {k: out[k] for k in names}
+
+    def gain(self, mapper_or_evidence, out=None):
+        """``FrontierPlanner.field``'s dict plus gain [F,W,H] int32: per frontier cell the unknown cells seen from it, 0 elsewhere."""
+        return self._fields(mapper_or_evidence, out, ("field", "frontier", "n_frontier", "gain"))
+
+    def field(self, mapper_or_evidence, out=None):
+        """``FrontierPlanner.field``'s dict (the nearest-frontier field) plus gain [F,W,H] int32, ufield [F,W,H] uint32 (the utility
+        field: a source's seed where nothing dominates it, FIELD_INF = impassable or cut off) and n_sources [F] (0: nothing worth
+        seeing is left, the whole ufield FIELD_INF).  ``out``: that dict, to write into."""
+        return self._fields(mapper_or_evidence, out, ("field", "frontier", "n_frontier", "gain", "ufield", "n_sources"))
+
+    def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None):
+        """``FrontierPlanner.plan`` down the utility field: shared or per-robot maps, the same arguments.  Returns the parent's dict
+        -- sub_goals, n_sub, status (RRT_NO_PATH: no source left, or none within reach), path_cost (the walk's length in cells),
+        target, target_cell; field, frontier and n_frontier stay the nearest-frontier ones -- plus gain [F,W,H], ufield [F,W,H],
+        n_sources [F] and target_gain [B] (the gain of the target cell, -1 unless FOUND or PATH_OVERFLOW).  ``out``: that dict, to
+        write into (a captured graph replays into the same buffers; nothing is allocated then)."""
+        ev, t_free, t_occ, origin, cell = self._map(mapper_or_evidence, origin, cell)
+        origin, cell, org_c, cell_c = self._placement(origin, cell)
+        start = torch.as_tensor(start).to(device=self.device, dtype=torch.float64).contiguous()
+        if start.dim() != 2 or start.shape[1] != 2:
+            raise ValueError("start must be [B,2]")
+        B, (F, W, H), S_max = start.shape[0], ev.shape, int(S_max)
+        if F != B and F != 1:
+            raise ValueError(f"{F} maps for {B} robots: one shared map, or one per robot")
+        table = informed_outputs(B, F, W, H, S_max)
+        if out is None:
+            out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost", "target", "target_cell"), self.device, torch.zeros)
+            out.update(_alloc(table, ("field", "frontier", "n_frontier", "gain", "ufield", "n_sources"), self.device))     # written whole
+            out["target_gain"] = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        else:
+            _check_table(table, out, self.device, "out")
+        if B == 0:
+            return out
+        self._field(ev, t_free, t_occ, out)
+        self._gain(ev, t_free, t_occ, out)
+        self._ufield(ev, out)
+        self._path(ev, t_occ, start, org_c, cell_c, S_max, out)
+        self._target(out, origin, cell, H)
+        self.last = out
+        return out
+
+    def _path(self, ev, t_occ, start, org_c, cell_c, S_max, out):
+        F, W, H = ev.shape
+        _lib.call("lipmpc_grid_frontier_utility_path_batch", device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
+                  origin=C.addressof(org_c), cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ,
+                  **_named(out, ("frontier", "gain", "ufield", "n_sources")), w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain,
+                  start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
+                  **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "target_gain")),
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)

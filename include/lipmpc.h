@@ -794,6 +794,96 @@ int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t W, int32_t 
                                       uint32_t* work, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                       int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, void* hip_stream);
 
+/* INFORMED EXPLORER (backward-compatible addition): send explorers where they will see most.  The frontier path call sends a
+ * robot to its NEAREST frontier cell, whatever that cell would reveal: a cell behind a wall stub is worth as much as one that
+ * faces an open unknown half-plane.  These three calls add the expected-visibility utility of frontier exploration (Gonzalez-
+ * Banos and Latombe 2002; Burgard et al. 2005): lipmpc_grid_frontier_gain_batch counts the unknown cells a robot standing on a
+ * frontier cell would see, lipmpc_grid_frontier_utility_field_batch relaxes a cost-to-go field whose sources start ahead by
+ * what they reveal -- so ONE field per shared map still serves every robot -- and lipmpc_grid_frontier_utility_path_batch sends
+ * any number of robots down it.  Everything compared is an integer.  All three calls: all pointers DEVICE pointers but origin /
+ * cell (HOST); asynchronous on hip_stream; no allocation and no host synchronisation, so they can be captured in a graph; every
+ * refusal is a return code decided on the host before anything is enqueued -- LIPMPC_E_ARG first, then LIPMPC_E_UNSUPPORTED
+ * (W * H > 2^17, W > 4096 or H > 4096), then F = 0 / B = 0 enqueues nothing and returns 0.
+ *
+ * lipmpc_grid_frontier_gain_batch: F maps; a wave per frontier cell, a lane per ray.
+ *  evidence [F,W,H] int32, t_free, t_occ 1..2^30: what lipmpc_grid_frontier_field_batch was given
+ *  frontier [F,W,H] uint8: its output (not optional here);  r_view 1..64, in cells: how far a robot sees
+ *  gain     [F,W,H] int32, written whole
+ * THE GAIN of one map, solid / free / unknown as in the frontier field call, r = r_view:
+ *  - gain[c] = 0 where frontier[c] == 0.  The call does not re-derive the frontier: it takes the given bytes.
+ *  - for a frontier cell s = (i, j) the END CELLS are the 8 r offsets (di, dj) with max(|di|, |dj|) == r.
+ *  - the RAY to an end cell visits, for k = 1, 2, ..., r, the offset (a, b) = (floor((2 k di + r) / (2 r)),
+ *    floor((2 k dj + r) / (2 r))), the floor toward minus infinity: the planners' LOS expression walked outward from s, with no
+ *    lexicographic swap.
+ *  - the ray ENDS before the first k at which a^2 + b^2 > r^2, or (i + a, j + b) is outside the grid, or that cell is solid.
+ *    Unknown and free cells do not stop a ray (an unknown cell is no partial occluder).
+ *  - gain[s] = the number of DISTINCT unknown cells visited by any of the 8 r rays.
+ *  The count is the size of a set: it depends on neither ray order nor lane order, so two calls give identical bits.  On an
+ *  all-unknown map the fan reaches every cell of the disc: gain = (cells with a^2 + b^2 <= r^2) - 1, 12852 at r = 64.
+ *  Work follows the number of frontier cells, not W H r^2: a workgroup takes 2048 cells of a map, compacts their frontier cells
+ *  and hands them to its 16 waves.  LDS: the map's solid and unknown bitmaps (2 x 16 KiB at 2^17 cells), the list of 2048 cells,
+ *  and per wave a window of (2 r + 1)^2 bits (2.1 KiB at r = 64) that the rays OR into and whose popcount is the gain.
+ * LIPMPC_E_ARG: F < 0, W or H < 2, t_free or t_occ outside 1..2^30, r_view outside 1..64, a null evidence / frontier / gain
+ *  (whatever F). */
+int lipmpc_grid_frontier_gain_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                    int32_t t_occ, const uint8_t* frontier, int32_t r_view, int32_t* gain, void* hip_stream);
+
+/* lipmpc_grid_frontier_utility_field_batch: F maps, one workgroup per map: cost-to-go with a head start for cells that reveal more.
+ *  frontier [F,W,H] uint8, field [F,W,H] uint32: the outputs of lipmpc_grid_frontier_field_batch; both are only read
+ *  gain     [F,W,H] int32: lipmpc_grid_frontier_gain_batch's output -- or any int32 array: values are clamped to 0..g_cap
+ *  w_gain 0..65535;  g_cap 1..16384;  min_gain 0..16384
+ *  ufield   [F,W,H] uint32 (it overlaps nothing else);  n_sources [F] int32
+ * THE RULE:
+ *  - passable(c) <=> field[c] != LIPMPC_FIELD_INF: `field` is read for passability only, the argument
+ *    lipmpc_grid_frontier_assign_batch makes.  Moves go between passable cells at the costs 5 / 7 with the no-corner-cut rule.
+ *  - source(c) <=> frontier[c] != 0 && passable(c) && gain[c] >= min_gain (gain[c] as stored).
+ *  - seed(c) = (w_gain * (g_cap - min(max(gain[c], 0), g_cap))) >> 4: sixteenths of a cost unit per cell that c reveals less
+ *    than g_cap; at most 2^26.
+ *  - ufield[c] = the least, over sources s, of seed(s) + the cost from c to s; INF on impassable cells and on cells that reach
+ *    no source.  Finite values stay below 7 * 2^17 + 2^26: no addition wraps.
+ *  - n_sources[f] = the number of sources.  With 0 the whole ufield is INF.
+ *  Hence: w_gain = 0 and min_gain = 0 give ufield == field, bit for bit.  With g_cap well below the disc's cell count every
+ *  cell that reveals at least g_cap has seed 0, and robots go to the NEAREST GOOD-ENOUGH frontier cell instead of all to the
+ *  single best one; min_gain > 0 prunes slivers, and when nothing worth seeing is left n_sources is 0.  A source may be
+ *  DOMINATED (ufield[c] < seed(c)): a better cell is near enough that nobody stops here.
+ *  The relaxation of lipmpc_grid_field_batch converges from any seeds by monotone minimum, and the least sum is unique: two
+ *  calls give identical bits.  ufield is kept in LDS, sized to the map, when 4 W H bytes beside one bitmap (impassable) and the
+ *  count's word pair fit the 160 KiB of a workgroup: 4 ((2 ceil(W H / 64) + 2) + 2 + W H) + 256 <= 163840, up to about 39,600
+ *  cells; a larger map is relaxed in `ufield` itself.
+ * Restated in numpy by tests/gain_oracle.py (seeded multi-source Dijkstra); the device's outputs equal it bit for bit.
+ * LIPMPC_E_ARG: F < 0, W or H < 2, w_gain outside 0..65535, g_cap outside 1..16384, min_gain outside 0..16384, a null pointer
+ *  (whatever F). */
+int lipmpc_grid_frontier_utility_field_batch(int device, int64_t F, int32_t W, int32_t H, const uint8_t* frontier,
+                                             const uint32_t* field, const int32_t* gain, int32_t w_gain, int32_t g_cap,
+                                             int32_t min_gain, uint32_t* ufield, int32_t* n_sources, void* hip_stream);
+
+/* lipmpc_grid_frontier_utility_path_batch: B robots, one lane per robot, each down the utility field of its map.
+ *  B, F, W, H, origin, cell, evidence, t_occ, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell:
+ *         lipmpc_grid_frontier_path_batch's
+ *  frontier, gain, ufield [F,W,H], n_sources [F], w_gain, g_cap, min_gain: what the utility field call was given and wrote
+ *  target_gain [B] int32
+ * PER ROBOT this is lipmpc_grid_frontier_path_batch with ufield in the place of field, with these differences and no others:
+ *  - n_sources[f] == 0 ends LIPMPC_RRT_NO_PATH, in the place of n_frontier[f] == 0.
+ *  - terminal(c) <=> source(c) && ufield[c] == seed(c): a source that nothing dominates.
+ *  - the descent ends at the FIRST terminal cell c_L.  The terminal test is made before a descending neighbour is looked for,
+ *    so a source whose seed ties a route through it is where the robot stops.  A start cell that is terminal after the snap
+ *    gives n_sub = 1, its own centre.  A non-terminal cell with no descending neighbour ends LIPMPC_RRT_NO_PATH: the input is
+ *    no utility field of this map.
+ *  - path_cost = (ufield[s] - ufield[c_L]) / 5.0, s the start cell after the snap: the walk's length in cells.
+ *  - target_gain[b] = gain[c_L] as stored; -1 unless the status is FOUND or PATH_OVERFLOW.
+ *  The snap's window and key, the descent's order, the string pulling, max_seg on ufield[a] - ufield[c_k], S_max, "rows from
+ *  n_sub on untouched", the centre expression without contraction and target_cell are lipmpc_grid_frontier_path_batch's.
+ *  With w_gain = 0 and min_gain = 0 every output equals that call's, bit for bit.
+ * Restated in numpy by tests/gain_oracle.py; the device's outputs equal it bit for bit.
+ * LIPMPC_E_ARG: what lipmpc_grid_frontier_path_batch refuses, the three gain parameters out of range, any null pointer
+ *  (whatever B). */
+int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                            const double* cell, const int32_t* evidence, int32_t t_occ, const uint8_t* frontier,
+                                            const int32_t* gain, const uint32_t* ufield, const int32_t* n_sources, int32_t w_gain,
+                                            int32_t g_cap, int32_t min_gain, const double* start, int32_t r_inflate, int32_t max_seg,
+                                            int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                            int32_t* target_cell, int32_t* target_gain, void* hip_stream);
+
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
  * c_eta, in the form lipmpc_plan_step_batch_c_eta solves against -- after the rows of a scan (first_slot = the scan's
