@@ -105,6 +105,19 @@ SIGNATURES = {
                                                              "ufield n_sources w_gain:i32 g_cap:i32 min_gain:i32 start r_inflate:i32 "
                                                              "max_seg:i32 S_max:i32 sub_goals n_sub status path_cost target_cell target_gain "
                                                              "hip_stream"),
+    "lipmpc_grid_tiled_info": _sig(C.c_int, "tile_w tile_h max_cells"),
+    "lipmpc_grid_tiled_workspace_bytes": _sig(C.c_int64, "F:i64 W:i32 H:i32"),
+    "lipmpc_grid_field_tiled_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 grid_shared:i32 origin cell occ goal r_inflate:i32 field "
+                                                   "field_status work work_bytes:i64 max_rounds:i32 resume:i32 settled hip_stream"),
+    "lipmpc_grid_frontier_field_tiled_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 evidence t_free:i32 t_occ:i32 r_inflate:i32 "
+                                                            "min_unknown:i32 frontier field n_frontier work work_bytes:i64 max_rounds:i32 "
+                                                            "resume:i32 settled hip_stream"),
+    "lipmpc_grid_path_tiled_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell occ grid_shared:i32 field field_status "
+                                                  "settled goal start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost "
+                                                  "hip_stream"),
+    "lipmpc_grid_frontier_path_tiled_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell evidence t_occ:i32 field "
+                                                           "n_frontier settled start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub "
+                                                           "status path_cost target_cell hip_stream"),
     "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
                                              "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),

@@ -17,6 +17,10 @@
 //   frontier_gain_kernel          a wave per frontier cell, a lane per ray of the fan: the distinct unknown cells seen from it.
 //   frontier_utility_*_kernel     one workgroup per map: the same relaxation from sources that start at a gain-dependent seed.
 //   frontier_utility_path_kernel  frontier_path_kernel down that field, ending at the first source that holds its own seed.
+// and the same two fields on LARGE maps (lipmpc_grid_field_tiled_batch, lipmpc_grid_frontier_field_tiled_batch and their path calls),
+// at the end of this file:
+//   tiled_*_kernel                set-up by many workgroups, then ROUNDS of one workgroup per (field, tile) that relax a tile in LDS with
+//                                 a one-cell halo held, ordered by kernel boundaries alone; the path kernels with one more rule in front.
 // Everything the kernels compare is an integer but the two floors that name a cell; the cell centres are one multiply and
 // one add, contraction off.  tests/field_oracle.py restates both contracts (Dijkstra) and the GPU tests hold every output to it
 // bit for bit.
@@ -383,15 +387,14 @@ __device__ inline int walk(const uint32_t* __restrict__ fld, int W, int H, int s
   return count + 1;
 }
 
-// One lane per robot.
-__global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int one_field, int W, int H, int64_t occ_stride, double ox,
-                                                                 double oy, double dx, double dy, const uint8_t* __restrict__ occ,
-                                                                 const uint32_t* __restrict__ field,
-                                                                 const int32_t* __restrict__ field_status,
-                                                                 const double* __restrict__ goal, const double* __restrict__ start,
-                                                                 int r_inflate, int max_seg, int S_max, double* __restrict__ sub_goals,
-                                                                 int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
-                                                                 double* __restrict__ path_cost) {
+// One lane per robot.  `settled`: null, or the tiled field calls' word per field -- a robot whose field is not settled gets
+// LIPMPC_RRT_FIELD_UNSETTLED before any other rule.
+__device__ __forceinline__ void grid_path_body(int64_t B, int one_field, int W, int H, int64_t occ_stride, double ox, double oy, double dx,
+                                               double dy, const uint8_t* __restrict__ occ, const uint32_t* __restrict__ field,
+                                               const int32_t* __restrict__ field_status, const int32_t* __restrict__ settled,
+                                               const double* __restrict__ goal, const double* __restrict__ start, int r_inflate,
+                                               int max_seg, int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+                                               int32_t* __restrict__ status, double* __restrict__ path_cost) {
   const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
   if (b >= B) return;
   const int64_t f = one_field ? 0 : b;
@@ -399,6 +402,7 @@ __global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int 
   const uint32_t* fld = field + f * (int64_t)ncells;
   auto done = [&](int st_, int n, double cost) { status[b] = st_; n_sub[b] = n; path_cost[b] = cost; };
   const double nan = __builtin_nan("");
+  if (settled && settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan);
   const int fs = field_status[f];
   if (fs == LIPMPC_FIELD_GOAL_OUTSIDE) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan);
   if (fs == LIPMPC_FIELD_GOAL_BLOCKED) return done(LIPMPC_RRT_GOAL_OCCUPIED, 0, nan);
@@ -421,15 +425,27 @@ __global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int 
   done(LIPMPC_RRT_FOUND, n, cost);
 }
 
-// One lane per robot: grid_path_kernel down a frontier field, to the centre of the first frontier cell reached.
-__global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, int one_field, int W, int H, double ox, double oy, double dx,
-                                                                     double dy, const int32_t* __restrict__ evidence, int t_occ,
-                                                                     const uint32_t* __restrict__ field,
-                                                                     const int32_t* __restrict__ n_frontier,
-                                                                     const double* __restrict__ start, int r_inflate, int max_seg,
-                                                                     int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
-                                                                     int32_t* __restrict__ status, double* __restrict__ path_cost,
-                                                                     int32_t* __restrict__ target_cell) {
+__global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int one_field, int W, int H, int64_t occ_stride, double ox,
+                                                                 double oy, double dx, double dy, const uint8_t* __restrict__ occ,
+                                                                 const uint32_t* __restrict__ field,
+                                                                 const int32_t* __restrict__ field_status,
+                                                                 const double* __restrict__ goal, const double* __restrict__ start,
+                                                                 int r_inflate, int max_seg, int S_max, double* __restrict__ sub_goals,
+                                                                 int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
+                                                                 double* __restrict__ path_cost) {
+  grid_path_body(B, one_field, W, H, occ_stride, ox, oy, dx, dy, occ, field, field_status, nullptr, goal, start, r_inflate, max_seg, S_max,
+                 sub_goals, n_sub, status, path_cost);
+}
+
+// One lane per robot: grid_path_kernel down a frontier field, to the centre of the first frontier cell reached.  `settled`: as
+// grid_path_body's.
+__device__ __forceinline__ void frontier_path_body(int64_t B, int one_field, int W, int H, double ox, double oy, double dx, double dy,
+                                                   const int32_t* __restrict__ evidence, int t_occ, const uint32_t* __restrict__ field,
+                                                   const int32_t* __restrict__ n_frontier, const int32_t* __restrict__ settled,
+                                                   const double* __restrict__ start, int r_inflate, int max_seg, int S_max,
+                                                   double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+                                                   int32_t* __restrict__ status, double* __restrict__ path_cost,
+                                                   int32_t* __restrict__ target_cell) {
   const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
   if (b >= B) return;
   const int64_t f = one_field ? 0 : b;
@@ -437,6 +453,7 @@ __global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, 
   const uint32_t* fld = field + f * (int64_t)ncells;
   auto done = [&](int st_, int n, double cost, int target) { status[b] = st_; n_sub[b] = n; path_cost[b] = cost; target_cell[b] = target; };
   const double nan = __builtin_nan("");
+  if (settled && settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan, -1);
   int si = 0, sj = 0;
   if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan, -1);
   int s = si * H + sj;
@@ -453,6 +470,18 @@ __global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, 
   walk(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
   centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
   done(LIPMPC_RRT_FOUND, n, cost, last_cell);
+}
+
+__global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, int one_field, int W, int H, double ox, double oy, double dx,
+                                                                     double dy, const int32_t* __restrict__ evidence, int t_occ,
+                                                                     const uint32_t* __restrict__ field,
+                                                                     const int32_t* __restrict__ n_frontier,
+                                                                     const double* __restrict__ start, int r_inflate, int max_seg,
+                                                                     int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+                                                                     int32_t* __restrict__ status, double* __restrict__ path_cost,
+                                                                     int32_t* __restrict__ target_cell) {
+  frontier_path_body(B, one_field, W, H, ox, oy, dx, dy, evidence, t_occ, field, n_frontier, nullptr, start, r_inflate, max_seg, S_max,
+                     sub_goals, n_sub, status, path_cost, target_cell);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1129,5 +1158,466 @@ extern "C" int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, in
                      (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier,
                      gain, ufield, n_sources, w_gain, g_cap, min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
                      path_cost, target_cell, target_gain);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+// =====================================================================================================================
+// THE TILED FIELD (lipmpc_grid_field_tiled_batch, lipmpc_grid_frontier_field_tiled_batch and their path calls): the same two
+// cost-to-go fields relaxed by MANY workgroups, with no cap below 2^24 cells.  The map is cut into tiles of TILE_W x TILE_H
+// cells (i x j, j contiguous).  A ROUND is one launch of tiled_round_kernel with one workgroup per (field, tile):
+//   - a tile whose flag in the round's `cur` array is 0 returns at once;
+//   - an active tile clears its flag, stages its field words and blocked bits with a one-cell halo in LDS, relaxes its own cells
+//     to the local fixed point with the halo held, writes back the cells that fell and, for every part of its rim on which a
+//     cell fell, sets the flag of the neighbouring tile behind it in the round's `next` array.
+// The two flag arrays change places from round to round; workgroups are ordered by the kernel boundaries of the caller's stream
+// and by nothing else: nobody waits for a word that another workgroup writes.
+//
+// WHY THE TILES GIVE DIJKSTRA'S FIELD.  As above, every value a cell ever holds is the cost of a real path to a source and values
+// only fall; a cell is written by the workgroup of its own tile only.  A halo word is read (relaxed, agent scope) while its
+// owner may be lowering it: the reader gets the old or the new word, both path costs, so what it derives is a path cost too.
+// INVARIANT: after every round, a tile whose flag is not set for the next round is at its local fixed point for the halo words
+// as they stand at the end of the round.  For if it ran, it reached the fixed point for the halo it read, and a halo word that
+// differs at the end of the round fell in this round, on the rim of its owner, which then set this tile's flag; if it did not
+// run, it was at its fixed point before and the same holds of its halo.  (Before the first round the flags are set on every
+// tile whose cells or halo hold a seed; any other tile holds INF beside INF.)  Hence NO FLAG SET <=> every tile is at its fixed
+// point for final halo words <=> the whole map is a fixed point of  f(c) = min over legal moves c -> n of f(n) + cost  with
+// f = 0 on the sources: by the argument above that is the least cost, which is unique -- whatever order the races fell in.
+// A diagonal move is judged on the BLOCKED BITS of its two side cells, halo included, not on their field words: a side cell in
+// another tile may still hold INF although it is unblocked, and the move must be taken all the same (the same fixed point as the
+// one-workgroup kernels', where both rules agree once the sweeps have settled).
+// THE ROUND GUARANTEE: after R rounds in total a cell holds its final value if some least-cost path from it to a source changes
+// tile at most R - 1 times.  By induction on R.  Let the path leave the cell's tile T for the first time by the move x -> y (y
+// in another tile; none if the path stays in T).  The rest of the path from y is a least-cost path that changes tile at most
+// R - 2 times, so y holds its final value after round R - 1: either from the start (a source, then T's flag was set for round 1)
+// or since it fell in some round r <= R - 1, on the rim beside T, which set T's flag for round r + 1.  In the first round in
+// which T runs after that, it stages y's final word and relaxes to its local fixed point; the moves of the path inside T are
+// legal by blocked bits alone, so every cell of the path in T comes out <= the path's cost, which is the least: final, by
+// round R at the latest.
+namespace {
+
+constexpr int TILE_W = 32, TILE_H = 64;               // cells of a tile along i and along j
+constexpr int TILE_THREADS = 256, TILE_ROWS = TILE_THREADS / TILE_H;      // a thread owns cell (4 k + tid / 64, tid % 64), k = 0..7
+constexpr int TILE_OWN = TILE_W / TILE_ROWS;
+constexpr int HALO_H = TILE_H + 2, HALO_CELLS = (TILE_W + 2) * HALO_H;    // 34 x 66 = 2244 words, 9 KiB: many workgroups per CU
+constexpr int HALO_PADDED = ((HALO_CELLS + 63) / 64) * 64;
+constexpr int SETUP_THREADS = 256;
+constexpr int64_t TILED_MAX_CELLS = 1 << 24;          // a finite value stays below 7 * 2^24: the additions cannot wrap
+constexpr int64_t TILED_MAX_THREADS = (int64_t)1 << 31;                   // of one launch: F * (W * H + 64) stays within it
+constexpr int MAX_ROUNDS = 65536;
+static_assert(TILE_H == 64 && TILE_OWN * TILE_ROWS == TILE_W && TILE_OWN == 8, "the ownership rule and the 8-bit move masks");
+
+// relaxed accesses of agent scope: the global field and the tile flags, read by one workgroup while another writes
+__device__ inline uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__host__ __device__ inline int tiles_along(int n, int side) { return (n + side - 1) / side; }
+
+// The workspace: per field three bitmaps (solid, unknown, blocked; the goal field uses the first and the last, of map 0 alone on
+// a shared grid), then the two flag arrays [F, tiles] each.
+struct TiledLayout {
+  int64_t bm_words, tiles, solid, unknown, blocked, flags0, flags1, words;
+};
+inline TiledLayout tiled_layout(int64_t F, int64_t W, int64_t H) {
+  TiledLayout l;
+  l.bm_words = bitmap_words(W * H);
+  l.tiles = (int64_t)tiles_along((int)W, TILE_W) * tiles_along((int)H, TILE_H);
+  l.solid = 0;
+  l.unknown = F * l.bm_words;
+  l.blocked = 2 * F * l.bm_words;
+  l.flags0 = 3 * F * l.bm_words;
+  l.flags1 = l.flags0 + F * l.tiles;
+  l.words = l.flags1 + F * l.tiles;
+  return l;
+}
+// (of a shape within the caps: F * (W * H + 64) <= 2^31, so nothing wraps)
+inline int64_t tiled_bytes(int64_t F, int64_t W, int64_t H) { return 4 * tiled_layout(F, W, H).words + 256; }
+
+// set-up, one wave per 64 cells of a map (blockIdx.x = map * chunks + chunk): solid (and unknown) bytes -> bitmap words; both
+// flag arrays and n_frontier cleared.  KIND 0: occ bytes; KIND 1: evidence.
+template <int KIND>
+__global__ void __launch_bounds__(SETUP_THREADS) tiled_bitmaps_kernel(int ncells, int chunks, int64_t F, int64_t tiles,
+                                                                      const uint8_t* __restrict__ occ,
+                                                                      const int32_t* __restrict__ evidence, int t_free, int t_occ,
+                                                                      uint32_t* __restrict__ solid, uint32_t* __restrict__ unk,
+                                                                      uint32_t* __restrict__ flags, int32_t* __restrict__ n_frontier) {
+  const int64_t m = blockIdx.x / chunks;
+  const int chunk = blockIdx.x - (int)m * chunks, tid = threadIdx.x, lane = tid & 63;
+  const int words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  const int c = chunk * SETUP_THREADS + tid, c0 = c - lane;
+  uint32_t* so = solid + m * words;
+  if (c0 < padded) {
+    bool is_solid, is_unknown = false;
+    if (KIND == 0) {
+      is_solid = c < ncells && occ[m * ncells + c] != 0;
+    } else {
+      const int e = c < ncells ? evidence[m * ncells + c] : 0;
+      is_solid = c < ncells && e >= t_occ;
+      is_unknown = c < ncells && !is_solid && !(e <= -t_free);
+    }
+    const uint64_t ms = __ballot(is_solid), mu = __ballot(is_unknown);
+    if (lane == 0) {
+      so[c0 >> 5] = (uint32_t)ms; so[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      if (KIND == 1) { unk[m * words + (c0 >> 5)] = (uint32_t)mu; unk[m * words + (c0 >> 5) + 1] = (uint32_t)(mu >> 32); }
+    }
+  }
+  if (chunk == 0 && tid < 2) {
+    so[words - 2 + tid] = 0;
+    if (KIND == 1) unk[m * words + words - 2 + tid] = 0;
+  }
+  if (KIND == 1 && chunk == 0 && tid == 2) n_frontier[m] = 0;
+  // the flags of all F fields, both arrays (contiguous), by the blocks of map 0 .. : a grid-stride loop over the whole launch
+  const int64_t total = 2 * F * tiles, step = (int64_t)gridDim.x * SETUP_THREADS;
+  for (int64_t k = (int64_t)blockIdx.x * SETUP_THREADS + tid; k < total; k += step) flags[k] = 0;
+}
+
+// set-up: blocked = solid dilated by the disc (| unknown), on the global bitmaps
+template <int KIND>
+__global__ void __launch_bounds__(SETUP_THREADS) tiled_blocked_kernel(int W, int H, int chunks, int r_inflate,
+                                                                      const uint32_t* __restrict__ solid,
+                                                                      const uint32_t* __restrict__ unk, uint32_t* __restrict__ blk) {
+  const int64_t m = blockIdx.x / chunks;
+  const int chunk = blockIdx.x - (int)m * chunks, tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  const int c = chunk * SETUP_THREADS + tid, c0 = c - lane;
+  if (c0 < padded) {
+    bool b = false;
+    if (c < ncells) {
+      const int i = c / H, j = c - i * H;
+      b = disc_hits(solid + m * words, W, H, i, j, r_inflate);
+      if (KIND == 1) b |= bit_of(unk + m * words, c);
+    }
+    const uint64_t mb = __ballot(b);
+    if (lane == 0) { blk[m * words + (c0 >> 5)] = (uint32_t)mb; blk[m * words + (c0 >> 5) + 1] = (uint32_t)(mb >> 32); }
+  }
+  if (chunk == 0 && tid < 2) blk[m * words + words - 2 + tid] = 0;
+}
+
+// a seed at (i, j): the flags of every tile that holds it among its cells or in its halo
+__device__ inline void flag_round_seed(uint32_t* flags, int W, int H, int tiles_j, int i, int j) {
+  for (int di = -1; di <= 1; ++di)
+    for (int dj = -1; dj <= 1; ++dj) {
+      const int ii = i + di, jj = j + dj;
+      if ((unsigned)ii < (unsigned)W && (unsigned)jj < (unsigned)H) st_agent(flags + (ii / TILE_W) * tiles_j + jj / TILE_H, 1u);
+    }
+}
+
+// set-up of the goal field: the status, 0 at the goal cell and INF elsewhere, the flags round the goal
+__global__ void __launch_bounds__(SETUP_THREADS) tiled_goal_seed_kernel(int W, int H, int chunks, int64_t blk_stride, double ox, double oy,
+                                                                        double dx, double dy, const double* __restrict__ goal,
+                                                                        const uint32_t* __restrict__ blk, uint32_t* __restrict__ field,
+                                                                        int32_t* __restrict__ field_status, uint32_t* __restrict__ flags,
+                                                                        int64_t tiles) {
+  const int64_t f = blockIdx.x / chunks;
+  const int chunk = blockIdx.x - (int)f * chunks, ncells = W * H;
+  const int c = chunk * SETUP_THREADS + threadIdx.x;
+  int gi = 0, gj = 0;
+  const bool inside = cell_of(goal[2 * f], goal[2 * f + 1], ox, oy, dx, dy, W, H, gi, gj);
+  const int gc = gi * H + gj;
+  const int status = !inside ? LIPMPC_FIELD_GOAL_OUTSIDE : bit_of(blk + f * blk_stride, gc) ? LIPMPC_FIELD_GOAL_BLOCKED : LIPMPC_FIELD_OK;
+  if (c == 0) field_status[f] = status;
+  if (c >= ncells) return;
+  const bool seed = status == LIPMPC_FIELD_OK && c == gc;
+  field[f * ncells + c] = seed ? 0u : INF;
+  if (seed) flag_round_seed(flags + f * tiles, W, H, tiles_along(H, TILE_H), gi, gj);
+}
+
+// set-up of the frontier field: the frontier test of frontier_body on the global bitmaps, 0 on frontier cells and INF elsewhere,
+// their count by integer atomics (n_frontier was cleared a kernel earlier), the flags round every frontier cell
+__global__ void __launch_bounds__(SETUP_THREADS) tiled_frontier_seed_kernel(int W, int H, int chunks, int min_unknown,
+                                                                            const uint32_t* __restrict__ unk,
+                                                                            const uint32_t* __restrict__ blk,
+                                                                            uint8_t* __restrict__ frontier, uint32_t* __restrict__ field,
+                                                                            int32_t* __restrict__ n_frontier, uint32_t* __restrict__ flags,
+                                                                            int64_t tiles) {
+  const int64_t f = blockIdx.x / chunks;
+  const int chunk = blockIdx.x - (int)f * chunks, lane = threadIdx.x & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells);
+  const int c = chunk * SETUP_THREADS + threadIdx.x;
+  const uint32_t *un = unk + f * words, *bl = blk + f * words;
+  bool fr = false;
+  if (c < ncells) {
+    const int i = c / H, j = c - i * H;
+    if (!bit_of(bl, c)) {
+      const int lo = max(j - 1, 0), hi = min(j + 1, H - 1);
+      const uint64_t mask = (1ull << (hi - lo + 1)) - 1;
+      int cnt = __popcll(window(un, c - j + lo) & mask);
+      if (i > 0) cnt += __popcll(window(un, c - H - j + lo) & mask);
+      if (i < W - 1) cnt += __popcll(window(un, c + H - j + lo) & mask);
+      fr = cnt >= min_unknown;
+    }
+    field[f * ncells + c] = fr ? 0u : INF;
+    if (frontier) frontier[f * ncells + c] = fr;
+    if (fr) flag_round_seed(flags + f * tiles, W, H, tiles_along(H, TILE_H), i, j);
+  }
+  const int mine = __popcll(__ballot(fr));
+  if (lane == 0 && mine) atomicAdd(n_frontier + f, mine);            // (integers: the sum is the same in any order)
+}
+
+// ONE ROUND.  blockIdx.x = field * tiles + tile.
+__global__ void __launch_bounds__(TILE_THREADS) tiled_round_kernel(int W, int H, int tiles_j, int tiles, int64_t blk_stride,
+                                                                   const uint32_t* __restrict__ blk, uint32_t* field, uint32_t* cur,
+                                                                   uint32_t* next) {
+  __shared__ uint32_t lf[HALO_CELLS];                 // field words, local index l = (li + 1) * HALO_H + lj + 1
+  __shared__ uint32_t lb[HALO_PADDED / 32 + 2];       // blocked bits by l; a cell outside the grid is blocked
+  __shared__ uint32_t rim;
+  const int64_t f = blockIdx.x / tiles;
+  const int tile = blockIdx.x - (int)f * tiles, tid = threadIdx.x, lane = tid & 63;
+  uint32_t* my_flag = cur + f * tiles + tile;
+  if (ld_agent(my_flag) == 0) return;                 // (one word for the whole workgroup: uniform)
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  const uint32_t* bl = blk + f * blk_stride;
+  uint32_t* fld = field + f * (int64_t)W * H;
+
+  for (int l0 = tid - lane; l0 < HALO_PADDED; l0 += TILE_THREADS) {
+    const int l = l0 + lane, li = l / HALO_H, lj = l - li * HALO_H;
+    const int gi = i0 + li - 1, gj = j0 + lj - 1;
+    const bool in = l < HALO_CELLS && (unsigned)gi < (unsigned)W && (unsigned)gj < (unsigned)H;
+    const int gc = in ? gi * H + gj : 0;
+    const uint32_t v = ld_agent(fld + gc);
+    const uint64_t mb = __ballot(!in || bit_of(bl, gc));
+    if (l < HALO_CELLS) lf[l] = in ? v : INF;
+    if (lane == 0) { lb[l0 >> 5] = (uint32_t)mb; lb[(l0 >> 5) + 1] = (uint32_t)(mb >> 32); }
+  }
+  if (tid == 0) rim = 0;
+  __syncthreads();                                    // (everybody has read the flag: it is cleared for the round after next)
+  if (tid == 0) st_agent(my_flag, 0u);
+
+  // the legal moves of my eight cells, a byte per cell, bit d = neighbour (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0),
+  // (1,1): the neighbour unblocked and, for a diagonal, both side cells unblocked.  0 for a blocked cell.
+  const int l_first = ((tid >> 6) + 1) * HALO_H + (tid & 63) + 1;
+  auto open_at = [&](int l) { return ((lb[l >> 5] >> (l & 31)) & 1u) ^ 1u; };       // 1 = unblocked (integers: no lane masks to keep)
+  uint64_t moves = 0;
+#pragma unroll 1
+  for (int k = 0; k < TILE_OWN; ++k) {
+    const int l = l_first + k * TILE_ROWS * HALO_H;
+    const uint32_t up = open_at(l - HALO_H), dn = open_at(l + HALO_H), lt = open_at(l - 1), rt = open_at(l + 1);
+    const uint32_t m = (open_at(l - HALO_H - 1) & up & lt) | up << 1 | (open_at(l - HALO_H + 1) & up & rt) << 2 | lt << 3 | rt << 4 |
+                       (open_at(l + HALO_H - 1) & dn & lt) << 5 | dn << 6 | (open_at(l + HALO_H + 1) & dn & rt) << 7;
+    moves |= (uint64_t)(m * open_at(l)) << (8 * k);
+  }
+
+  // the sweeps of relax(), on my cells, the halo held
+  uint32_t fell = 0;
+  for (;;) {
+    int changed = 0;
+#pragma unroll 1
+    for (int k = 0; k < TILE_OWN; ++k) {                // (not unrolled: eight cells' lane masks at once overfill the scalar file)
+      const uint32_t m = (uint32_t)(moves >> (8 * k)) & 0xFFu;
+      if (m) {
+        const int l = l_first + k * TILE_ROWS * HALO_H;
+        auto via = [&](int bit, int off, uint32_t cost) {
+          const uint32_t v = ld(lf + l + off);
+          return ((m >> bit) & 1u) && v != INF ? v + cost : INF;
+        };
+        const uint32_t cur_v = ld(lf + l);
+        const uint32_t best = min(min(min(via(0, -HALO_H - 1, DIAGONAL), via(1, -HALO_H, AXIAL)), min(via(2, -HALO_H + 1, DIAGONAL), via(3, -1, AXIAL))),
+                                  min(min(via(4, 1, AXIAL), via(5, HALO_H - 1, DIAGONAL)), min(via(6, HALO_H, AXIAL), via(7, HALO_H + 1, DIAGONAL))));
+        if (best < cur_v) { st(lf + l, best); changed = 1; fell |= 1u << k; }
+      }
+    }
+    if (!__syncthreads_or(changed)) break;
+  }
+
+  // write back what fell; which parts of the rim fell: bit 0 top, 1 bottom, 2 left, 3 right, 4..7 the corners
+  uint32_t r = 0;
+  const int lj = tid & 63;
+#pragma unroll
+  for (int k = 0; k < TILE_OWN; ++k)
+    if ((fell >> k) & 1u) {
+      const int li = k * TILE_ROWS + (tid >> 6);
+      st_agent(fld + (i0 + li) * H + j0 + lj, lf[l_first + k * TILE_ROWS * HALO_H]);
+      const bool top = li == 0, bot = li == TILE_W - 1, lft = lj == 0, rgt = lj == TILE_H - 1;
+      r |= (uint32_t)top | (uint32_t)bot << 1 | (uint32_t)lft << 2 | (uint32_t)rgt << 3 | (uint32_t)(top & lft) << 4 |
+           (uint32_t)(top & rgt) << 5 | (uint32_t)(bot & lft) << 6 | (uint32_t)(bot & rgt) << 7;
+    }
+  if (r) atomicOr(&rim, r);
+  __syncthreads();
+  if (tid < 8 && ((rim >> tid) & 1u)) {
+    const int di = tid == 0 || tid == 4 || tid == 5 ? -1 : tid == 1 || tid == 6 || tid == 7 ? 1 : 0;
+    const int dj = tid == 2 || tid == 4 || tid == 6 ? -1 : tid == 3 || tid == 5 || tid == 7 ? 1 : 0;
+    const int ni = ti + di, nj = tj + dj;
+    if ((unsigned)ni < (unsigned)(tiles / tiles_j) && (unsigned)nj < (unsigned)tiles_j) st_agent(next + f * tiles + ni * tiles_j + nj, 1u);
+  }
+}
+
+// after the call's last round: settled[f] = no flag of field f set in `live`; with `swap` the flags move to array 0, where the
+// next call's first round reads them.  blockIdx.x = field.
+__global__ void __launch_bounds__(SETUP_THREADS) tiled_settle_kernel(int tiles, int swap, uint32_t* flags0, uint32_t* flags1,
+                                                                     int32_t* __restrict__ settled) {
+  const int64_t f = blockIdx.x;
+  uint32_t *a0 = flags0 + f * tiles, *a1 = flags1 + f * tiles;
+  int any = 0;
+  for (int t = threadIdx.x; t < tiles; t += SETUP_THREADS) {
+    const uint32_t v = swap ? a1[t] : a0[t];
+    if (swap) { a0[t] = v; a1[t] = 0; }
+    any |= v != 0;
+  }
+  any = __syncthreads_or(any);
+  if (threadIdx.x == 0) settled[f] = !any;
+}
+
+__global__ void __launch_bounds__(PATH_THREADS) tiled_goal_descent_kernel(int64_t B, int one_field, int W, int H, int64_t occ_stride,
+                                                                          double ox, double oy, double dx, double dy,
+                                                                          const uint8_t* __restrict__ occ,
+                                                                          const uint32_t* __restrict__ field,
+                                                                          const int32_t* __restrict__ field_status,
+                                                                          const int32_t* __restrict__ settled,
+                                                                          const double* __restrict__ goal, const double* __restrict__ start,
+                                                                          int r_inflate, int max_seg, int S_max,
+                                                                          double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+                                                                          int32_t* __restrict__ status, double* __restrict__ path_cost) {
+  grid_path_body(B, one_field, W, H, occ_stride, ox, oy, dx, dy, occ, field, field_status, settled, goal, start, r_inflate, max_seg, S_max,
+                 sub_goals, n_sub, status, path_cost);
+}
+
+__global__ void __launch_bounds__(PATH_THREADS) tiled_frontier_descent_kernel(int64_t B, int one_field, int W, int H, double ox, double oy,
+                                                                              double dx, double dy, const int32_t* __restrict__ evidence,
+                                                                              int t_occ, const uint32_t* __restrict__ field,
+                                                                              const int32_t* __restrict__ n_frontier,
+                                                                              const int32_t* __restrict__ settled,
+                                                                              const double* __restrict__ start, int r_inflate, int max_seg,
+                                                                              int S_max, double* __restrict__ sub_goals,
+                                                                              int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
+                                                                              double* __restrict__ path_cost,
+                                                                              int32_t* __restrict__ target_cell) {
+  frontier_path_body(B, one_field, W, H, ox, oy, dx, dy, evidence, t_occ, field, n_frontier, settled, start, r_inflate, max_seg, S_max,
+                     sub_goals, n_sub, status, path_cost, target_cell);
+}
+
+// the tiled calls' caps, after every E_ARG
+int tiled_cap_refusal(int64_t F, int32_t W, int32_t H) {
+  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > TILED_MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (F > 0 && F * ((int64_t)W * H + 64) > TILED_MAX_THREADS) return LIPMPC_E_UNSUPPORTED;
+  return LIPMPC_OK;
+}
+
+// what the two tiled field calls add to their refusals: E_ARG, then the caps; a `work` too small for a shape within the caps is
+// E_ARG (beyond them no size is defined)
+int tiled_refusal(int64_t F, int32_t W, int32_t H, const void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume,
+                  const int32_t* settled) {
+  if (!work || !settled || max_rounds < 1 || max_rounds > MAX_ROUNDS || (resume != 0 && resume != 1)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  return work_bytes < tiled_bytes(F, W, H) ? LIPMPC_E_ARG : LIPMPC_OK;
+}
+
+// the rounds and the settle kernel
+int tiled_rounds(hipStream_t s, int64_t F, int W, int H, int64_t blk_stride, const TiledLayout& l, uint32_t* work, uint32_t* field,
+                 int max_rounds, int32_t* settled) {
+  const int tiles = (int)l.tiles, tiles_j = tiles_along(H, TILE_H);
+  uint32_t* flags[2] = {work + l.flags0, work + l.flags1};
+  for (int r = 0; r < max_rounds; ++r)
+    hipLaunchKernelGGL(tiled_round_kernel, dim3((unsigned)(F * tiles)), dim3(TILE_THREADS), 0, s, W, H, tiles_j, tiles, blk_stride,
+                       work + l.blocked, field, flags[r & 1], flags[(r + 1) & 1]);
+  hipLaunchKernelGGL(tiled_settle_kernel, dim3((unsigned)F), dim3(SETUP_THREADS), 0, s, tiles, max_rounds & 1, flags[0], flags[1], settled);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+}  // namespace
+
+extern "C" int lipmpc_grid_tiled_info(int32_t* tile_w, int32_t* tile_h, int64_t* max_cells) {
+  if (!tile_w || !tile_h || !max_cells) return LIPMPC_E_ARG;
+  *tile_w = TILE_W;
+  *tile_h = TILE_H;
+  *max_cells = TILED_MAX_CELLS;
+  return LIPMPC_OK;
+}
+
+extern "C" int64_t lipmpc_grid_tiled_workspace_bytes(int64_t F, int32_t W, int32_t H) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  return tiled_bytes(F, W, H);
+}
+
+extern "C" int lipmpc_grid_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin,
+                                             const double* cell, const uint8_t* occ, const double* goal, int32_t r_inflate,
+                                             uint32_t* field, int32_t* field_status, void* work, int64_t work_bytes, int32_t max_rounds,
+                                             int32_t resume, int32_t* settled, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
+    return LIPMPC_E_ARG;
+  if (!occ || !goal || !field || !field_status) return LIPMPC_E_ARG;
+  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const TiledLayout l = tiled_layout(F, W, H);
+  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  const int64_t maps = grid_shared ? 1 : F, blk_stride = grid_shared ? 0 : l.bm_words;
+  uint32_t* w = (uint32_t*)work;
+  if (!resume) {
+    hipLaunchKernelGGL(tiled_bitmaps_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles, occ,
+                       (const int32_t*)nullptr, 0, 0, w + l.solid, w + l.unknown, w + l.flags0, (int32_t*)nullptr);
+    hipLaunchKernelGGL(tiled_blocked_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
+                       w + l.solid, w + l.unknown, w + l.blocked);
+    hipLaunchKernelGGL(tiled_goal_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, blk_stride, ox, oy, dx,
+                       dy, goal, w + l.blocked, field, field_status, w + l.flags0, l.tiles);
+  }
+  return tiled_rounds(s, F, W, H, blk_stride, l, w, field, max_rounds, settled);
+}
+
+extern "C" int lipmpc_grid_frontier_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                                      int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier,
+                                                      uint32_t* field, int32_t* n_frontier, void* work, int64_t work_bytes,
+                                                      int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
+      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || !field || !n_frontier)
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const TiledLayout l = tiled_layout(F, W, H);
+  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  uint32_t* w = (uint32_t*)work;
+  if (!resume) {
+    hipLaunchKernelGGL(tiled_bitmaps_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles,
+                       (const uint8_t*)nullptr, evidence, t_free, t_occ, w + l.solid, w + l.unknown, w + l.flags0, n_frontier);
+    hipLaunchKernelGGL(tiled_blocked_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
+                       w + l.solid, w + l.unknown, w + l.blocked);
+    hipLaunchKernelGGL(tiled_frontier_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, min_unknown,
+                       w + l.unknown, w + l.blocked, frontier, field, n_frontier, w + l.flags0, l.tiles);
+  }
+  return tiled_rounds(s, F, W, H, l.bm_words, l, w, field, max_rounds, settled);
+}
+
+extern "C" int lipmpc_grid_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell,
+                                            const uint8_t* occ, int32_t grid_shared, const uint32_t* field, const int32_t* field_status,
+                                            const int32_t* settled, const double* goal, const double* start, int32_t r_inflate,
+                                            int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                            double* path_cost, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (!occ || !field || !field_status || !settled || !goal || !start || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(tiled_goal_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, ox, oy, dx, dy, occ, field,
+                     field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                                     const double* cell, const int32_t* evidence, int32_t t_occ, const uint32_t* field,
+                                                     const int32_t* n_frontier, const int32_t* settled, const double* start,
+                                                     int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
+                                                     int32_t* status, double* path_cost, int32_t* target_cell, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (!evidence || !field || !n_frontier || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell)
+    return LIPMPC_E_ARG;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(tiled_frontier_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, ox, oy, dx, dy, evidence, t_occ, field, n_frontier, settled, start,
+                     r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

@@ -545,7 +545,8 @@ class UnknownEnvFleet:
             at its final goal, or on a failed solve, stays stopped);
           - each robot's working goal becomes the first sub-goal of its path that is at least ``lookahead`` from the robot, or
             the final goal when none is or when the plan's status is anything other than RRT_FOUND (RRT_NO_OBSTACLE_GRID
-            included: the map is empty, the robot heads straight for the goal).
+            included: the map is empty, the robot heads straight for the goal; RRT_FIELD_UNSETTLED included: a tiled planner
+            whose budget of rounds did not settle the field -- the next replan tries again).
         Returns what ``run`` returns, plus n_replans (int), rrt_status [B] of the last plan, working_goal [B,2] and walking [B]
         (int8) as the last sample left them: a robot ARRIVED if it is not walking, its last_status is SOLVED or UNCERTIFIED
         (the stop rule stopped it, not a failed solve) and its working goal is its final goal."""
@@ -592,7 +593,9 @@ class UnknownEnvFleet:
             from it, or the frontier cell's centre when none is (``select_working_goals`` with its target as the goal);
           - a robot that is not walking, whose last_status is SOLVED or UNCERTIFIED, and whose plan is FOUND walks again: robots
             the stop rule stopped and robots parked earlier (a robot stopped by a failed solve stays stopped, as everywhere);
-          - a robot whose plan is not FOUND is parked (walking = 0; it keeps its working goal).
+          - a robot whose plan is not FOUND is parked (walking = 0; it keeps its working goal).  That holds for
+            RRT_FIELD_UNSETTLED too (a ``FrontierPlanner(tiled=True, rounds=n)`` whose budget did not settle the field): the robot
+            walks again after a replan that settles, and since ``done`` reads RRT_NO_PATH only it never ends the fleet.
         After the last sample one closing plan on the final map and positions parks likewise and sets no goal; it is not counted.
         With a ``CoordinatedFrontierPlanner`` as ``explorer`` the robots claim frontier targets apart in every replan: the robots
         that may claim are those whose last_status is SOLVED or UNCERTIFIED -- a robot stopped for good by a failed solve must

@@ -29,13 +29,85 @@ from . import _lib
 from .solver import _alloc, _check_table, _named, pack_rings
 
 RRT_FOUND, RRT_NO_PATH, RRT_START_OCCUPIED, RRT_GOAL_OCCUPIED, RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, \
-    RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID = range(8)
+    RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID, RRT_FIELD_UNSETTLED = range(9)
 RRT_STATUS_NAMES = ("FOUND", "NO_PATH", "START_OCCUPIED", "GOAL_OCCUPIED", "GRID_TOO_LARGE", "NO_OBSTACLE_GRID",
-                    "PATH_OVERFLOW", "OUTSIDE_GRID")
+                    "PATH_OVERFLOW", "OUTSIDE_GRID", "FIELD_UNSETTLED")
 
 
 FIELD_INF = 0xFFFFFFFF      # LIPMPC_FIELD_INF: a cell of a field that is blocked or has no path to the goal
 FIELD_NO_CAP = 0x7FFFFFFF   # max_seg of "no spacing cap": no field value reaches it (a field stays below 7 * 2^17)
+
+
+def tiled_info():
+    """(tile_w, tile_h, max_cells) of the tiled field calls (lipmpc_grid_tiled_info): a tile's cells along i and along j, and the
+    cap on W * H.  Host only."""
+    tw, th, cap = C.c_int32(), C.c_int32(), C.c_int64()
+    _lib.call("lipmpc_grid_tiled_info", tile_w=C.addressof(tw), tile_h=C.addressof(th), max_cells=C.addressof(cap))
+    return tw.value, th.value, cap.value
+
+
+class _TiledKeywords(type):
+    """The keyword-only ``tiled`` / ``rounds`` of the two field planners, taken off before ``__init__`` runs: the classes'
+    ``__init__`` signatures -- which callers hand on positionally and through ``**kwargs`` -- stay what they were."""
+
+    def __call__(cls, *args, tiled: bool = False, rounds: int | None = None, **kwargs):
+        self = cls.__new__(cls)
+        self._init_tiled(tiled, rounds)
+        self.__init__(*args, **kwargs)
+        return self
+
+
+class _TiledRounds(metaclass=_TiledKeywords):
+    """What ``GridFieldPlanner`` and ``FrontierPlanner`` share with ``tiled=True``: the workspace of the tiled field calls (grown
+    only, every buffer kept alive: work enqueued on an earlier one may still run; never reallocated while the stream is capturing)
+    and the rounds.  ``rounds`` = an int: ONE call with that budget, no synchronisation, capturable; None: a budget from the
+    round guarantee for an open map, then resumes with a doubled budget until every field is settled -- ``settled`` is read on the
+    host, so this raises under stream capture."""
+
+    _TILED = True               # False: a subclass whose further calls keep the one-workgroup cap
+
+    def _init_tiled(self, tiled, rounds):
+        self.tiled, self.rounds = bool(tiled), None if rounds is None else int(rounds)
+        if self.tiled and not self._TILED:
+            raise ValueError(f"{type(self).__name__}: tiled=True is not supported ({self._TILED_WHY} the cap of 2^17 cells)")
+        if self.rounds is not None and (not self.tiled or not 1 <= self.rounds <= 65536):
+            raise ValueError(f"rounds {rounds}: 1..65536 or None, with tiled=True only")
+        self._works = []            # every workspace ever handed to a call; the last one is the current one
+
+    def _settled(self, out, F):
+        """out["settled"] [F] int32, made if the caller's dict has none."""
+        t = out.get("settled")
+        if t is None:
+            t = out["settled"] = torch.empty((F,), dtype=torch.int32, device=self.device)
+        elif t.shape != (F,) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"out['settled'] must be a contiguous int32 tensor [{F}] on the planner's device")
+        return t
+
+    def _run_tiled(self, name, F, W, H, out, **args):
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self.rounds is None and capturing:
+            raise RuntimeError("rounds=None reads `settled` on the host: give the planner a fixed `rounds` to capture its calls")
+        need = int(self.lib.lipmpc_grid_tiled_workspace_bytes(F, W, H))
+        if need < 0:
+            _lib.check(need, "lipmpc_grid_tiled_workspace_bytes")
+        if not self._works or self._works[-1].numel() < need:
+            if capturing:
+                raise RuntimeError("the tiled workspace must grow: run the call once before the capture")
+            self._works.append(torch.empty(need, dtype=torch.uint8, device=self.device))
+        work, settled = self._works[-1], self._settled(out, F)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+
+        def call(budget, resume):
+            _lib.call(name, device=self.device_index, F=F, W=W, H=H, **args, work=work, work_bytes=work.numel(), max_rounds=budget,
+                      resume=resume, settled=settled, hip_stream=stream)
+        if self.rounds is not None:
+            return call(self.rounds, 0)
+        tw, th, _ = tiled_info()
+        budget = max(8, -(-W // tw) - (-H // th) + 1)
+        call(budget, 0)
+        while F and not bool(settled.all()):           # (ends: every round but the last lowers a word, and words are bounded below)
+            budget = min(2 * budget, 65536)
+            call(budget, 1)
 
 
 def field_plan_outputs(B, F, W, H, S_max):
@@ -247,14 +319,19 @@ class RrtStarPlanner:
         return out["sub_goals"][0, :n].cpu().numpy()
 
 
-class GridFieldPlanner:
+class GridFieldPlanner(_TiledRounds):
     """A complete, deterministic planner on a GIVEN occupancy grid (include/lipmpc.h, GRID FIELD PLANNER): the cost-to-go field
     from the goal over the 8-connected unblocked cells (axial step 5, diagonal 7, no corner cut), then per robot a descent down
     the field, pulled taut into sub-goals.  A path that exists is found and is a shortest one in that metric; there is no seed;
     one field serves every robot that shares the map and the goal.
     ``r_inflate``: cells within this many cells (Euclidean) of a solid cell are blocked, 0..16 -- the body radius over the cell
     size, rounded up.  ``max_seg``: the sub-goals' spacing cap in field units (5 per cell), >= 5; None = no cap.
-    Ring maps: plan on ``GridMap.from_planner(...)``."""
+    Ring maps: plan on ``GridMap.from_planner(...)``.
+    Keyword-only ``tiled`` / ``rounds``.  ``tiled=False``: one workgroup per field, maps of up to 2^17 cells (above: E_UNSUPPORTED).  ``tiled=True``: the tiled calls at
+    every map size, up to 2^24 cells (include/lipmpc.h, TILED FIELDS) -- the same field bit for bit once ``settled``; ``rounds`` as
+    ``_TiledRounds`` says; ``field()`` and ``plan_grid_batch()`` then return ``settled`` [F] too, and a robot whose field is not
+    settled gets RRT_FIELD_UNSETTLED and no sub-goal.  ``UnknownEnvFleet.run_replanning`` treats that status as every status other
+    than RRT_FOUND: until a later replan settles the robot's working goal is its final goal, and nothing ends the run."""
 
     def __init__(self, r_inflate: int = 0, max_seg: int | None = None, device: int | None = None):
         if not torch.cuda.is_available():
@@ -275,6 +352,10 @@ class GridFieldPlanner:
         return goal
 
     def _field(self, goal, grid, out):
+        if self.tiled:
+            ga = grid._args(goal.shape[0], self.device)
+            return self._run_tiled("lipmpc_grid_field_tiled_batch", goal.shape[0], ga.pop("W"), ga.pop("H"), out, **ga, goal=goal,
+                                   r_inflate=self.r_inflate, field=out["field"], field_status=out["field_status"])
         _lib.call("lipmpc_grid_field_batch", device=self.device_index, F=goal.shape[0], **grid._args(goal.shape[0], self.device), goal=goal,
                   r_inflate=self.r_inflate, field=out["field"], field_status=out["field_status"],
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
@@ -293,6 +374,8 @@ class GridFieldPlanner:
         else:
             _check_table({k: table[k] for k in names}, out, self.device, "out")
         self._field(goal, grid, out)
+        if self.tiled:
+            return dict(field=out["field"], status=out["field_status"], settled=out["settled"])
         return dict(field=out["field"], status=out["field_status"])
 
     def plan_grid_batch(self, goal, grid, start, S_max: int | None = 64, seeds=None, out=None):
@@ -318,18 +401,22 @@ class GridFieldPlanner:
             out.update(_alloc(table, ("field", "field_status"), self.device))            # written whole by the field call
         else:
             _check_table(table, out, self.device, "out")
+        if self.tiled:
+            self._settled(out, F)
         if B == 0:
             return out
         self._field(goal, grid, out)
         ga = grid._args(F, self.device)
-        _lib.call("lipmpc_grid_path_batch", device=self.device_index, B=B, F=F, **ga, field=out["field"], field_status=out["field_status"],
+        path = dict(lipmpc_grid_path_tiled_batch=dict(settled=out["settled"])) if self.tiled else dict(lipmpc_grid_path_batch={})
+        (name, more), = path.items()
+        _lib.call(name, device=self.device_index, B=B, F=F, **ga, **more, field=out["field"], field_status=out["field_status"],
                   goal=goal, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost")), hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
         self.last = out
         return out
 
 
-class FrontierPlanner:
+class FrontierPlanner(_TiledRounds):
     """Nearest-frontier exploration (Yamauchi 1997) on an evidence grid (include/lipmpc.h, FRONTIER EXPLORER): a cell is solid
     with evidence >= ``t_occ``, free with evidence <= -``t_free`` and unknown otherwise; a FRONTIER cell is an unblocked cell with
     at least ``min_unknown`` unknown cells among its 8 neighbours; the field is the cost-to-go to the nearest frontier cell over the
@@ -342,7 +429,11 @@ class FrontierPlanner:
     nothing (``InformedFrontierPlanner`` weighs what a cell would show) -- and n_frontier == 0 (status RRT_NO_PATH
     for everybody) is how "nothing left to explore" is told.  The walker that follows these goals cannot turn on the spot while
     walking: a goal that jumps behind it can make its solve INFEASIBLE, which costs the robot a capture step in a fleet with
-    ``recover`` and its run in one without."""
+    ``recover`` and its run in one without.
+    Keyword-only ``tiled`` / ``rounds``: as ``GridFieldPlanner``'s -- the tiled calls at every map size up to 2^24 cells, ``settled`` [F] in the
+    dicts of ``field()`` and ``plan()``, RRT_FIELD_UNSETTLED (target_cell -1, target NaN) for a robot whose field is not settled.
+    ``UnknownEnvFleet.run_exploring`` needs no change: its ``done`` reads RRT_NO_PATH only, so a robot whose replan came back
+    unsettled is parked until a later replan settles, and never ends the fleet."""
 
     def __init__(self, r_inflate: int = 2, min_unknown: int = 2, t_free: int | None = None, t_occ: int | None = None,
                  max_seg: int | None = None, device: int | None = None):
@@ -378,6 +469,10 @@ class FrontierPlanner:
 
     def _field(self, ev, t_free, t_occ, out):
         F, W, H = ev.shape
+        if self.tiled:
+            return self._run_tiled("lipmpc_grid_frontier_field_tiled_batch", F, W, H, out, evidence=ev, t_free=t_free, t_occ=t_occ,
+                                   r_inflate=self.r_inflate, min_unknown=self.min_unknown, frontier=out["frontier"], field=out["field"],
+                                   n_frontier=out["n_frontier"])
         _lib.call("lipmpc_grid_frontier_field_batch", device=self.device_index, F=F, W=W, H=H, evidence=ev, t_free=t_free, t_occ=t_occ,
                   r_inflate=self.r_inflate, min_unknown=self.min_unknown, frontier=out["frontier"], field=out["field"],
                   n_frontier=out["n_frontier"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
@@ -394,7 +489,7 @@ class FrontierPlanner:
         else:
             _check_table({k: table[k] for k in names}, out, self.device, "out")
         self._field(ev, t_free, t_occ, out)
-        return {k: out[k] for k in names}
+        return {k: out[k] for k in names + (("settled",) if self.tiled else ())}
 
     def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None):
         """Plan B robots from ``start`` [B,2] to their nearest frontier: on a shared map (a mapper without ``per_robot``, an
@@ -419,10 +514,15 @@ class FrontierPlanner:
             out.update(_alloc(table, ("field", "frontier", "n_frontier"), self.device))      # written whole by the field call
         else:
             _check_table(table, out, self.device, "out")
+        if self.tiled:
+            self._settled(out, F)
         if B == 0:
             return out
         self._field(ev, t_free, t_occ, out)
-        _lib.call("lipmpc_grid_frontier_path_batch", device=self.device_index, B=B, F=F, W=W, H=H, origin=C.addressof(org_c),
+        path = dict(lipmpc_grid_frontier_path_tiled_batch=dict(settled=out["settled"])) if self.tiled else \
+            dict(lipmpc_grid_frontier_path_batch={})
+        (name, more), = path.items()
+        _lib.call(name, device=self.device_index, B=B, F=F, W=W, H=H, origin=C.addressof(org_c), **more,
                   cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ, field=out["field"], n_frontier=out["n_frontier"], start=start,
                   r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell")),
@@ -462,6 +562,8 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     The model's limits: a round is sequential by nature -- one relaxation of the whole map per claim, in one workgroup; robots
     that are left when the frontier or ``max_claims`` is used up are FOLLOWERS, who keep their plain nearest-frontier plan and so
     share a target; there is no memory between plans, so a replan may hand a robot another target than the last one."""
+
+    _TILED, _TILED_WHY = False, "the claim rounds keep"
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
         self.r_claim, self.max_claims = int(r_claim), int(max_claims)
@@ -522,6 +624,8 @@ class InformedFrontierPlanner(FrontierPlanner):
     one.  The other arguments are ``FrontierPlanner``'s.
     The model's limits: unknown cells do not occlude; there is no memory between plans (no hysteresis), so a replan may hand a robot
     another target; a shared field sends robots that stand together to the same cell, as the parent does."""
+
+    _TILED, _TILED_WHY = False, "the gain call and the utility field keep"
 
     def __init__(self, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, **frontier_planner_kwargs):
         self.r_view, self.w_gain, self.g_cap, self.min_gain = int(r_view), int(w_gain), int(g_cap), int(min_gain)

@@ -40,7 +40,11 @@ extern "C" {
                                 *    + lipmpc_grid_field_batch / lipmpc_grid_path_batch;
                                 *    + lipmpc_grid_frontier_field_batch / lipmpc_grid_frontier_path_batch;
                                 *    + lipmpc_lidar_c_eta_split_batch / lipmpc_lidar_grid_c_eta_split_batch;
-                                *    + lipmpc_fleet_recover_update_batch; + lipmpc_grid_frontier_assign_batch */
+                                *    + lipmpc_fleet_recover_update_batch; + lipmpc_grid_frontier_assign_batch;
+                                *    + lipmpc_grid_tiled_info / lipmpc_grid_tiled_workspace_bytes /
+                                *      lipmpc_grid_field_tiled_batch / lipmpc_grid_frontier_field_tiled_batch /
+                                *      lipmpc_grid_path_tiled_batch / lipmpc_grid_frontier_path_tiled_batch,
+                                *      LIPMPC_RRT_FIELD_UNSETTLED */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -556,6 +560,7 @@ int lipmpc_map_update_batch(int device, int64_t B, int32_t resolution, int32_t W
 #define LIPMPC_RRT_NO_OBSTACLE_GRID 5  /* no occupied cell: the distance transform is not defined */
 #define LIPMPC_RRT_PATH_OVERFLOW    6  /* the path has more than S_max sub-goals (path_cost is still written) */
 #define LIPMPC_RRT_OUTSIDE_GRID     7  /* lipmpc_rrt_plan_grid_batch only: the start or the goal rounds to a cell outside the given grid */
+#define LIPMPC_RRT_FIELD_UNSETTLED  8  /* the tiled path calls only: the robot's field has settled == 0 (more rounds are needed) */
 
 typedef struct lipmpc_rrt_params {
   int32_t width;        /* W, grid cells across x minus one: 1..4095           (width_grid_size, :102) */
@@ -883,6 +888,83 @@ int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, int64_t F, in
                                             int32_t g_cap, int32_t min_gain, const double* start, int32_t r_inflate, int32_t max_seg,
                                             int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                             int32_t* target_cell, int32_t* target_gain, void* hip_stream);
+
+/* TILED FIELDS (backward-compatible addition): the two cost-to-go fields above on LARGE maps, relaxed by many workgroups.  The
+ * four calls above keep their cap of 2^17 cells and their one workgroup per field; the calls here take any map with
+ * W * H <= 2^24 and W, H <= 4096 (a finite field value stays below 7 * 2^24), and compute THE SAME FIELD, bit for bit: the
+ * least cost is unique.  The map is cut into tiles of tile_w x tile_h cells (along i and along j; lipmpc_grid_tiled_info).  The
+ * calls' set-up kernels (bitmaps, the blocked bitmap by the disc test, seeds, tile flags, n_frontier, statuses) run one
+ * workgroup per 256 cells; then a call enqueues ROUNDS.  One round is one kernel launch with one workgroup per (field, tile): a
+ * tile that is not marked active returns at once; an active tile stages its field words and blocked bits with a one-cell halo in
+ * LDS, relaxes its cells to the local fixed point with the halo held, writes back the cells that fell and marks the
+ * neighbouring tiles behind every part of its rim on which a cell fell active for the next round.  Workgroups are ordered by
+ * the kernel boundaries on hip_stream and by nothing else: there is no cooperative launch, no grid barrier and no loop in which
+ * one workgroup waits for another.  The device cannot end the rounds early, so the CALLER sets the budget: max_rounds rounds are
+ * enqueued, and settled[f] tells whether they were enough.
+ *
+ * lipmpc_grid_tiled_info: *tile_w = the tile's cells along i, *tile_h = along j, *max_cells = 2^24.  Host only.  LIPMPC_E_ARG:
+ *  a null pointer.
+ * lipmpc_grid_tiled_workspace_bytes: the bytes of `work` for F fields on a W x H map; non-decreasing in F, in W and in H.  Host
+ *  only.  LIPMPC_E_ARG (as a negative value): F < 0, W or H < 2; LIPMPC_E_UNSUPPORTED: a shape the field calls refuse.
+ *
+ * lipmpc_grid_field_tiled_batch: lipmpc_grid_field_batch's arguments, contract and outputs, and
+ *  work, work_bytes  a device buffer of at least lipmpc_grid_tiled_workspace_bytes(F, W, H) bytes
+ *  max_rounds  1..65536: the rounds this call enqueues
+ *  resume      0: a COLD call -- it initialises everything it reads: the previous contents of work, field, field_status and
+ *              settled are arbitrary.  1: work and field are as the previous call WITH THE SAME ARGUMENTS left them (same
+ *              buffers, F, W, H, map, goal, r_inflate; stream-ordered after it); max_rounds more rounds are enqueued.
+ *              field_status is written by a cold call only.
+ *  settled     [F] int32: 1 <=> no tile of field f is marked active after the call's last round
+ * WHAT HOLDS AFTER A CALL:
+ *  - settled[f] == 1: field f is lipmpc_grid_field_batch's, bit for bit, and field_status[f] is that call's.  A resume on a
+ *    settled field changes no bit of it.
+ *  - settled[f] == 0: every finite word of field f is the cost of a real path from that cell to the goal cell, so >= the final
+ *    value, and it IS the final value wherever the round guarantee says so.  Blocked cells hold INF.
+ *  - THE ROUND GUARANTEE: after R rounds in total (the cold call's and every resume's), a cell holds its final value if some
+ *    least-cost path from it to a source (the goal cell; a frontier cell) changes tile at most R - 1 times.  On an open W x H
+ *    map ceil(W / tile_w) + ceil(H / tile_h) rounds therefore settle every cell's VALUE; settled itself may take a round more,
+ *    in which nothing falls.
+ *  - A diagonal move is judged on the blocked state of its two side cells (the contract's rule), never on whether their field
+ *    words are finite yet: that is what makes the guarantee exact.
+ *  - Two cold calls give identical bits in field, field_status and settled; with settled == 0 the FIELD's bits may differ
+ *    between two runs (a halo word read in the round in which its owner lowers it may be the old or the new one), its settled
+ *    cells, as guaranteed above, do not.
+ * No allocation, no host synchronisation, capturable in a graph; every refusal is decided on the host before anything is
+ * enqueued.  LIPMPC_E_ARG: what lipmpc_grid_field_batch refuses as such, a null occ / goal / field / field_status / work /
+ *  settled (whatever F), max_rounds outside 1..65536, resume neither 0 nor 1.  Then LIPMPC_E_UNSUPPORTED: W * H > 2^24, W > 4096,
+ *  H > 4096, or F * (W * H + 64) > 2^31 (the threads of one launch).  Then LIPMPC_E_ARG: work_bytes below
+ *  lipmpc_grid_tiled_workspace_bytes(F, W, H).  Then F = 0 enqueues nothing and returns 0.
+ *
+ * lipmpc_grid_frontier_field_tiled_batch: the same over lipmpc_grid_frontier_field_batch's arguments, contract and outputs
+ *  (frontier, field, n_frontier; frontier and n_frontier are written by a cold call only).  A map with n_frontier == 0 is settled
+ *  before the first round.  Refusals as above, with lipmpc_grid_frontier_field_batch's LIPMPC_E_ARG cases.
+ *
+ * lipmpc_grid_path_tiled_batch, lipmpc_grid_frontier_path_tiled_batch: lipmpc_grid_path_batch and
+ *  lipmpc_grid_frontier_path_batch word for word, with the cap above instead of theirs, and one more input:
+ *  settled [F] int32, the field call's output.  A robot whose field has settled[f] == 0 gets LIPMPC_RRT_FIELD_UNSETTLED BEFORE
+ *  any other rule, with n_sub = 0, path_cost = NaN, target_cell = -1 (the frontier call) and nothing else written: no path is
+ *  walked down a field that may still change.  LIPMPC_E_ARG and B = 0 as those calls, a null settled included;
+ *  LIPMPC_E_UNSUPPORTED as the tiled field calls. */
+int lipmpc_grid_tiled_info(int32_t* tile_w, int32_t* tile_h, int64_t* max_cells);
+int64_t lipmpc_grid_tiled_workspace_bytes(int64_t F, int32_t W, int32_t H);
+int lipmpc_grid_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin,
+                                  const double* cell, const uint8_t* occ, const double* goal, int32_t r_inflate, uint32_t* field,
+                                  int32_t* field_status, void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume,
+                                  int32_t* settled, void* hip_stream);
+int lipmpc_grid_frontier_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                           int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier,
+                                           uint32_t* field, int32_t* n_frontier, void* work, int64_t work_bytes,
+                                           int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream);
+int lipmpc_grid_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell,
+                                 const uint8_t* occ, int32_t grid_shared, const uint32_t* field, const int32_t* field_status,
+                                 const int32_t* settled, const double* goal, const double* start, int32_t r_inflate,
+                                 int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                 double* path_cost, void* hip_stream);
+int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                          const double* cell, const int32_t* evidence, int32_t t_occ, const uint32_t* field,
+                                          const int32_t* n_frontier, const int32_t* settled, const double* start,
+                                          int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
+                                          int32_t* status, double* path_cost, int32_t* target_cell, void* hip_stream);
 
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
