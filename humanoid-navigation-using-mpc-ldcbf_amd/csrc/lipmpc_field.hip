@@ -21,6 +21,12 @@
 // at the end of this file:
 //   tiled_*_kernel                set-up by many workgroups, then ROUNDS of one workgroup per (field, tile) that relax a tile in LDS with
 //                                 a one-cell halo held, ordered by kernel boundaries alone; the path kernels with one more rule in front.
+// and the informed and the coordinated explorer on LARGE maps (lipmpc_grid_frontier_gain_tiled_batch,
+// lipmpc_grid_frontier_utility_field_tiled_batch, lipmpc_grid_frontier_utility_path_tiled_batch,
+// lipmpc_grid_frontier_assign_tiled_batch), after them:
+//   tile_gain_kernel              one workgroup per (map, tile): the fan against bitmaps of the tile grown by r_view.
+//   tile_utility_*_kernel         the utility field's seeds for the rounds above; the path kernel with one more rule in front.
+//   claim_*_kernel                frontier_assign_*_kernel's rounds cut into kernels, each round's field relaxed by the rounds above.
 // Everything the kernels compare is an integer but the two floors that name a cell; the cell centres are one multiply and
 // one add, contraction off.  tests/field_oracle.py restates both contracts (Dijkstra) and the GPU tests hold every output to it
 // bit for bit.
@@ -929,6 +935,7 @@ __device__ inline int walk_to(const uint32_t* __restrict__ fld, int W, int H, in
 }
 
 // One lane per robot: frontier_path_kernel down a utility field, to the centre of the first terminal cell reached.
+// (tile_utility_descent_kernel, further down, holds a COPY of this body behind one more rule: a fix here belongs there too.)
 __global__ void __launch_bounds__(PATH_THREADS) frontier_utility_path_kernel(
     int64_t B, int one_field, int W, int H, double ox, double oy, double dx, double dy, const int32_t* __restrict__ evidence, int t_occ,
     const uint8_t* __restrict__ frontier, const int32_t* __restrict__ gain, const uint32_t* __restrict__ ufield,
@@ -1619,5 +1626,498 @@ extern "C" int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int6
   hipLaunchKernelGGL(tiled_frontier_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
                      (hipStream_t)hip_stream, B, (int)(F == 1), W, H, ox, oy, dx, dy, evidence, t_occ, field, n_frontier, settled, start,
                      r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+// =====================================================================================================================
+// THE INFORMED AND THE COORDINATED EXPLORER ON LARGE MAPS (lipmpc_grid_frontier_gain_tiled_batch,
+// lipmpc_grid_frontier_utility_field_tiled_batch, lipmpc_grid_frontier_utility_path_tiled_batch,
+// lipmpc_grid_frontier_assign_tiled_batch): the gain by one workgroup per tile against bitmaps of the tile grown by r_view, the
+// utility field and every claim round's field by the rounds above.
+//
+// WHY "UNBLOCKED" IS THE ONE-WORKGROUP CALLS' "field != INF".  The one-workgroup utility call takes passable(c) <=> the settled
+// nearest-frontier field is finite at c; the tiled one takes the blocked bit, and needs no settled field.  (1) A frontier cell is
+// unblocked and holds 0 in that field, so it is passable under both rules: the sources are the same.  (2) An unblocked cell that is
+// INF in that field reaches no frontier cell by legal moves, hence no source: it is INF in either utility field, and no move
+// through it lowers any other cell.  (3) A diagonal's side cell is an axial neighbour of the diagonal's target; if it is
+// unblocked it is finite wherever the target is, so judging diagonals on blocked bits or on finite words allows the same moves
+// among the cells that reach a source.  Both rules have the same fixed point, which is unique.
+namespace {
+
+constexpr int TILE_CELLS = TILE_W * TILE_H;
+
+// LDS of the tiled gain kernel: the solid and unknown bitmaps of the tile grown by r_view on every side, the tile's frontier
+// count (a word pair), the tile's frontier cells, one window per wave -- bounded by r_view, whatever the map: 49,304 bytes at 64
+__host__ __device__ inline int64_t tile_gain_lds_bytes(int r_view) {
+  const int64_t grown = (int64_t)(TILE_W + 2 * r_view) * (TILE_H + 2 * r_view);
+  return 4 * (2 * bitmap_words(grown) + 2 + TILE_CELLS + GAIN_WAVES * gain_window_words(r_view));
+}
+
+// frontier_gain_kernel by tiles: blockIdx.x = map * tiles + tile.  A tile without a frontier cell writes its zeros and returns;
+// any other classifies the evidence of the grown tile (a cell outside the grid counts as solid: it ends a ray as the grid's edge
+// does), then marches as that kernel does, on local indices l = (i - i0 + r) * (TILE_H + 2 r) + j - j0 + r.  A ray from a cell
+// of the tile stays within r of it, hence inside the grown tile.
+__global__ void __launch_bounds__(GAIN_THREADS) tile_gain_kernel(int W, int H, int tiles_j, int tiles, const int32_t* __restrict__ evidence,
+                                                                 int t_free, int t_occ, const uint8_t* __restrict__ frontier, int r_view,
+                                                                 int32_t* __restrict__ gain) {
+  extern __shared__ uint32_t field_lds[];
+  const int64_t f = blockIdx.x / tiles;
+  const int tile = blockIdx.x - (int)f * tiles, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  const int r = r_view, lh = TILE_H + 2 * r, grown = (TILE_W + 2 * r) * lh;
+  const int words = (int)bitmap_words(grown), padded = (words - 2) * 32, ww = (int)gain_window_words(r);
+  uint32_t *solid = field_lds, *unk = field_lds + words, *count = field_lds + 2 * words, *list = count + 2;
+  uint32_t* win = list + TILE_CELLS + wave * ww;
+  const int64_t ncells = (int64_t)W * H;
+  const int32_t* ev = evidence + f * ncells;
+  const uint8_t* fr = frontier + f * ncells;
+  int32_t* out = gain + f * ncells;
+
+  if (tid == 0) *count = 0;
+  __syncthreads();
+  // the tile's frontier cells, as local cells li * TILE_H + lj (in whatever order: each cell's gain is its own)
+  for (int t = tid; t < TILE_CELLS; t += GAIN_THREADS) {
+    const int i = i0 + t / TILE_H, j = j0 + t % TILE_H;
+    if (i < W && j < H) {
+      if (fr[i * H + j] != 0) list[atomicAdd(count, 1u)] = (uint32_t)t;
+      else out[i * H + j] = 0;
+    }
+  }
+  __syncthreads();
+  const int n = (int)*count;
+  if (n == 0) return;                                   // (one word for the whole workgroup: uniform)
+  for (int l0 = tid - lane; l0 < padded; l0 += GAIN_THREADS) {
+    const int l = l0 + lane, li = l / lh, lj = l - li * lh;
+    const int gi = i0 - r + li, gj = j0 - r + lj;
+    const bool in = l < grown && (unsigned)gi < (unsigned)W && (unsigned)gj < (unsigned)H;
+    const int e = in ? ev[gi * H + gj] : 0;
+    const bool is_solid = !in || e >= t_occ, is_free = e <= -t_free;
+    const uint64_t ms = __ballot(is_solid), mu = __ballot(!is_solid && !is_free);
+    if (lane == 0) {
+      solid[l0 >> 5] = (uint32_t)ms; solid[(l0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      unk[l0 >> 5] = (uint32_t)mu; unk[(l0 >> 5) + 1] = (uint32_t)(mu >> 32);
+    }
+  }
+  if (tid < 2) { solid[words - 2 + tid] = 0; unk[words - 2 + tid] = 0; }
+  __syncthreads();
+  const int r2 = r * r, two_r = 2 * r, side = two_r + 1, n_rays = 8 * r;
+  for (int k = wave; k < n; k += GAIN_WAVES) {
+    const int t = (int)list[k], si = t / TILE_H + r, sj = t % TILE_H + r;     // the source, in the grown tile
+    for (int w = lane; w < ww; w += 64) win[w] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int q = lane; q < n_rays; q += 64) {
+      const int edge = q / two_r, u = q - edge * two_r;
+      const int di = edge == 0 ? -r : edge == 1 ? u - r : edge == 2 ? r : r - u;
+      const int dj = edge == 0 ? u - r : edge == 1 ? r : edge == 2 ? r - u : -r;
+      int qi = 0, ri = r, qj = 0, rj = r;
+      for (int step = 1; step <= r; ++step) {
+        ri += 2 * di; rj += 2 * dj;
+        if (ri >= two_r) { ri -= two_r; ++qi; } else if (ri < 0) { ri += two_r; --qi; }
+        if (rj >= two_r) { rj -= two_r; ++qj; } else if (rj < 0) { rj += two_r; --qj; }
+        if (qi * qi + qj * qj > r2) break;
+        const int l = (si + qi) * lh + sj + qj;
+        if (bit_of(solid, l)) break;
+        if (bit_of(unk, l)) {
+          const int b = (qi + r) * side + qj + r;
+          atomicOr(win + (b >> 5), 1u << (b & 31));
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    int seen = 0;
+    for (int w = lane; w < ww; w += 64) seen += __popc(win[w]);
+    for (int o = 32; o; o >>= 1) seen += __shfl_xor(seen, o);
+    if (lane == 0) out[(i0 + t / TILE_H) * H + j0 + t % TILE_H] = seen;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the window is read before the next cell clears it)
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// set-up of the utility field: the sources by the blocked bitmap, their seeds and INF elsewhere, their count by integer atomics
+// (n_sources was cleared a kernel earlier), the flags round every source
+__global__ void __launch_bounds__(SETUP_THREADS) tile_utility_seed_kernel(int W, int H, int chunks, const uint32_t* __restrict__ blk,
+                                                                          const uint8_t* __restrict__ frontier,
+                                                                          const int32_t* __restrict__ gain, int w_gain, int g_cap,
+                                                                          int min_gain, uint32_t* __restrict__ ufield,
+                                                                          int32_t* __restrict__ n_sources, uint32_t* __restrict__ flags,
+                                                                          int64_t tiles) {
+  const int64_t f = blockIdx.x / chunks;
+  const int chunk = blockIdx.x - (int)f * chunks, lane = threadIdx.x & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells);
+  const int c = chunk * SETUP_THREADS + threadIdx.x;
+  bool src = false;
+  if (c < ncells) {
+    const int64_t at = f * ncells + c;
+    int g = 0;
+    if (frontier[at] != 0 && !bit_of(blk + f * words, c)) {
+      g = gain[at];
+      src = g >= min_gain;
+    }
+    ufield[at] = src ? gain_seed(g, w_gain, g_cap) : INF;
+    if (src) {
+      const int i = c / H;
+      flag_round_seed(flags + f * tiles, W, H, tiles_along(H, TILE_H), i, c - i * H);
+    }
+  }
+  const int mine = __popcll(__ballot(src));
+  if (lane == 0 && mine) atomicAdd(n_sources + f, mine);              // (integers: the sum is the same in any order)
+}
+
+// frontier_utility_path_kernel with one more rule in front: a robot whose utility field is not settled gets
+// LIPMPC_RRT_FIELD_UNSETTLED before any other rule.  The rest is THAT KERNEL'S BODY, COPIED word for word (as walk_in() is a copy of
+// walk()): sharing it through a device function moved instructions in that kernel, which stays as it was compiled.  A fix to one
+// of the two bodies belongs in the other.
+__global__ void __launch_bounds__(PATH_THREADS) tile_utility_descent_kernel(
+    int64_t B, int one_field, int W, int H, double ox, double oy, double dx, double dy, const int32_t* __restrict__ evidence, int t_occ,
+    const uint8_t* __restrict__ frontier, const int32_t* __restrict__ gain, const uint32_t* __restrict__ ufield,
+    const int32_t* __restrict__ n_sources, const int32_t* __restrict__ settled, int w_gain, int g_cap, int min_gain,
+    const double* __restrict__ start, int r_inflate, int max_seg, int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+    int32_t* __restrict__ status, double* __restrict__ path_cost, int32_t* __restrict__ target_cell, int32_t* __restrict__ target_gain) {
+  const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const int64_t f = one_field ? 0 : b;
+  const int ncells = W * H;
+  const uint32_t* fld = ufield + f * (int64_t)ncells;
+  const uint8_t* fr = frontier + f * (int64_t)ncells;
+  const int32_t* gn = gain + f * (int64_t)ncells;
+  auto done = [&](int st_, int n, double cost, int target) {
+    status[b] = st_; n_sub[b] = n; path_cost[b] = cost; target_cell[b] = target; target_gain[b] = target >= 0 ? gn[target] : -1;
+  };
+  // (a source is passable: its field is finite, which the comparison with a seed says too)
+  auto terminal = [&](int c) {
+    if (fr[c] == 0) return false;
+    const int g = gn[c];
+    return g >= min_gain && fld[c] == gain_seed(g, w_gain, g_cap);
+  };
+  const double nan = __builtin_nan("");
+  if (settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan, -1);
+  int si = 0, sj = 0;
+  if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan, -1);
+  int s = si * H + sj;
+  if (evidence[f * (int64_t)ncells + s] >= t_occ) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan, -1);
+  if (n_sources[f] == 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
+  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  double* sg = sub_goals + b * (int64_t)S_max * 2;
+  int last_cell;
+  const int n = walk_to(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell, terminal);
+  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);             // (a `ufield` that is no utility field of this map)
+  const double cost = (double)(fld[s] - fld[last_cell]) / 5.0;
+  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, cost, last_cell);
+  walk_to(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell, terminal);
+  centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
+  done(LIPMPC_RRT_FOUND, n, cost, last_cell);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the coordinated claim by tiles (lipmpc_grid_frontier_assign_tiled_batch): assign_body's rounds cut into kernels, every field_k
+// relaxed by tiled_round_kernel.  The workspace: CLAIM_CTL control words, the impassable and the source bitmap, the two flag
+// arrays, then field_k.
+constexpr int CLAIM_CTL = 8;                          // words 0, 1: the key (64 bits, 8-byte aligned as `work` is); then:
+constexpr int CTL_TARGET = 2, CTL_STOPPED = 3, CTL_CLAIMS = 4, CTL_UNSETTLED = 5, CTL_ROUND_SETTLED = 6, CTL_ANY_SOURCE = 7;
+constexpr int64_t CLAIM_MAX_LAUNCHES = 1 << 20;       // max_claims * max_rounds of one call
+
+struct ClaimLayout {
+  int64_t bm_words, tiles, blocked, sources, flags0, flags1, field, words;
+};
+inline ClaimLayout claim_layout(int64_t W, int64_t H) {
+  ClaimLayout l;
+  l.bm_words = bitmap_words(W * H);
+  l.tiles = (int64_t)tiles_along((int)W, TILE_W) * tiles_along((int)H, TILE_H);
+  l.blocked = CLAIM_CTL;
+  l.sources = l.blocked + l.bm_words;
+  l.flags0 = l.sources + l.bm_words;
+  l.flags1 = l.flags0 + l.tiles;
+  l.field = l.flags1 + l.tiles;
+  l.words = l.field + W * H;
+  return l;
+}
+inline int64_t claim_bytes(int64_t W, int64_t H) { return 4 * claim_layout(W, H).words + 256; }
+
+// once per call, over cells: impassable = the given field is INF, sources = the given frontier on passable cells, both by
+// ballots; both flag arrays cleared; the control words.  With max_claims == 0 or an unsettled given field the call is stopped
+// from the start.
+__global__ void __launch_bounds__(SETUP_THREADS) claim_setup_kernel(int ncells, int64_t tiles, int max_claims,
+                                                                    const uint8_t* __restrict__ frontier,
+                                                                    const uint32_t* __restrict__ field,
+                                                                    const int32_t* __restrict__ settled, uint32_t* __restrict__ ctl,
+                                                                    uint32_t* __restrict__ blk, uint32_t* __restrict__ src,
+                                                                    uint32_t* __restrict__ flags) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  const int c = blockIdx.x * SETUP_THREADS + tid, c0 = c - lane;
+  if (c0 < padded) {
+    const bool pass = c < ncells && field[c] != INF;
+    const uint64_t mb = __ballot(c < ncells && !pass), ms = __ballot(pass && frontier[c] != 0);
+    if (lane == 0) {
+      blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32);
+      src[c0 >> 5] = (uint32_t)ms; src[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+    }
+  }
+  if (blockIdx.x == 0) {
+    if (tid < 2) { blk[words - 2 + tid] = 0; src[words - 2 + tid] = 0; }
+    if (tid == 2) {
+      const uint32_t unsettled = settled[0] == 0;
+      ctl[0] = ctl[1] = ctl[CTL_TARGET] = INF;
+      ctl[CTL_STOPPED] = unsettled | (uint32_t)(max_claims == 0);
+      ctl[CTL_CLAIMS] = 0;
+      ctl[CTL_UNSETTLED] = unsettled;
+      ctl[CTL_ROUND_SETTLED] = 1;
+      ctl[CTL_ANY_SOURCE] = 0;
+    }
+  }
+  const int64_t total = 2 * tiles, step = (int64_t)gridDim.x * SETUP_THREADS;
+  for (int64_t k = (int64_t)blockIdx.x * SETUP_THREADS + tid; k < total; k += step) flags[k] = 0;
+}
+
+// once per call, over robots: U_0 as assign_body encodes it, claim_round[b] = -2 - (start cell), -1 for everyone else
+__global__ void __launch_bounds__(SETUP_THREADS) claim_robots_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
+                                                                     const double* __restrict__ start,
+                                                                     const int8_t* __restrict__ may_claim, int max_claims,
+                                                                     const int32_t* __restrict__ status,
+                                                                     int32_t* __restrict__ claim_round) {
+  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const int sb = status[b];
+  int si = 0, sj = 0, v = -1;
+  if (max_claims > 0 && (sb == LIPMPC_RRT_FOUND || sb == LIPMPC_RRT_PATH_OVERFLOW) && (!may_claim || may_claim[b]) &&
+      cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
+    v = -2 - (si * H + sj);
+  claim_round[b] = v;
+}
+
+// the claim seed, blockIdx.x = tile: field_k = 0 on what is left of the sources and INF elsewhere on the tile's cells; the tile's
+// flag of the first round = some source among its cells or in its halo (what flag_round_seed sets), its flag of the second
+// array 0 -- each flag word has one writer, so nothing is cleared under another workgroup's hands
+__global__ void __launch_bounds__(TILE_THREADS) claim_seed_kernel(int W, int H, int tiles_j, uint32_t* __restrict__ ctl,
+                                                                  const uint32_t* __restrict__ src, uint32_t* __restrict__ field_k,
+                                                                  uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
+  if (ld_agent(ctl + CTL_STOPPED)) return;              // (both flag arrays are clear: whoever stopped the call cleared them)
+  const int tile = blockIdx.x, tid = threadIdx.x;
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  int own = 0, near = 0;
+  for (int l = tid; l < HALO_CELLS; l += TILE_THREADS) {
+    const int li = l / HALO_H, lj = l - li * HALO_H, i = i0 + li - 1, j = j0 + lj - 1;
+    if ((unsigned)i >= (unsigned)W || (unsigned)j >= (unsigned)H) continue;
+    const bool s = bit_of(src, i * H + j);
+    const bool inner = li >= 1 && li <= TILE_W && lj >= 1 && lj <= TILE_H;
+    if (inner) field_k[i * H + j] = s ? 0u : INF;
+    own |= s & inner;
+    near |= s;
+  }
+  near = __syncthreads_or(near);
+  if (tid == 0) { flags0[tile] = near != 0; flags1[tile] = 0; }
+  if (own) st_agent(ctl + CTL_ANY_SOURCE, 1u);
+}
+
+// the pick, over robots: the least (cost << 32 | b) among the candidates of U_k, by a wave reduction and a 64-bit atomicMin.
+// Every workgroup finds the same answer to "are the rounds over" from words that earlier kernels wrote.
+__global__ void __launch_bounds__(SETUP_THREADS) claim_pick_kernel(int64_t B, int W, int H, int r_inflate, uint32_t* ctl,
+                                                                   const uint32_t* field_k, const int32_t* __restrict__ claim_round) {
+  if (ld_agent(ctl + CTL_STOPPED)) return;
+  const bool no_source = ld_agent(ctl + CTL_ANY_SOURCE) == 0, unsettled = ld_agent(ctl + CTL_ROUND_SETTLED) == 0;
+  if (no_source || unsettled) return;                   // (the claim kernel stops the call: it reads the same two words)
+  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  unsigned long long mine = ~0ull;
+  if (b < B) {
+    const int v = claim_round[b];
+    if (v <= -2) {
+      const int s = claim_cell(field_k, W, H, -2 - v, r_inflate);
+      if (s >= 0) mine = ((unsigned long long)ld(field_k + s) << 32) | (unsigned long long)b;
+    }
+  }
+  for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
+  if ((threadIdx.x & 63) == 0 && mine != ~0ull) atomicMin((unsigned long long*)ctl, mine);
+}
+
+// the claim, ONE workgroup: one lane walks the winner's path down field_k and writes its rows and claim_round; then everybody
+// clears the disc from the source bitmap.  Whatever happened, the kernel leaves both flag arrays clear, the key reset and the
+// "any source" word 0 for the next round's seed.
+__global__ void __launch_bounds__(FIELD_THREADS) claim_take_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
+                                                                   int r_inflate, int r_claim, int max_seg, int S_max, int k, int tiles,
+                                                                   uint32_t* ctl, uint32_t* src, const uint32_t* field_k, uint32_t* flags,
+                                                                   double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                                                   int32_t* target_cell, int32_t* claim_round) {
+  const int tid = threadIdx.x;
+  const bool stopped = ctl[CTL_STOPPED] != 0, no_source = ctl[CTL_ANY_SOURCE] == 0, unsettled = ctl[CTL_ROUND_SETTLED] == 0;
+  const unsigned long long win = *(const unsigned long long*)ctl;
+  __syncthreads();                                      // (everybody has read the control words)
+  for (int t = tid; t < 2 * tiles; t += FIELD_THREADS) flags[t] = 0;
+  if (tid == 0) { ctl[0] = ctl[1] = INF; ctl[CTL_ANY_SOURCE] = 0; ctl[CTL_ROUND_SETTLED] = 1; }
+  if (stopped) return;
+  if (no_source || unsettled || win == ~0ull) {         // no source left, a field that did not settle, no candidate
+    if (tid == 0) { ctl[CTL_STOPPED] = 1; if (!no_source && unsettled) ctl[CTL_UNSETTLED] = 1; }
+    return;
+  }
+  const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
+  if (tid == 0) {
+    // one lane walks the winner's path, twice: count, then -- if the sub-goals fit -- write (rows past n_sub stay untouched)
+    const int s = claim_cell(field_k, W, H, -2 - claim_round[wb], r_inflate);
+    double* sg = sub_goals + wb * (int64_t)S_max * 2;
+    int last_cell = s, n = 0;
+    for (int pass = 0; pass < 2 && n >= 0 && n <= S_max; ++pass)
+      n = walk_in(field_k, W, H, s, max_seg, ox, oy, dx, dy, pass ? sg : nullptr, last_cell);
+    if (n > 0) {
+      if (n <= S_max) centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
+      status[wb] = n <= S_max ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+      n_sub[wb] = n <= S_max ? n : 0;
+      path_cost[wb] = (double)ld(field_k + s) / 5.0;
+      target_cell[wb] = last_cell;
+      claim_round[wb] = k;
+      ctl[CTL_CLAIMS] = (uint32_t)(k + 1);
+    }
+    ctl[CTL_TARGET] = n > 0 ? (uint32_t)last_cell : INF;  // (a fixed point always has a descent: INF cannot happen)
+  }
+  __syncthreads();
+  const uint32_t t = ctl[CTL_TARGET];
+  int eligible = 0;
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) eligible |= claim_round[b] <= -2;
+  const int more = __syncthreads_or(eligible);
+  if (t == INF || !more) {                              // U is used up
+    if (tid == 0) ctl[CTL_STOPPED] = 1;
+    return;
+  }
+  // S_{k+1}: the sources outside the winner's disc, clipped to the grid
+  const int ti = (int)t / H, tj = (int)t - ti * H, r2 = r_claim * r_claim;
+  const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
+  for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+    const int i = c / H, j = c - i * H;
+    if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+  }
+}
+
+// the last kernel, over robots: the followers (still in U), n_claims and claims_settled
+__global__ void __launch_bounds__(SETUP_THREADS) claim_finish_kernel(int64_t B, const uint32_t* __restrict__ ctl, int32_t* claim_round,
+                                                                     int32_t* __restrict__ n_claims, int32_t* __restrict__ claims_settled) {
+  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  if (b < B && claim_round[b] < -1) claim_round[b] = -1;
+  if (b == 0) { n_claims[0] = (int32_t)ctl[CTL_CLAIMS]; claims_settled[0] = ctl[CTL_UNSETTLED] == 0; }
+}
+
+// E_ARG of a grid's placement
+bool bad_placement(const double* origin, const double* cell) {
+  if (!origin || !cell) return true;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  return !(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY);
+}
+
+}  // namespace
+
+extern "C" int64_t lipmpc_grid_frontier_gain_tiled_lds_bytes(int32_t r_view) {
+  if (r_view < 1 || r_view > R_VIEW_MAX) return LIPMPC_E_ARG;
+  return tile_gain_lds_bytes(r_view);
+}
+
+extern "C" int lipmpc_grid_frontier_gain_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                                     int32_t t_occ, const uint8_t* frontier, int32_t r_view, int32_t* gain,
+                                                     void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
+      r_view < 1 || r_view > R_VIEW_MAX || !evidence || !frontier || !gain)
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  const int tiles_j = tiles_along(H, TILE_H), tiles = tiles_along(W, TILE_W) * tiles_j;
+  hipLaunchKernelGGL(tile_gain_kernel, dim3((unsigned)(F * tiles)), dim3(GAIN_THREADS), (size_t)tile_gain_lds_bytes(r_view),
+                     (hipStream_t)hip_stream, W, H, tiles_j, tiles, evidence, t_free, t_occ, frontier, r_view, gain);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_utility_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence,
+                                                              int32_t t_free, int32_t t_occ, int32_t r_inflate, const uint8_t* frontier,
+                                                              const int32_t* gain, int32_t w_gain, int32_t g_cap, int32_t min_gain,
+                                                              uint32_t* ufield, int32_t* n_sources, void* work, int64_t work_bytes,
+                                                              int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
+      r_inflate < 0 || r_inflate > R_INFLATE_MAX || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 ||
+      min_gain > G_CAP_MAX || !evidence || !frontier || !gain || !ufield || !n_sources)
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const TiledLayout l = tiled_layout(F, W, H);
+  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  uint32_t* w = (uint32_t*)work;
+  if (!resume) {
+    hipLaunchKernelGGL(tiled_bitmaps_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles,
+                       (const uint8_t*)nullptr, evidence, t_free, t_occ, w + l.solid, w + l.unknown, w + l.flags0, n_sources);
+    hipLaunchKernelGGL(tiled_blocked_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
+                       w + l.solid, w + l.unknown, w + l.blocked);
+    hipLaunchKernelGGL(tile_utility_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, w + l.blocked,
+                       frontier, gain, w_gain, g_cap, min_gain, ufield, n_sources, w + l.flags0, l.tiles);
+  }
+  return tiled_rounds(s, F, W, H, l.bm_words, l, w, ufield, max_rounds, settled);
+}
+
+extern "C" int lipmpc_grid_frontier_utility_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                                             const double* cell, const int32_t* evidence, int32_t t_occ,
+                                                             const uint8_t* frontier, const int32_t* gain, const uint32_t* ufield,
+                                                             const int32_t* n_sources, const int32_t* settled, int32_t w_gain,
+                                                             int32_t g_cap, int32_t min_gain, const double* start, int32_t r_inflate,
+                                                             int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
+                                                             int32_t* status, double* path_cost, int32_t* target_cell,
+                                                             int32_t* target_gain, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX || w_gain < 0 ||
+      w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !evidence || !frontier || !gain ||
+      !ufield || !n_sources || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !target_gain)
+    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(tile_utility_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier,
+                     gain, ufield, n_sources, settled, w_gain, g_cap, min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
+                     path_cost, target_cell, target_gain);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int64_t lipmpc_grid_frontier_assign_tiled_workspace_bytes(int32_t W, int32_t H) {
+  if (W < 2 || H < 2) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  return claim_bytes(W, H);
+}
+
+extern "C" int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                                       const uint8_t* frontier, const uint32_t* field, const int32_t* settled,
+                                                       const double* start, const int8_t* may_claim, int32_t r_inflate, int32_t r_claim,
+                                                       int32_t max_claims, int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes,
+                                                       int32_t max_rounds, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                                       double* path_cost, int32_t* target_cell, int32_t* claim_round, int32_t* n_claims,
+                                                       int32_t* claims_settled, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
+      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS || (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
+    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  if (work_bytes < claim_bytes(W, H)) return LIPMPC_E_ARG;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const ClaimLayout c = claim_layout(W, H);
+  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
+  const unsigned robots = (unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS);
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  uint32_t* w = (uint32_t*)work;
+  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
+  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
+  hipLaunchKernelGGL(claim_setup_kernel, dim3((unsigned)chunks), dim3(SETUP_THREADS), 0, s, ncells, c.tiles, max_claims, frontier, field,
+                     settled, w, w + c.blocked, w + c.sources, w + c.flags0);
+  hipLaunchKernelGGL(claim_robots_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims,
+                     status, claim_round);
+  for (int k = 0; k < max_claims; ++k) {
+    hipLaunchKernelGGL(claim_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, w + c.field,
+                       w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
+    hipLaunchKernelGGL(claim_pick_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+    hipLaunchKernelGGL(claim_take_kernel, dim3(1), dim3(FIELD_THREADS), 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, max_seg, S_max, k,
+                       tiles, w, w + c.sources, w + c.field, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell, claim_round);
+  }
+  hipLaunchKernelGGL(claim_finish_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, w, claim_round, n_claims, claims_settled);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

@@ -17,6 +17,10 @@ targets apart, nearest claim first (``lipmpc_grid_frontier_assign_batch``).
 ``InformedFrontierPlanner`` is ``FrontierPlanner`` with a utility from expected visibility: the unknown cells a robot would see
 from every frontier cell (``lipmpc_grid_frontier_gain_batch``), a cost-to-go field whose sources start ahead by that gain
 (``lipmpc_grid_frontier_utility_field_batch``) and sub-goals down it (``lipmpc_grid_frontier_utility_path_batch``).
+
+``TiledCoordinatedFrontierPlanner`` and ``TiledInformedFrontierPlanner`` are those two on maps of up to 2^24 cells: the same outputs
+by the tiled calls (``lipmpc_grid_frontier_assign_tiled_batch``; ``lipmpc_grid_frontier_gain_tiled_batch``,
+``lipmpc_grid_frontier_utility_field_tiled_batch``, ``lipmpc_grid_frontier_utility_path_tiled_batch``).
 """
 from __future__ import annotations
 
@@ -69,32 +73,40 @@ class _TiledRounds(metaclass=_TiledKeywords):
     def _init_tiled(self, tiled, rounds):
         self.tiled, self.rounds = bool(tiled), None if rounds is None else int(rounds)
         if self.tiled and not self._TILED:
-            raise ValueError(f"{type(self).__name__}: tiled=True is not supported ({self._TILED_WHY} the cap of 2^17 cells)")
+            raise ValueError(f"{type(self).__name__}: tiled=True is not supported ({self._TILED_WHY} the cap of 2^17 cells; "
+                             f"the large-map class is {self._TILED_CLASS})")
         if self.rounds is not None and (not self.tiled or not 1 <= self.rounds <= 65536):
             raise ValueError(f"rounds {rounds}: 1..65536 or None, with tiled=True only")
         self._works = []            # every workspace ever handed to a call; the last one is the current one
 
-    def _settled(self, out, F):
-        """out["settled"] [F] int32, made if the caller's dict has none."""
-        t = out.get("settled")
+    def _settled(self, out, F, key="settled"):
+        """out[key] [F] int32, made if the caller's dict has none."""
+        t = out.get(key)
         if t is None:
-            t = out["settled"] = torch.empty((F,), dtype=torch.int32, device=self.device)
+            t = out[key] = torch.empty((F,), dtype=torch.int32, device=self.device)
         elif t.shape != (F,) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous():
-            raise ValueError(f"out['settled'] must be a contiguous int32 tensor [{F}] on the planner's device")
+            raise ValueError(f"out['{key}'] must be a contiguous int32 tensor [{F}] on the planner's device")
         return t
 
-    def _run_tiled(self, name, F, W, H, out, **args):
+    def _workspace(self, works, need, what):
+        """The current buffer of the grow-only list ``works``, of at least ``need`` bytes (< 0: the size call's refusal)."""
+        if need < 0:
+            _lib.check(need, what)
+        if not works or works[-1].numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the tiled workspace must grow: run the call once before the capture")
+            works.append(torch.empty(need, dtype=torch.uint8, device=self.device))
+        return works[-1]
+
+    def _run_tiled(self, name, F, W, H, out, works=None, key="settled", **args):
+        """One tiled field call by the ``rounds`` rule.  ``works``: the call's own workspace list (default: the planner's first);
+        ``key``: where in ``out`` its ``settled`` goes."""
         capturing = torch.cuda.is_current_stream_capturing()
         if self.rounds is None and capturing:
             raise RuntimeError("rounds=None reads `settled` on the host: give the planner a fixed `rounds` to capture its calls")
-        need = int(self.lib.lipmpc_grid_tiled_workspace_bytes(F, W, H))
-        if need < 0:
-            _lib.check(need, "lipmpc_grid_tiled_workspace_bytes")
-        if not self._works or self._works[-1].numel() < need:
-            if capturing:
-                raise RuntimeError("the tiled workspace must grow: run the call once before the capture")
-            self._works.append(torch.empty(need, dtype=torch.uint8, device=self.device))
-        work, settled = self._works[-1], self._settled(out, F)
+        work = self._workspace(self._works if works is None else works, int(self.lib.lipmpc_grid_tiled_workspace_bytes(F, W, H)),
+                               "lipmpc_grid_tiled_workspace_bytes")
+        settled = self._settled(out, F, key)
         stream = torch.cuda.current_stream(self.device).cuda_stream
 
         def call(budget, resume):
@@ -563,7 +575,9 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     that are left when the frontier or ``max_claims`` is used up are FOLLOWERS, who keep their plain nearest-frontier plan and so
     share a target; there is no memory between plans, so a replan may hand a robot another target than the last one."""
 
-    _TILED, _TILED_WHY = False, "the claim rounds keep"
+    _TILED, _TILED_WHY, _TILED_CLASS = False, "the claim rounds keep", "TiledCoordinatedFrontierPlanner"
+    _FRESH = ("field", "frontier", "n_frontier", "work")            # outputs written whole: a fresh dict gets them uninitialised
+    _table = staticmethod(assign_outputs)
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
         self.r_claim, self.max_claims = int(r_claim), int(max_claims)
@@ -589,10 +603,10 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
             if tuple(may_claim.shape) != (B,):
                 raise ValueError("may_claim must be [B]")
             may_claim = (may_claim != 0).to(torch.int8)
-        table = assign_outputs(B, W, H, S_max)
+        table = self._table(B, W, H, S_max)
         if out is None:
             out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost", "target", "target_cell"), self.device, torch.zeros)
-            out.update(_alloc(table, ("field", "frontier", "n_frontier", "work"), self.device))
+            out.update(_alloc(table, self._FRESH, self.device))
             out.update(claim_round=torch.full((B,), -1, dtype=torch.int32, device=self.device),
                        n_claims=torch.zeros((1,), dtype=torch.int32, device=self.device))
         else:
@@ -601,14 +615,94 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         if B == 0:
             return out
         origin, cell, org_c, cell_c = self._placement(*self._map(mapper_or_evidence, origin, cell)[3:])
+        self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out)
+        self._target(out, origin, cell, H)
+        self.last = out
+        return out
+
+    def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
         _lib.call("lipmpc_grid_frontier_assign_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
                   cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], start=start, may_claim=may_claim,
                   r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims, max_seg=self.max_seg, S_max=S_max,
                   work=out["work"], **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
-        self._target(out, origin, cell, H)
-        self.last = out
+
+
+def tiled_assign_outputs(B, W, H, S_max):
+    """Outputs of TiledCoordinatedFrontierPlanner.plan: CoordinatedFrontierPlanner.plan's without its scratch field (the tiled claim
+    call's workspace is the planner's own) and with claims_settled; ``settled`` [1] comes as in ``FrontierPlanner(tiled=True)``."""
+    table = assign_outputs(B, W, H, S_max)
+    del table["work"]
+    return dict(table, claims_settled=(torch.int32, (1,), False))
+
+
+CLAIM_MAX_LAUNCHES = 1 << 20    # max_claims * max_rounds of one lipmpc_grid_frontier_assign_tiled_batch
+
+
+class _AlwaysTiled:
+    """The large-map classes: ``tiled`` is always True, ``rounds`` stays the keyword of ``_TiledRounds``."""
+
+    _TILED = True
+
+    def _init_tiled(self, tiled, rounds):
+        super()._init_tiled(True, rounds)
+
+
+class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
+    """``CoordinatedFrontierPlanner`` on maps of up to 2^24 cells (include/lipmpc.h, TILED EXPLORERS): the tiled nearest-frontier
+    plan of ``FrontierPlanner(tiled=True)``, then the same claim rule with every round's field relaxed by tiled rounds
+    (``lipmpc_grid_frontier_assign_tiled_batch``).  Returns the parent's dict without ``work``, plus ``settled`` [1] (the
+    nearest-frontier field) and ``claims_settled`` [1]: 1 = the claim rounds ended by the rule and every output is the parent's, bit
+    for bit; 0 = the given field or some round's field did not settle within the budget -- then the claims made so far are the
+    rule's first ``n_claims`` rounds and everyone else keeps the nearest-frontier plan.
+    Keyword-only ``rounds``: an int = the budget of the frontier field AND of every claim round, one call each, no synchronisation,
+    capturable (``max_claims`` * ``rounds`` <= 2^20: the launches of one call); None = the frontier field as ``_TiledRounds`` says,
+    then the claim call repeated with a doubled per-claim budget while ``claims_settled`` is 0, up to min(65536, 2^20 /
+    ``max_claims``) -- at that cap the dict is returned with ``claims_settled`` 0.
+    The cost is fixed by the budget, not by what the fleet needs: ``max_claims`` * (budget + 4) + 3 launches per claim call.  On
+    small maps the one-workgroup parent is faster; it stays the default.  The limits that remain: the claim rounds are sequential
+    and not gain-seeded, and there is no memory between plans."""
+
+    _FRESH = ("field", "frontier", "n_frontier")
+    _table = staticmethod(tiled_assign_outputs)
+
+    def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
+        if self.rounds is not None and int(max_claims) * self.rounds > CLAIM_MAX_LAUNCHES:
+            raise ValueError(f"max_claims {max_claims} * rounds {self.rounds}: at most 2^20, the launches of one claim call")
+        super().__init__(r_claim, max_claims, **frontier_planner_kwargs)
+        self._claim_works = []      # the claim call's own workspace: grown only, every buffer kept alive
+
+    def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None):
+        """``CoordinatedFrontierPlanner.plan`` by the tiled calls: its dict without ``work``, plus ``settled`` and ``claims_settled`` [1]."""
+        out = super().plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim)
+        self._settled(out, 1, "claims_settled")            # (B = 0: no call was made)
         return out
+
+    def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self.rounds is None and capturing:
+            raise RuntimeError("rounds=None reads `claims_settled` on the host: give the planner a fixed `rounds` to capture its calls")
+        work = self._workspace(self._claim_works, int(self.lib.lipmpc_grid_frontier_assign_tiled_workspace_bytes(W, H)),
+                               "lipmpc_grid_frontier_assign_tiled_workspace_bytes")
+        done = self._settled(out, 1, "claims_settled")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+
+        def call(budget):
+            _lib.call("lipmpc_grid_frontier_assign_tiled_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
+                      cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], settled=out["settled"], start=start,
+                      may_claim=may_claim, r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims,
+                      max_seg=self.max_seg, S_max=S_max, work=work, work_bytes=work.numel(), max_rounds=budget,
+                      **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
+                      claims_settled=done, hip_stream=stream)
+        if self.rounds is not None:
+            return call(self.rounds)
+        tw, th, _ = tiled_info()
+        cap = min(65536, CLAIM_MAX_LAUNCHES // max(self.max_claims, 1))
+        budget = min(cap, max(8, -(-W // tw) - (-H // th) + 1))
+        call(budget)
+        while budget < cap and not bool(done[0]):
+            budget = min(2 * budget, cap)
+            call(budget)                                   # (the whole call again: it reproduces the rounds made so far and goes on)
 
 
 class InformedFrontierPlanner(FrontierPlanner):
@@ -625,7 +719,8 @@ class InformedFrontierPlanner(FrontierPlanner):
     The model's limits: unknown cells do not occlude; there is no memory between plans (no hysteresis), so a replan may hand a robot
     another target; a shared field sends robots that stand together to the same cell, as the parent does."""
 
-    _TILED, _TILED_WHY = False, "the gain call and the utility field keep"
+    _TILED, _TILED_WHY, _TILED_CLASS = False, "the gain call and the utility field keep", "TiledInformedFrontierPlanner"
+    _SETTLED = ()               # what the large-map subclass adds to the dicts of gain() and field()
 
     def __init__(self, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, **frontier_planner_kwargs):
         self.r_view, self.w_gain, self.g_cap, self.min_gain = int(r_view), int(w_gain), int(g_cap), int(min_gain)
@@ -656,7 +751,7 @@ class InformedFrontierPlanner(FrontierPlanner):
         self._gain(ev, t_free, t_occ, out)
         if "ufield" in names:
             self._ufield(ev, out)
-        return {k: out[k] for k in names}
+        return {k: out[k] for k in names + tuple(k for k in self._SETTLED if k in out)}
 
     def gain(self, mapper_or_evidence, out=None):
         """``FrontierPlanner.field``'s dict plus gain [F,W,H] int32: per frontier cell the unknown cells seen from it, 0 elsewhere."""
@@ -705,5 +800,61 @@ class InformedFrontierPlanner(FrontierPlanner):
                   origin=C.addressof(org_c), cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ,
                   **_named(out, ("frontier", "gain", "ufield", "n_sources")), w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain,
                   start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
+                  **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "target_gain")),
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class TiledInformedFrontierPlanner(_AlwaysTiled, InformedFrontierPlanner):
+    """``InformedFrontierPlanner`` on maps of up to 2^24 cells (include/lipmpc.h, TILED EXPLORERS): the tiled nearest-frontier
+    field, the gain by one workgroup per tile (``lipmpc_grid_frontier_gain_tiled_batch``), the utility field by tiled rounds in a
+    workspace of its own (``lipmpc_grid_frontier_utility_field_tiled_batch``) and the paths down it
+    (``lipmpc_grid_frontier_utility_path_tiled_batch``).  ``gain``, ``field`` and ``plan`` return the parent's dicts plus ``settled``
+    [F] (the nearest-frontier field) and ``usettled`` [F] (the utility field); once both are 1 every output is the parent's, bit for
+    bit.  A robot whose utility field is not settled gets RRT_FIELD_UNSETTLED, target_cell -1, target_gain -1 and no sub-goal; the
+    utility field does not read the nearest-frontier field, so ``settled`` == 0 alone costs a robot nothing.
+    Keyword-only ``rounds``: an int = the budget of each of the two fields, one call each, no synchronisation, capturable; None =
+    each field resumed with doubled budgets until it is settled (reads ``settled`` on the host: raises under stream capture).
+    The limits that remain are the parent's: unknown cells do not occlude, and there is no memory between plans."""
+
+    def __init__(self, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, **frontier_planner_kwargs):
+        super().__init__(r_view, w_gain, g_cap, min_gain, **frontier_planner_kwargs)
+        self._uworks = []           # the utility field's own workspace: a resume of the frontier field still reads the other one
+
+    _SETTLED = ("settled", "usettled")
+
+    def _field(self, ev, t_free, t_occ, out):
+        self._classes = t_free, t_occ                      # (what the utility field call classifies the evidence by)
+        return super()._field(ev, t_free, t_occ, out)
+
+    def _gain(self, ev, t_free, t_occ, out):
+        F, W, H = ev.shape
+        _lib.call("lipmpc_grid_frontier_gain_tiled_batch", device=self.device_index, F=F, W=W, H=H, evidence=ev, t_free=t_free,
+                  t_occ=t_occ, frontier=out["frontier"], r_view=self.r_view, gain=out["gain"],
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _ufield(self, ev, out):
+        F, W, H = ev.shape
+        t_free, t_occ = self._classes
+        self._run_tiled("lipmpc_grid_frontier_utility_field_tiled_batch", F, W, H, out, works=self._uworks, key="usettled", evidence=ev,
+                        t_free=t_free, t_occ=t_occ, r_inflate=self.r_inflate, frontier=out["frontier"], gain=out["gain"],
+                        w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, ufield=out["ufield"], n_sources=out["n_sources"])
+
+    def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None):
+        """``InformedFrontierPlanner.plan`` by the tiled calls: its dict plus ``settled`` and ``usettled`` [F]."""
+        F = self._map(mapper_or_evidence, origin, cell)[0].shape[0]
+        if out is not None:
+            self._settled(out, F)
+            self._settled(out, F, "usettled")
+        out = super().plan(mapper_or_evidence, start, origin, cell, S_max, out)
+        for key in ("settled", "usettled"):                # (B = 0: no call was made)
+            self._settled(out, F, key)
+        return out
+
+    def _path(self, ev, t_occ, start, org_c, cell_c, S_max, out):
+        F, W, H = ev.shape
+        _lib.call("lipmpc_grid_frontier_utility_path_tiled_batch", device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
+                  origin=C.addressof(org_c), cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ,
+                  **_named(out, ("frontier", "gain", "ufield", "n_sources")), settled=out["usettled"], w_gain=self.w_gain, g_cap=self.g_cap,
+                  min_gain=self.min_gain, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "target_gain")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)

@@ -966,6 +966,104 @@ int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int64_t F, int3
                                           int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                           int32_t* status, double* path_cost, int32_t* target_cell, void* hip_stream);
 
+/* TILED EXPLORERS (backward-compatible addition): the informed and the coordinated explorer on LARGE maps.  The three informed
+ * calls and the claim call above keep their cap of 2^17 cells and their one workgroup per map; the calls here take what the tiled
+ * field calls take -- W, H <= 4096, W * H <= 2^24, F * (W * H + 64) <= 2^31 (the claim call: F = 1) -- and compute THE SAME
+ * OUTPUTS, bit for bit.  All of them: device pointers but origin / cell (HOST); asynchronous on hip_stream; no allocation and no
+ * host synchronisation, so they can be captured in a graph; every refusal is decided on the host before anything is enqueued, in
+ * this order: LIPMPC_E_ARG, then the caps as LIPMPC_E_UNSUPPORTED, then a work_bytes that is too small as LIPMPC_E_ARG, then
+ * F = 0 / B = 0 enqueues nothing and returns 0.
+ *
+ * lipmpc_grid_frontier_gain_tiled_batch: lipmpc_grid_frontier_gain_batch's arguments, contract and output, word for word, with
+ *  the caps above.  No workspace and no rounds: the gain is local.  One workgroup per (map, tile of tile_w x tile_h cells): a tile
+ *  whose frontier bytes hold no frontier cell writes its zeros and returns, so the work still follows the frontier; any other
+ *  classifies the evidence of the tile grown by r_view on every side -- at most (tile_w + 128) x (tile_h + 128) = 160 x 192 cells
+ *  -- into solid and unknown bits in LDS (a cell outside the grid ends a ray, as there), compacts the tile's frontier cells and
+ *  runs that call's wave-per-cell, lane-per-ray march with the same quotient / remainder stepping and the same window popcount.
+ *  LDS, bounded by r_view and no longer by the map, with g = (tile_w + 2 r)(tile_h + 2 r):
+ *    4 (2 (2 ceil(g / 64) + 2) + 2 + tile_w tile_h + 16 * 2 ceil((2 r + 1)^2 / 64)) bytes, all dynamic: 49,304 at r = 64, 8,920 at r = 1.
+ *  lipmpc_grid_frontier_gain_tiled_lds_bytes(r_view): that figure as the host passes it at launch.  Host only.  LIPMPC_E_ARG (as a
+ *  negative value): r_view outside 1..64.
+ *
+ * lipmpc_grid_frontier_utility_field_tiled_batch: the utility field by rounds.
+ *  F, W, H, evidence, t_free, t_occ, r_inflate: what the frontier field call was given
+ *  frontier, gain, w_gain, g_cap, min_gain, ufield, n_sources: lipmpc_grid_frontier_utility_field_batch's
+ *  work, work_bytes, max_rounds, resume, settled: lipmpc_grid_field_tiled_batch's; `work` is a workspace of this call's OWN
+ *  (not the frontier field call's, which a resume of that call still reads), of lipmpc_grid_tiled_workspace_bytes(F, W, H) bytes
+ *  A cold call builds the solid, unknown and blocked bitmaps from the evidence as the tiled frontier field call does, then
+ *   source(c) <=> frontier[c] != 0 && !blocked(c) && gain[c] >= min_gain;  ufield = seed(c) on sources and INF elsewhere;
+ *   n_sources by integer atomics; then max_rounds rounds and settled.  n_sources is written by a cold call only.  A map with
+ *   n_sources == 0 is settled before the first round, its ufield all INF.
+ *  PASSABLE HERE IS "UNBLOCKED", where the one-workgroup call reads field != INF.  The two agree on everything that matters: a
+ *   frontier cell is always finite in the nearest-frontier field, so the sources are the same; an unblocked cell that is INF
+ *   there reaches no frontier cell, hence no source, and is INF in either utility field; a diagonal's side cell is an axial
+ *   neighbour of the diagonal's target, so judging diagonals on blocked bits allows the same moves among cells that reach a
+ *   source.  So a settled ufield equals lipmpc_grid_frontier_utility_field_batch's, bit for bit -- and the call does not need the
+ *   nearest-frontier field to be settled, or to exist.
+ *  resume, settled, the round guarantee (with "a source" for "the goal cell", costs counted from the source's seed) and "two cold
+ *   calls give identical bits" are lipmpc_grid_frontier_field_tiled_batch's.  Finite values stay below 7 * 2^24 + 2^26.
+ *  LIPMPC_E_ARG: F < 0, W or H < 2, t_free or t_occ outside 1..2^30, r_inflate outside 0..16, the three gain parameters out of
+ *   range, a null evidence / frontier / gain / ufield / n_sources / work / settled (whatever F), max_rounds outside 1..65536,
+ *   resume neither 0 nor 1.
+ *
+ * lipmpc_grid_frontier_utility_path_tiled_batch: lipmpc_grid_frontier_utility_path_batch word for word, with the caps above and
+ *  one more input, settled [F] int32, the utility field call's output.  settled[f] == 0 gives LIPMPC_RRT_FIELD_UNSETTLED BEFORE
+ *  any other rule, with n_sub = 0, path_cost = NaN, target_cell = -1, target_gain = -1 and nothing else written.
+ *
+ * lipmpc_grid_frontier_assign_tiled_batch: lipmpc_grid_frontier_assign_batch's rule, word for word -- "passable <=> the given
+ *  field[c] != INF" and the given frontier bytes included -- with every round's field relaxed by tiled rounds.
+ *  B .. S_max, sub_goals .. n_claims: that call's
+ *  settled [1] int32: of the given nearest-frontier field (the tiled frontier field call's output)
+ *  work, work_bytes: at least lipmpc_grid_frontier_assign_tiled_workspace_bytes(W, H) bytes, 8-byte aligned (else LIPMPC_E_ARG).  It holds the
+ *   impassable and the source bitmap, field_k [W * H], two tile-flag arrays, the 64-bit key, the target word, a `stopped` word
+ *   and four more control words.
+ *  max_rounds 1..65536: the budget of EACH claim round;  claims_settled [1] int32
+ *  The host enqueues a fixed sequence that the device cannot shorten: two set-up kernels (bitmaps by ballots and the control
+ *  words; the robots' -2 - start cell encoding of U_0), then for k = 0 .. max_claims - 1 the claim seed (one workgroup per tile:
+ *  field_k = 0 on what is left of the sources and INF elsewhere, the tile's flag of the first round = a source among its cells or
+ *  in its halo, its other flag 0), max_rounds rounds with F = 1 and the impassable bitmap, the settle kernel, the pick (over
+ *  robots: the least (cost << 32 | b) by a wave reduction and a 64-bit atomicMin) and the claim (one workgroup: one lane walks the
+ *  winner's path and writes its rows and claim_round, then all threads clear the disc from the source bitmap, both flag arrays
+ *  and the key), and a last kernel that turns the robots still in U into followers and writes n_claims and claims_settled.  The
+ *  rounds are over when no source is left, there is no candidate, U is used up, settled[0] == 0, or this round's field is not
+ *  settled after max_rounds rounds; the kernel that finds that sets `stopped`, and every later kernel of the call returns on
+ *  reading it -- a seed kernel that sets no flag leaves the round launches idle, one word read per workgroup.
+ *  THE COST, whatever the fleet needs: max_claims * (max_rounds + 4) + 3 launches.
+ *  - claims_settled[0] == 1 <=> the rounds ended by the rule (max_claims reached included); then every output equals
+ *    lipmpc_grid_frontier_assign_batch's, bit for bit.
+ *  - claims_settled[0] == 0 <=> settled[0] == 0 (then n_claims = 0) or some round's field did not settle within max_rounds: the
+ *    claims made so far are exactly the rule's first n_claims rounds, and everyone else keeps the nearest-frontier plan.  A
+ *    repeat of the WHOLE call with a larger budget on the same buffers reproduces those rounds and goes on: the rounds are a
+ *    deterministic function of the inputs, and a winner's overwritten status stays FOUND or PATH_OVERFLOW, which keeps it in U_0.
+ *    (The call restores nobody's rows: after a call that made MORE claims, a robot that claims no longer keeps that call's rows, not
+ *    the path call's.  Repeat with the same or a larger budget, or run the path call first.)
+ *  LIPMPC_E_ARG: what lipmpc_grid_frontier_assign_batch refuses as such, a null settled / claims_settled, max_rounds outside
+ *   1..65536, max_claims * max_rounds > 2^20 (the launches of one call), a work that is not 8-byte aligned.
+ * lipmpc_grid_frontier_assign_tiled_workspace_bytes: non-decreasing in W and in H.  Host only.  LIPMPC_E_ARG (as a negative
+ *  value): W or H < 2; LIPMPC_E_UNSUPPORTED: a shape the call refuses. */
+int64_t lipmpc_grid_frontier_gain_tiled_lds_bytes(int32_t r_view);
+int lipmpc_grid_frontier_gain_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
+                                          int32_t t_occ, const uint8_t* frontier, int32_t r_view, int32_t* gain, void* hip_stream);
+int lipmpc_grid_frontier_utility_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence,
+                                                   int32_t t_free, int32_t t_occ, int32_t r_inflate, const uint8_t* frontier,
+                                                   const int32_t* gain, int32_t w_gain, int32_t g_cap, int32_t min_gain,
+                                                   uint32_t* ufield, int32_t* n_sources, void* work, int64_t work_bytes,
+                                                   int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream);
+int lipmpc_grid_frontier_utility_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                                  const double* cell, const int32_t* evidence, int32_t t_occ, const uint8_t* frontier,
+                                                  const int32_t* gain, const uint32_t* ufield, const int32_t* n_sources,
+                                                  const int32_t* settled, int32_t w_gain, int32_t g_cap, int32_t min_gain,
+                                                  const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
+                                                  double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                                  int32_t* target_cell, int32_t* target_gain, void* hip_stream);
+int64_t lipmpc_grid_frontier_assign_tiled_workspace_bytes(int32_t W, int32_t H);
+int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                            const uint8_t* frontier, const uint32_t* field, const int32_t* settled, const double* start,
+                                            const int8_t* may_claim, int32_t r_inflate, int32_t r_claim, int32_t max_claims,
+                                            int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes, int32_t max_rounds,
+                                            double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+                                            int32_t* claim_round, int32_t* n_claims, int32_t* claims_settled, void* hip_stream);
+
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
  * c_eta, in the form lipmpc_plan_step_batch_c_eta solves against -- after the rows of a scan (first_slot = the scan's
