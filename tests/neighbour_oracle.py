@@ -62,6 +62,66 @@ def neighbour_rows(state, radius, sense_range, k_rows, n_obs_max, share=0.5, gro
     return dict(c_eta=ce, n_rows=n_rows, n_near=n_near, neighbours=nbr)
 
 
+def neighbour_rows_sweep(state, radius, sense_range, k_rows, n_obs_max, share=0.5, group=None, first_slot=None, c_eta=None,
+                         pairs_per_chunk=1 << 21):
+    """``neighbour_rows`` for batches too large for all pairs: the present robots sorted by x, every robot's candidates the
+    window |x_i - x_j| <= R (1 + 2^-10) (and the same bound on y), then the contract's expressions unchanged on the candidates.
+    dist < R gives |x_i - x_j| < R (1 + 5 2^-53) in exact arithmetic (the argument at cell_of in csrc/lipmpc_neighbours.hip:
+    every rounding of dx, dx dx, the sum and the root loses at most a factor 1 - 2^-53, and a dx dx below the normal doubles
+    means |dx| < 2^-510), and a double below the rounded window edge is at or below the exact one, so the window holds every
+    robot in range.  No grid, no hash: it shares nothing with the kernel's search.  tests/test_neighbour_cases_oracle.py holds it
+    to ``neighbour_rows`` bit for bit."""
+    st = np.asarray(state, np.float64)
+    B = st.shape[0]
+    x, y = st[:, 0], st[:, 2]
+    rad = np.broadcast_to(np.asarray(radius, np.float64), (B,))
+    grp = np.zeros(B, np.int64) if group is None else np.asarray(group, np.int64)
+    fs = np.zeros(B, np.int64) if first_slot is None else np.clip(np.asarray(first_slot, np.int64), 0, n_obs_max)
+    ce = np.zeros((B, n_obs_max, 4)) if c_eta is None else np.array(c_eta, np.float64, copy=True)
+    share, R = np.float64(share), np.float64(sense_range)
+    order = np.nonzero(present(st, rad, None if group is None else grp))[0]
+    order = order[np.argsort(x[order], kind="stable")]
+    xs = x[order]
+    I, J, D2 = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0)]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        reach = R * (1.0 + 2.0 ** -10)
+        lo, hi = np.searchsorted(xs, xs - reach, "left"), np.searchsorted(xs, xs + reach, "right")
+        cnt = hi - lo
+        ends = np.cumsum(cnt)
+        a = 0
+        while a < len(order):
+            b = max(a + 1, int(np.searchsorted(ends, (ends[a - 1] if a else 0) + pairs_per_chunk, "right")))
+            c = cnt[a:b]
+            i = order[np.repeat(np.arange(a, b), c)]
+            j = order[np.arange(c.sum()) - np.repeat(np.cumsum(c) - c, c) + np.repeat(lo[a:b], c)]
+            keep = (np.abs(y[i] - y[j]) <= reach) & (i != j) & (grp[i] == grp[j])
+            i, j = i[keep], j[keep]
+            dx, dy = x[i] - x[j], y[i] - y[j]
+            d2 = dx * dx + dy * dy
+            near = np.sqrt(d2) < R
+            I.append(i[near]); J.append(j[near]); D2.append(d2[near])
+            a = b
+        I, J, D2 = np.concatenate(I), np.concatenate(J), np.concatenate(D2)
+        by = np.lexsort((J, D2, I))                                   # robot by robot, ascending (d2, j)
+        I, J = I[by], J[by]
+        n_near = np.bincount(I, minlength=B)
+        rank = np.arange(len(I)) - (np.cumsum(n_near) - n_near)[I]
+        n_rows = np.minimum(np.minimum(k_rows, n_obs_max - fs), n_near)
+        row = rank < n_rows[I]
+        i, j, rank = I[row], J[row], rank[row]
+        dx, dy = x[i] - x[j], y[i] - y[j]
+        d2 = dx * dx + dy * dy
+        dist = np.sqrt(d2)
+        rs = rad[i] + rad[j]
+        offset = rs + share * (dist - rs)
+        ex, ey = dx / dist, dy / dist
+        ce[np.arange(n_obs_max)[None, :] >= (fs + n_rows)[:, None]] = 0.0
+        ce[i, fs[i] + rank] = np.stack([x[j] + offset * ex, y[j] + offset * ey, ex, ey], 1)
+    nbr = np.full((B, k_rows), -1, np.int32)
+    nbr[i, rank] = j
+    return dict(c_eta=ce, n_rows=n_rows.astype(np.int32), n_near=n_near.astype(np.int32), neighbours=nbr)
+
+
 def plan_step_rows(state, goal, first_foot, rows, P, exact=False, delta=0.0):
     """lipmpc_oracle.plan_step against given half-spaces ``rows`` [n,4] = (c_x, c_y, eta_x, eta_y): the step oracle derives its
     rows from rings through list_c_and_eta, which is stood in for here (the rows as data, as lipmpc_plan_step_batch_c_eta
