@@ -97,6 +97,10 @@ SIGNATURES = {
     "lipmpc_grid_frontier_assign_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field start may_claim r_inflate:i32 "
                                                        "r_claim:i32 max_claims:i32 max_seg:i32 S_max:i32 work sub_goals n_sub status path_cost "
                                                        "target_cell claim_round n_claims hip_stream"),
+    "lipmpc_grid_frontier_assign_keep_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field start may_claim "
+                                                            "prev_target r_inflate:i32 r_claim:i32 r_keep:i32 keep_ratio16:i32 "
+                                                            "keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work sub_goals n_sub status "
+                                                            "path_cost target_cell claim_round n_claims kept n_kept hip_stream"),
     "lipmpc_grid_frontier_gain_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 evidence t_free:i32 t_occ:i32 frontier r_view:i32 gain "
                                                      "hip_stream"),
     "lipmpc_grid_frontier_utility_field_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 frontier field gain w_gain:i32 g_cap:i32 "
@@ -133,6 +137,12 @@ SIGNATURES = {
                                                              "r_inflate:i32 r_claim:i32 max_claims:i32 max_seg:i32 S_max:i32 work work_bytes:i64 "
                                                              "max_rounds:i32 sub_goals n_sub status path_cost target_cell claim_round n_claims "
                                                              "claims_settled hip_stream"),
+    "lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes": _sig(C.c_int64, "W:i32 H:i32"),
+    "lipmpc_grid_frontier_assign_keep_tiled_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field settled start "
+                                                                  "may_claim prev_target r_inflate:i32 r_claim:i32 r_keep:i32 "
+                                                                  "keep_ratio16:i32 keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work "
+                                                                  "work_bytes:i64 max_rounds:i32 sub_goals n_sub status path_cost "
+                                                                  "target_cell claim_round n_claims kept n_kept claims_settled hip_stream"),
     "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
                                              "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),

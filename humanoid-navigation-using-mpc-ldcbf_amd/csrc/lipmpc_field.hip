@@ -731,6 +731,269 @@ __global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_global_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// claim hysteresis (lipmpc_grid_frontier_assign_keep_batch): a KEEP PHASE ahead of the greedy rounds, on a body of its own -- the
+// two kernels above and their code objects stay what they were.  A robot with a previous target keeps what is left of it (the
+// ANCHOR: the source nearest to it within r_keep) when the single-source field from the anchor says that it is reachable and not
+// much farther than the robot's nearest frontier; a keeper's disc leaves the sources as a winner's does.  Every relaxation of the
+// map, keep attempt or greedy round, is a SLOT, and a call makes at most max_claims of them.
+// LDS: the assign kernels' layout with KEEP_WORDS in place of ASSIGN_WORDS -- the spare word 3 is the next keep candidate of the
+// chunk; after the nine parked pairs come three more pointers (kept, the given field, prev_target), four scalars of the lane
+// that walks (keep_ratio16, keep_slack, max_seg, S_max), the slot's entry cell and the count of U
+constexpr int KEEP_WORDS = 34;
+constexpr int R_KEEP_MAX = 64, KEEP_RATIO_MIN = 16, KEEP_RATIO_MAX = 1024, KEEP_SLACK_MAX = 4096;
+__host__ __device__ inline int64_t keep_bitmap_words(int64_t ncells) { return 2 * bitmap_words(ncells) + KEEP_WORDS; }
+__host__ __device__ inline int64_t keep_lds_bytes(int64_t ncells, bool in_lds) {
+  return 4 * (keep_bitmap_words(ncells) + (in_lds ? ncells : 0));
+}
+
+inline bool keep_fits_lds(int64_t ncells) { return keep_lds_bytes(ncells, true) + LDS_SLACK <= LDS_LIMIT; }
+
+// what the one-workgroup body and the tiled kernels share of the keep rule.
+// the anchor search, a workgroup of FIELD_THREADS: this thread's wave's least (d^2 << 32 | cell) over the sources within r_keep of
+// the previous target pt (the window clipped to the grid), ~0 for none; the caller reduces the waves with a 64-bit atomicMin
+__device__ __forceinline__ unsigned long long anchor_key(const uint32_t* src, int pt, int r_keep, int W, int H) {
+  const int pi = pt / H, pj = pt - pi * H;
+  const int i_lo = max(pi - r_keep, 0), i_hi = min(pi + r_keep, W - 1), j_lo = max(pj - r_keep, 0), j_hi = min(pj + r_keep, H - 1);
+  const int nj = j_hi - j_lo + 1, count = (i_hi - i_lo + 1) * nj;
+  unsigned long long mine = ~0ull;
+  for (int idx = threadIdx.x; idx < count; idx += FIELD_THREADS) {
+    const int q = idx / nj, i = i_lo + q, j = j_lo + idx - q * nj, c = i * H + j;
+    const int d2 = (i - pi) * (i - pi) + (j - pj) * (j - pj);
+    if (d2 <= r_keep * r_keep && bit_of(src, c)) mine = min(mine, ((unsigned long long)(uint32_t)d2 << 32) | (uint32_t)c);
+  }
+  for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
+  return mine;
+}
+
+// a previous target that is a cell of the grid (anything else is "none")
+__device__ __forceinline__ bool is_cell(int32_t prev, int ncells) { return (uint32_t)prev < (uint32_t)ncells; }
+
+// THE TEST (one lane): the robot whose start cell is `cell` enters the slot's field at s (-1: nowhere); it keeps iff it also
+// enters the given field, at e, and 16 keepfield[s] <= keep_ratio16 given[e] + 80 keep_slack in 64 bits
+template <typename FieldPtr>
+__device__ __forceinline__ bool keep_passes(FieldPtr fld, const uint32_t* __restrict__ given, int W, int H, int cell, int s, int r_inflate,
+                                            uint32_t keep_ratio16, uint32_t keep_slack) {
+  const int ci = cell / H;
+  const int e = given[cell] != INF ? cell : snap(given, W, H, ci, cell - ci * H, r_inflate);
+  const unsigned long long cost = ld(fld + max(s, 0)), near = given[max(e, 0)];
+  return s >= 0 && e >= 0 && 16ull * cost <= (unsigned long long)keep_ratio16 * near + 80ull * (unsigned long long)keep_slack;
+}
+
+template <typename FieldPtr>
+__device__ __forceinline__ void assign_keep_body(FieldPtr fld, uint32_t* bm, int64_t B, int W, int H, double ox, double oy, double dx,
+                                                 double dy, const uint8_t* __restrict__ frontier, const uint32_t* __restrict__ field,
+                                                 const double* __restrict__ start, const int8_t* __restrict__ may_claim,
+                                                 const int32_t* __restrict__ prev_target, int r_inflate, int r_claim, int r_keep,
+                                                 int keep_ratio16, int keep_slack, int max_claims, int max_seg, int S_max,
+                                                 double* __restrict__ sub_goals, int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
+                                                 double* __restrict__ path_cost, int32_t* __restrict__ target_cell, int32_t* claim_round,
+                                                 int32_t* __restrict__ n_claims, int8_t* __restrict__ kept, int32_t* __restrict__ n_kept) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  uint32_t *blk = bm, *src = bm + words, *tgt = bm + 2 * words + 2, *next = bm + 2 * words + 3;
+  unsigned long long* key = (unsigned long long*)(bm + 2 * words);
+  uint32_t* parked = bm + 2 * words + 4;                  // 64-bit values as word pairs
+  auto park = [&](int slot, unsigned long long v) { parked[2 * slot] = (uint32_t)v; parked[2 * slot + 1] = (uint32_t)(v >> 32); };
+  auto unpark = [&](int slot) { return ((unsigned long long)parked[2 * slot + 1] << 32) | parked[2 * slot]; };
+
+  // U_0, each robot with its start cell (assign_body's encoding in claim_round); nobody has kept anything yet
+  int in_u = 0;
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+    const int sb = status[b];
+    int si = 0, sj = 0, v = -1;
+    if (max_claims > 0 && (sb == LIPMPC_RRT_FOUND || sb == LIPMPC_RRT_PATH_OVERFLOW) && (!may_claim || may_claim[b]) &&
+        cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
+      v = -2 - (si * H + sj);
+    claim_round[b] = v;
+    kept[b] = 0;
+    in_u += v <= -2;
+  }
+  int claims = 0, keeps = 0, slots = 0;
+  if (max_claims > 0) {
+    for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+      const int c = c0 + lane;
+      const bool pass = c < ncells && field[c] != INF;
+      const uint64_t mb = __ballot(c < ncells && !pass), ms = __ballot(pass && frontier[c] != 0);
+      if (lane == 0) {
+        blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32);
+        src[c0 >> 5] = (uint32_t)ms; src[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      }
+    }
+    if (tid < 2) { blk[words - 2 + tid] = 0; src[words - 2 + tid] = 0; }
+    if (tid == 0) {
+      *key = ~0ull;
+      *next = INF;
+      parked[29] = 0;
+      park(0, __double_as_longlong(ox)); park(1, __double_as_longlong(oy)); park(2, __double_as_longlong(dx));
+      park(3, __double_as_longlong(dy));
+      park(4, (unsigned long long)sub_goals); park(5, (unsigned long long)n_sub); park(6, (unsigned long long)status);
+      park(7, (unsigned long long)path_cost); park(8, (unsigned long long)target_cell);
+      park(9, (unsigned long long)kept); park(10, (unsigned long long)field); park(11, (unsigned long long)prev_target);
+      parked[24] = (uint32_t)keep_ratio16; parked[25] = (uint32_t)keep_slack; parked[26] = (uint32_t)max_seg; parked[27] = (uint32_t)S_max;
+    }
+    __syncthreads();
+    // |U|: counted once, one less with every winner -- when the last of U has won, kept or claimed, no further slot is begun
+    if (in_u) atomicAdd(parked + 29, (uint32_t)in_u);
+    __syncthreads();
+    int left = (int)parked[29];
+
+    // (one lane) the rows of robot wb, who enters the slot's field at s and wins as number k: the path rule, as assign_body
+    // writes a winner's.  Returns the target cell, or -1 (a fixed point always has a descent: it cannot happen)
+    auto write_rows = [&](int64_t wb, int s, int k) {
+      const double wox = __longlong_as_double(unpark(0)), woy = __longlong_as_double(unpark(1));
+      const double wdx = __longlong_as_double(unpark(2)), wdy = __longlong_as_double(unpark(3));
+      const int S_max = (int)parked[27], max_seg = (int)parked[26];
+      double* sg = (double*)unpark(4) + wb * (int64_t)S_max * 2;
+      int last_cell = s, n = 0;
+      for (int pass = 0; pass < 2 && n >= 0 && n <= S_max; ++pass)
+        n = walk_in(fld, W, H, s, max_seg, wox, woy, wdx, wdy, pass ? sg : nullptr, last_cell);
+      if (n <= 0) return -1;
+      if (n <= S_max) centre(last_cell, H, wox, woy, wdx, wdy, sg + 2 * (n - 1));
+      ((int32_t*)unpark(6))[wb] = n <= S_max ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+      ((int32_t*)unpark(5))[wb] = n <= S_max ? n : 0;
+      ((double*)unpark(7))[wb] = (double)ld(fld + s) / 5.0;
+      ((int32_t*)unpark(8))[wb] = last_cell;
+      claim_round[wb] = k;
+      return last_cell;
+    };
+    // the sources outside the disc of r_claim round cell t, clipped to the grid
+    auto take_disc = [&](int t) {
+      const int ti = t / H, tj = t - ti * H, r2 = r_claim * r_claim;
+      const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
+      for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+        const int i = c / H, j = c - i * H;
+        if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+      }
+      __syncthreads();
+    };
+
+    // THE SLOTS.  One loop serves both phases, so that the relaxation and the walk are compiled once.  While `keeping`, a slot
+    // belongs to the next robot of U_0 whose previous target has an anchor -- ascending index: a chunk of FIELD_THREADS robots at
+    // a time, a thread per robot, `next` hands out the chunk's candidates one by one; after the last of them, to a greedy round of
+    // assign_body (a = -1).
+    auto is_candidate = [&](int64_t b) {
+      return b < B && claim_round[b] <= -2 && is_cell(((const int32_t*)unpark(11))[b], ncells);
+    };
+    int64_t base = 0;
+    int cursor = 0;
+    bool keeping = true, candidate = is_candidate(tid);
+    while (slots < max_claims && left > 0) {
+      int a = -1;
+      int64_t wb = 0;
+      while (keeping) {
+        if (candidate && tid >= cursor) atomicMin(next, (uint32_t)tid);
+        __syncthreads();
+        const uint32_t nx = *next;
+        __syncthreads();                                  // everybody has read it
+        if (nx == INF) {                                  // the chunk is done
+          base += FIELD_THREADS;
+          cursor = 0;
+          keeping = base < B;
+          candidate = keeping && is_candidate(base + tid);
+          continue;
+        }
+        if (tid == 0) *next = INF;                        // (the next minimum comes at least two barriers on)
+        cursor = (int)nx + 1;
+        wb = base + nx;
+        // the anchor: the source within r_keep of the previous target with the least (d^2, cell)
+        const unsigned long long mine = anchor_key(src, ((const int32_t*)unpark(11))[wb], r_keep, W, H);
+        if (lane == 0 && mine != ~0ull) atomicMin(key, mine);
+        __syncthreads();
+        const unsigned long long found = *key;
+        __syncthreads();                                  // everybody has read it
+        if (found == ~0ull) continue;                     // nothing is left of the target: no slot is spent
+        if (tid == 0) *key = ~0ull;
+        a = (int)(found & 0xFFFFFFFFull);
+        break;
+      }
+      ++slots;
+      // the slot's field: the least cost to the anchor alone, or to what is left of the sources
+      int any = 0;
+      for (int c = tid; c < ncells; c += FIELD_THREADS) {
+        const bool s = a >= 0 ? c == a : bit_of(src, c);
+        st(fld + c, s ? 0u : INF);
+        any |= s;
+      }
+      if (!__syncthreads_or(any)) break;
+      relax(fld, blk, W, H);
+      if (a < 0) {
+        // the candidates of U, and the least (cost, b) among them
+        unsigned long long mine = ~0ull;
+        for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+          const int v = claim_round[b];
+          if (v > -2) continue;
+          const int s = claim_cell(fld, W, H, -2 - v, r_inflate);
+          if (s >= 0) mine = min(mine, ((unsigned long long)ld(fld + s) << 32) | (unsigned long long)b);
+        }
+        for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
+        if (lane == 0 && mine != ~0ull) atomicMin(key, mine);
+        __syncthreads();
+        const unsigned long long win = *key;
+        if (win == ~0ull) break;                          // no candidate: the rounds end
+        wb = (int64_t)(win & 0xFFFFFFFFull);
+      }
+      if (tid == 0) {
+        // where wb enters the slot's field; a keeper also has to pass the test, against the given field at its entry into that
+        const int cell = -2 - claim_round[wb];
+        const int s = claim_cell(fld, W, H, cell, r_inflate);
+        bool ok = s >= 0;
+        if (a >= 0) ok = keep_passes(fld, (const uint32_t*)unpark(10), W, H, cell, s, r_inflate, parked[24], parked[25]);
+        parked[28] = ok ? (uint32_t)s : INF;
+      }
+      __syncthreads();
+      const uint32_t entry = parked[28];
+      if (tid == 0) *key = ~0ull;                         // (everybody has read it; the next minimum comes two barriers on)
+      if (entry == INF) {
+        if (a >= 0) continue;                             // not kept: the robot stays in U, the slot is spent
+        break;
+      }
+      if (tid == 0) {
+        const int last = write_rows(wb, (int)entry, claims);
+        if (last >= 0 && a >= 0) ((int8_t*)unpark(9))[wb] = 1;
+        *tgt = last >= 0 ? (uint32_t)last : INF;          // (a fixed point always has a descent: INF cannot happen)
+      }
+      __syncthreads();
+      const uint32_t t = *tgt;
+      if (t == INF) break;
+      ++claims;
+      if (a >= 0) ++keeps;
+      if (--left == 0) break;                             // U is used up
+      if (slots >= max_claims) break;
+      take_disc((int)t);
+    }
+    // the followers: still in U
+    __syncthreads();
+    for (int64_t b = tid; b < B; b += FIELD_THREADS)
+      if (claim_round[b] < -1) claim_round[b] = -1;
+  }
+  if (tid == 0) { n_claims[0] = claims; n_kept[0] = keeps; }
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_keep_lds_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const double* __restrict__ start, const int8_t* __restrict__ may_claim,
+    const int32_t* __restrict__ prev_target, int r_inflate, int r_claim, int r_keep, int keep_ratio16, int keep_slack, int max_claims,
+    int max_seg, int S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+    int32_t* claim_round, int32_t* __restrict__ n_claims, int8_t* __restrict__ kept, int32_t* __restrict__ n_kept) {
+  extern __shared__ uint32_t field_lds[];
+  assign_keep_body(field_lds + keep_bitmap_words((int64_t)W * H), field_lds, B, W, H, ox, oy, dx, dy, frontier, field, start, may_claim,
+                   prev_target, r_inflate, r_claim, r_keep, keep_ratio16, keep_slack, max_claims, max_seg, S_max, sub_goals, n_sub, status,
+                   path_cost, target_cell, claim_round, n_claims, kept, n_kept);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_keep_global_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const double* __restrict__ start, const int8_t* __restrict__ may_claim,
+    const int32_t* __restrict__ prev_target, int r_inflate, int r_claim, int r_keep, int keep_ratio16, int keep_slack, int max_claims,
+    int max_seg, int S_max, uint32_t* work, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+    int32_t* claim_round, int32_t* __restrict__ n_claims, int8_t* __restrict__ kept, int32_t* __restrict__ n_kept) {
+  extern __shared__ uint32_t field_lds[];
+  assign_keep_body(work, field_lds, B, W, H, ox, oy, dx, dy, frontier, field, start, may_claim, prev_target, r_inflate, r_claim, r_keep,
+                   keep_ratio16, keep_slack, max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, claim_round,
+                   n_claims, kept, n_kept);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // the informed explorer (lipmpc_grid_frontier_gain_batch, lipmpc_grid_frontier_utility_field_batch,
 // lipmpc_grid_frontier_utility_path_batch): what a robot would see from a frontier cell, the cost-to-go field whose sources start
 // ahead by what they reveal, and the paths down it.
@@ -1099,6 +1362,42 @@ extern "C" int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t 
     hipLaunchKernelGGL(frontier_assign_global_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
                        cell[1], frontier, field, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max, work, sub_goals,
                        n_sub, status, path_cost, target_cell, claim_round, n_claims);
+  }
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_assign_keep_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                                      const uint8_t* frontier, const uint32_t* field, const double* start,
+                                                      const int8_t* may_claim, const int32_t* prev_target, int32_t r_inflate,
+                                                      int32_t r_claim, int32_t r_keep, int32_t keep_ratio16, int32_t keep_slack,
+                                                      int32_t max_claims, int32_t max_seg, int32_t S_max, uint32_t* work,
+                                                      double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                                      int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, int8_t* kept,
+                                                      int32_t* n_kept, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
+      keep_slack > KEEP_SLACK_MAX || !frontier || !field || !start || !prev_target || !work || !sub_goals || !n_sub || !status ||
+      !path_cost || !target_cell || !claim_round || !n_claims || !kept || !n_kept)
+    return LIPMPC_E_ARG;
+  if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t ncells = (int64_t)W * H;
+  const bool in_lds = keep_fits_lds(ncells);
+  const size_t lds = (size_t)keep_lds_bytes(ncells, in_lds);
+  if (in_lds) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_keep_lds_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return LIPMPC_E_HIP;
+    hipLaunchKernelGGL(frontier_assign_keep_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
+                       cell[1], frontier, field, start, may_claim, prev_target, r_inflate, r_claim, r_keep, keep_ratio16, keep_slack,
+                       max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims, kept, n_kept);
+  } else {
+    hipLaunchKernelGGL(frontier_assign_keep_global_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
+                       cell[1], frontier, field, start, may_claim, prev_target, r_inflate, r_claim, r_keep, keep_ratio16, keep_slack,
+                       max_claims, max_seg, S_max, work, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims, kept,
+                       n_kept);
   }
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
@@ -1996,6 +2295,204 @@ __global__ void __launch_bounds__(SETUP_THREADS) claim_finish_kernel(int64_t B, 
   if (b == 0) { n_claims[0] = (int32_t)ctl[CTL_CLAIMS]; claims_settled[0] = ctl[CTL_UNSETTLED] == 0; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// claim hysteresis by tiles (lipmpc_grid_frontier_assign_keep_tiled_batch): per SLOT a mode kernel decides whose the slot is --
+// the next keep candidate that has an anchor, else a greedy round -- and the claim kernels' siblings below read the mode.  The
+// workspace is the tiled claim call's with KEEP_CTL control words in place of CLAIM_CTL; k is the control word CTL_CLAIMS, not
+// the host's slot index.  tiled_round_kernel, tiled_settle_kernel and the kernels above are not touched.
+constexpr int KEEP_CTL = 16;
+constexpr int CTL_MODE = 8, CTL_ROBOT = 9, CTL_ANCHOR = 10, CTL_CURSOR = 11, CTL_KEPT = 12;      // MODE: 1 = a keep slot, 0 = a greedy round
+
+inline ClaimLayout keep_claim_layout(int64_t W, int64_t H) {
+  ClaimLayout l = claim_layout(W, H);
+  const int64_t more = KEEP_CTL - CLAIM_CTL;
+  l.blocked += more; l.sources += more; l.flags0 += more; l.flags1 += more; l.field += more; l.words += more;
+  return l;
+}
+inline int64_t keep_claim_bytes(int64_t W, int64_t H) { return 4 * keep_claim_layout(W, H).words + 256; }
+
+// once per call, over robots: claim_robots_kernel's U_0, nobody has kept anything, and the keep control words
+__global__ void __launch_bounds__(SETUP_THREADS) keep_robots_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
+                                                                    const double* __restrict__ start,
+                                                                    const int8_t* __restrict__ may_claim, int max_claims,
+                                                                    const int32_t* __restrict__ status, int32_t* __restrict__ claim_round,
+                                                                    int8_t* __restrict__ kept, uint32_t* __restrict__ ctl) {
+  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  if (b == 0) { ctl[CTL_MODE] = 0; ctl[CTL_ROBOT] = 0; ctl[CTL_ANCHOR] = INF; ctl[CTL_CURSOR] = 0; ctl[CTL_KEPT] = 0; }
+  if (b >= B) return;
+  const int sb = status[b];
+  int si = 0, sj = 0, v = -1;
+  if (max_claims > 0 && (sb == LIPMPC_RRT_FOUND || sb == LIPMPC_RRT_PATH_OVERFLOW) && (!may_claim || may_claim[b]) &&
+      cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
+    v = -2 - (si * H + sj);
+  claim_round[b] = v;
+  kept[b] = 0;
+}
+
+// the mode of the next slot, ONE workgroup: from the cursor on, the first robot of U with a previous target that has an anchor in
+// what is left of the sources (assign_keep_body's search, chunk by chunk); none: every slot from here on is a greedy round
+__global__ void __launch_bounds__(FIELD_THREADS) keep_mode_kernel(int64_t B, int W, int H, int r_keep, uint32_t* ctl,
+                                                                  const uint32_t* __restrict__ src,
+                                                                  const int32_t* __restrict__ claim_round,
+                                                                  const int32_t* __restrict__ prev_target) {
+  __shared__ uint32_t next;
+  __shared__ unsigned long long key;
+  const int tid = threadIdx.x, lane = tid & 63, ncells = W * H;
+  const bool stopped = ctl[CTL_STOPPED] != 0;
+  const int64_t from = ctl[CTL_CURSOR];
+  if (tid == 0) { next = INF; key = ~0ull; }
+  __syncthreads();                                      // (everybody has read the control words)
+  if (stopped) return;
+  for (int64_t base = from; base < B; base += FIELD_THREADS) {
+    const int64_t mb = base + tid;
+    const bool candidate = mb < B && claim_round[mb] <= -2 && is_cell(prev_target[mb], ncells);
+    for (int cursor = 0;;) {
+      if (candidate && tid >= cursor) atomicMin(&next, (uint32_t)tid);
+      __syncthreads();
+      const uint32_t nx = next;
+      __syncthreads();                                  // everybody has read it
+      if (nx == INF) break;
+      if (tid == 0) next = INF;
+      cursor = (int)nx + 1;
+      const int64_t wb = base + nx;
+      const unsigned long long mine = anchor_key(src, prev_target[wb], r_keep, W, H);
+      if (lane == 0 && mine != ~0ull) atomicMin(&key, mine);
+      __syncthreads();
+      const unsigned long long found = key;
+      if (found == ~0ull) continue;                     // nothing is left of the target: no slot is spent (the key is still ~0)
+      if (tid == 0) {
+        ctl[CTL_MODE] = 1; ctl[CTL_ROBOT] = (uint32_t)wb; ctl[CTL_ANCHOR] = (uint32_t)(found & 0xFFFFFFFFull);
+        ctl[CTL_CURSOR] = (uint32_t)(wb + 1);
+      }
+      return;
+    }
+  }
+  if (tid == 0) { ctl[CTL_MODE] = 0; ctl[CTL_ANCHOR] = INF; ctl[CTL_CURSOR] = (uint32_t)B; }
+}
+
+// claim_seed_kernel with the mode: a keep slot's only source is the anchor
+__global__ void __launch_bounds__(TILE_THREADS) keep_seed_kernel(int W, int H, int tiles_j, uint32_t* __restrict__ ctl,
+                                                                 const uint32_t* __restrict__ src, uint32_t* __restrict__ field_k,
+                                                                 uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
+  if (ld_agent(ctl + CTL_STOPPED)) return;              // (both flag arrays are clear: whoever stopped the call cleared them)
+  const bool keep = ld_agent(ctl + CTL_MODE) != 0;
+  const int anchor = (int)ld_agent(ctl + CTL_ANCHOR);
+  const int tile = blockIdx.x, tid = threadIdx.x;
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  int own = 0, near = 0;
+  for (int l = tid; l < HALO_CELLS; l += TILE_THREADS) {
+    const int li = l / HALO_H, lj = l - li * HALO_H, i = i0 + li - 1, j = j0 + lj - 1;
+    if ((unsigned)i >= (unsigned)W || (unsigned)j >= (unsigned)H) continue;
+    const bool s = keep ? i * H + j == anchor : bit_of(src, i * H + j);
+    const bool inner = li >= 1 && li <= TILE_W && lj >= 1 && lj <= TILE_H;
+    if (inner) field_k[i * H + j] = s ? 0u : INF;
+    own |= s & inner;
+    near |= s;
+  }
+  near = __syncthreads_or(near);
+  if (tid == 0) { flags0[tile] = near != 0; flags1[tile] = 0; }
+  if (own) st_agent(ctl + CTL_ANY_SOURCE, 1u);
+}
+
+// claim_pick_kernel with the mode: in a keep slot the slot's robot is the only candidate
+__global__ void __launch_bounds__(SETUP_THREADS) keep_pick_kernel(int64_t B, int W, int H, int r_inflate, uint32_t* ctl,
+                                                                  const uint32_t* field_k, const int32_t* __restrict__ claim_round) {
+  if (ld_agent(ctl + CTL_STOPPED)) return;
+  const bool no_source = ld_agent(ctl + CTL_ANY_SOURCE) == 0, unsettled = ld_agent(ctl + CTL_ROUND_SETTLED) == 0;
+  if (no_source || unsettled) return;
+  const bool keep = ld_agent(ctl + CTL_MODE) != 0;
+  const int64_t only = ld_agent(ctl + CTL_ROBOT);
+  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  unsigned long long mine = ~0ull;
+  if (b < B && (!keep || b == only)) {
+    const int v = claim_round[b];
+    if (v <= -2) {
+      const int s = claim_cell(field_k, W, H, -2 - v, r_inflate);
+      if (s >= 0) mine = ((unsigned long long)ld(field_k + s) << 32) | (unsigned long long)b;
+    }
+  }
+  for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
+  if ((threadIdx.x & 63) == 0 && mine != ~0ull) atomicMin((unsigned long long*)ctl, mine);
+}
+
+// claim_take_kernel with the mode, ONE workgroup: a keeper has to pass the test before its rows are written; a keep slot whose
+// robot has no entry or fails the test ends without a winner and without stopping the call.  k is the control word.
+__global__ void __launch_bounds__(FIELD_THREADS) keep_take_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
+                                                                  int r_inflate, int r_claim, int keep_ratio16, int keep_slack, int max_seg,
+                                                                  int S_max, int tiles, uint32_t* ctl, uint32_t* src,
+                                                                  const uint32_t* field_k, const uint32_t* __restrict__ field,
+                                                                  uint32_t* flags, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                                                  double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                                                  int8_t* kept) {
+  const int tid = threadIdx.x;
+  const bool stopped = ctl[CTL_STOPPED] != 0, no_source = ctl[CTL_ANY_SOURCE] == 0, unsettled = ctl[CTL_ROUND_SETTLED] == 0;
+  const bool keep = ctl[CTL_MODE] != 0;
+  const int k = (int)ctl[CTL_CLAIMS];
+  const unsigned long long win = *(const unsigned long long*)ctl;
+  __syncthreads();                                      // (everybody has read the control words)
+  for (int t = tid; t < 2 * tiles; t += FIELD_THREADS) flags[t] = 0;
+  if (tid == 0) { ctl[0] = ctl[1] = INF; ctl[CTL_ANY_SOURCE] = 0; ctl[CTL_ROUND_SETTLED] = 1; ctl[CTL_TARGET] = INF; }
+  if (stopped) return;
+  if (no_source || unsettled || (win == ~0ull && !keep)) {      // no source left, a field that did not settle, no candidate
+    if (tid == 0) { ctl[CTL_STOPPED] = 1; if (!no_source && unsettled) ctl[CTL_UNSETTLED] = 1; }
+    return;
+  }
+  if (win == ~0ull) return;                             // a keep slot whose anchor is out of the robot's reach: spent, nothing else
+  const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
+  __syncthreads();                                      // (lane 0's reset of the target word comes before its new value)
+  if (tid == 0) {
+    const int cell = -2 - claim_round[wb];
+    const int s = claim_cell(field_k, W, H, cell, r_inflate);
+    bool ok = s >= 0;
+    if (keep) ok = keep_passes(field_k, field, W, H, cell, s, r_inflate, (uint32_t)keep_ratio16, (uint32_t)keep_slack);
+    if (ok) {
+      double* sg = sub_goals + wb * (int64_t)S_max * 2;
+      int last_cell = s, n = 0;
+      for (int pass = 0; pass < 2 && n >= 0 && n <= S_max; ++pass)
+        n = walk_in(field_k, W, H, s, max_seg, ox, oy, dx, dy, pass ? sg : nullptr, last_cell);
+      if (n > 0) {
+        if (n <= S_max) centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
+        status[wb] = n <= S_max ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+        n_sub[wb] = n <= S_max ? n : 0;
+        path_cost[wb] = (double)ld(field_k + s) / 5.0;
+        target_cell[wb] = last_cell;
+        claim_round[wb] = k;
+        ctl[CTL_CLAIMS] = (uint32_t)(k + 1);
+        if (keep) { kept[wb] = 1; ctl[CTL_KEPT] += 1; }
+        ctl[CTL_TARGET] = (uint32_t)last_cell;
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t t = ctl[CTL_TARGET];
+  if (t == INF) {                                       // a keeper that failed the test stays in U; (a winner always has a descent)
+    if (tid == 0 && !keep) ctl[CTL_STOPPED] = 1;
+    return;
+  }
+  int eligible = 0;
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) eligible |= claim_round[b] <= -2;
+  const int more = __syncthreads_or(eligible);
+  if (!more) {                                          // U is used up
+    if (tid == 0) ctl[CTL_STOPPED] = 1;
+    return;
+  }
+  const int ti = (int)t / H, tj = (int)t - ti * H, r2 = r_claim * r_claim;
+  const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
+  for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+    const int i = c / H, j = c - i * H;
+    if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+  }
+}
+
+// the last kernel, over robots: claim_finish_kernel's outputs and n_kept
+__global__ void __launch_bounds__(SETUP_THREADS) keep_finish_kernel(int64_t B, const uint32_t* __restrict__ ctl, int32_t* claim_round,
+                                                                    int32_t* __restrict__ n_claims, int32_t* __restrict__ n_kept,
+                                                                    int32_t* __restrict__ claims_settled) {
+  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  if (b < B && claim_round[b] < -1) claim_round[b] = -1;
+  if (b == 0) { n_claims[0] = (int32_t)ctl[CTL_CLAIMS]; n_kept[0] = (int32_t)ctl[CTL_KEPT]; claims_settled[0] = ctl[CTL_UNSETTLED] == 0; }
+}
+
 // E_ARG of a grid's placement
 bool bad_placement(const double* origin, const double* cell) {
   if (!origin || !cell) return true;
@@ -2119,5 +2616,61 @@ extern "C" int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, in
                        tiles, w, w + c.sources, w + c.field, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell, claim_round);
   }
   hipLaunchKernelGGL(claim_finish_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, w, claim_round, n_claims, claims_settled);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int64_t lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes(int32_t W, int32_t H) {
+  if (W < 2 || H < 2) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  return keep_claim_bytes(W, H);
+}
+
+extern "C" int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin,
+                                                            const double* cell, const uint8_t* frontier, const uint32_t* field,
+                                                            const int32_t* settled, const double* start, const int8_t* may_claim,
+                                                            const int32_t* prev_target, int32_t r_inflate, int32_t r_claim,
+                                                            int32_t r_keep, int32_t keep_ratio16, int32_t keep_slack, int32_t max_claims,
+                                                            int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes,
+                                                            int32_t max_rounds, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                                            double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                                            int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled,
+                                                            void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
+      keep_slack > KEEP_SLACK_MAX || !frontier || !field || !settled || !start || !prev_target || !work || !sub_goals || !n_sub || !status ||
+      !path_cost || !target_cell || !claim_round || !n_claims || !kept || !n_kept || !claims_settled || ((uintptr_t)work & 7) != 0 ||
+      max_rounds < 1 || max_rounds > MAX_ROUNDS || (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
+    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  if (work_bytes < keep_claim_bytes(W, H)) return LIPMPC_E_ARG;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const ClaimLayout c = keep_claim_layout(W, H);
+  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
+  const unsigned robots = (unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS);
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  uint32_t* w = (uint32_t*)work;
+  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
+  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
+  // 3 launches round the slots, and per slot the mode, the seed, max_rounds rounds and their settle, the pick and the take:
+  // max_claims * (max_rounds + 5) + 3
+  hipLaunchKernelGGL(claim_setup_kernel, dim3((unsigned)chunks), dim3(SETUP_THREADS), 0, s, ncells, c.tiles, max_claims, frontier, field,
+                     settled, w, w + c.blocked, w + c.sources, w + c.flags0);
+  hipLaunchKernelGGL(keep_robots_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims,
+                     status, claim_round, kept, w);
+  for (int slot = 0; slot < max_claims; ++slot) {
+    hipLaunchKernelGGL(keep_mode_kernel, dim3(1), dim3(FIELD_THREADS), 0, s, B, W, H, r_keep, w, w + c.sources, claim_round, prev_target);
+    hipLaunchKernelGGL(keep_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, w + c.field,
+                       w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
+    hipLaunchKernelGGL(keep_pick_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+    hipLaunchKernelGGL(keep_take_kernel, dim3(1), dim3(FIELD_THREADS), 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, keep_ratio16,
+                       keep_slack, max_seg, S_max, tiles, w, w + c.sources, w + c.field, field, w + c.flags0, sub_goals, n_sub, status,
+                       path_cost, target_cell, claim_round, kept);
+  }
+  hipLaunchKernelGGL(keep_finish_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, w, claim_round, n_claims, n_kept, claims_settled);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

@@ -602,6 +602,11 @@ class UnknownEnvFleet:
         never hold a frontier, or the fleet never finishes -- and a robot in a capture step (``recover``) is a follower for that
         replan: it keeps its nearest-frontier plan.  The result then gains n_claims [n_replans] (device tensor: the claims of
         every replan; the closing plan's are not counted).  With any other explorer nothing changes.
+        With a ``CoordinatedFrontierPlanner`` that has ``r_keep`` every replan (the closing one included) is ``explorer.replan``
+        with the previous replan's targets as ``prev_target``: a robot's ``target_cell`` where that replan said RRT_FOUND, else
+        -1, and -1 for everybody at the first replan; they are kept in a buffer of the fleet's own, on the device.  The result
+        then gains n_kept [n_replans] (the keepers of every replan) and n_jumps [n_replans]: the robots whose target is FOUND at
+        this replan and was at the previous one, and lies more than ``r_keep`` cells (Euclidean) from it.
         The model's limits: with a plain ``FrontierPlanner`` every robot goes to ITS nearest frontier (no task assignment:
         ``CoordinatedFrontierPlanner`` adds it), and the walker cannot turn on the spot while walking -- a working goal that
         jumps behind a robot can make its solve INFEASIBLE.  That ends the robot's run only in a fleet without ``recover``: with
@@ -631,6 +636,11 @@ class UnknownEnvFleet:
         plan_out = [None]                                    # the plan's buffers: made by the first plan, reused by every later one
         coordinated = isinstance(explorer, CoordinatedFrontierPlanner)
         n_claims = torch.zeros((rows,), dtype=torch.int32, device=dev) if coordinated else None
+        keeping = coordinated and explorer.r_keep is not None
+        if keeping:
+            # the fleet's memory: every robot's target of the last replan (-1: none), and what it did to the claims
+            prev = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            n_kept, n_jumps = (torch.zeros((rows,), dtype=torch.int32, device=dev) for _ in range(2))
         info = dict(n_replans=0)
 
         def replan(k, pl, closing=False):
@@ -644,7 +654,10 @@ class UnknownEnvFleet:
             pos = fl["state"][:, (0, 2)].contiguous()
             solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
             claim = dict(may_claim=solved.to(torch.int8)) if coordinated else {}
-            plan = plan_out[0] = explorer.plan(mapper, pos, S_max=64 if S_max is None else S_max, out=plan_out[0], **claim)
+            if keeping:
+                claim["prev_target"] = prev
+            plan = plan_out[0] = (explorer.replan if keeping else explorer.plan)(mapper, pos, S_max=64 if S_max is None else S_max,
+                                                                                out=plan_out[0], **claim)
             found = plan["status"] == RRT_FOUND
             if not closing:
                 resume = (fl["walking"] == 0) & solved & found
@@ -656,6 +669,14 @@ class UnknownEnvFleet:
                 known_free[info["n_replans"]].copy_((ev <= -t_free).sum((1, 2)))
                 if coordinated:
                     n_claims[info["n_replans"]].copy_(plan["n_claims"][0])
+                if keeping:
+                    tc, H = plan["target_cell"], ev.shape[2]
+                    di = torch.div(tc, H, rounding_mode="floor") - torch.div(prev, H, rounding_mode="floor")
+                    dj = torch.remainder(tc, H) - torch.remainder(prev, H)
+                    jumped = found & (prev >= 0) & (di * di + dj * dj > explorer.r_keep ** 2)
+                    n_jumps[info["n_replans"]].copy_(jumped.sum())
+                    n_kept[info["n_replans"]].copy_(plan["n_kept"][0])
+                    prev.copy_(torch.where(found, tc, torch.full_like(tc, -1)))
                 info["n_replans"] += 1
             fl["walking"].masked_fill_(~found, 0)
             info["explore_status"] = plan["status"]
@@ -668,6 +689,8 @@ class UnknownEnvFleet:
                    done=(fl["walking"] == 0) & solved & (info["explore_status"] == RRT_NO_PATH))
         if coordinated:
             res["n_claims"] = n_claims
+        if keeping:
+            res.update(n_kept=n_kept, n_jumps=n_jumps)
         return res
 
 

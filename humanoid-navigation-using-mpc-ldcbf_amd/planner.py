@@ -145,6 +145,11 @@ def assign_outputs(B, W, H, S_max):
                 work=(torch.uint32, (W, H), True))
 
 
+def assign_keep_outputs(B, W, H, S_max):
+    """Outputs of a CoordinatedFrontierPlanner with ``r_keep``: ``assign_outputs`` plus who kept the last target and how many."""
+    return dict(assign_outputs(B, W, H, S_max), kept=(torch.int8, (B,), True), n_kept=(torch.int32, (1,), True))
+
+
 def informed_outputs(B, F, W, H, S_max):
     """Outputs of InformedFrontierPlanner.plan, in the order it returns them: FrontierPlanner.plan's (field, frontier and n_frontier
     stay the nearest-frontier ones), then the gain, the utility field, its source count and the gain of every robot's target."""
@@ -573,16 +578,42 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     rounds (0..4096).  Everything is an integer comparison: two calls give identical bits.
     The model's limits: a round is sequential by nature -- one relaxation of the whole map per claim, in one workgroup; robots
     that are left when the frontier or ``max_claims`` is used up are FOLLOWERS, who keep their plain nearest-frontier plan and so
-    share a target; there is no memory between plans, so a replan may hand a robot another target than the last one."""
+    share a target; ``plan`` has no memory, so a replan may hand a robot another target than the last one.
+    CLAIM HYSTERESIS (keywords ``r_keep`` 0..64, ``keep_ratio16`` 16..1024, ``keep_slack`` 0..4096; all three or none, no
+    defaults: nobody has measured one; ``lipmpc_grid_frontier_assign_keep_batch``): ``replan(..., prev_target=)`` runs a keep
+    phase ahead of the rounds.  A robot keeps what is left of its last target -- the nearest frontier cell within ``r_keep``
+    cells of it -- when that cell is reachable and its cost is at most ``keep_ratio16`` / 16 times the cost to the robot's
+    nearest frontier plus ``keep_slack`` cells; a keeper takes its disc like a winner, and keep attempts and rounds share the
+    ``max_claims`` relaxations.  Without ``r_keep`` the very calls of before are made.  What remains: the keep test compares with
+    the NEAREST frontier, not with what the rounds would have handed the robot; followers have no memory; the informed planners
+    have none either."""
 
     _TILED, _TILED_WHY, _TILED_CLASS = False, "the claim rounds keep", "TiledCoordinatedFrontierPlanner"
     _FRESH = ("field", "frontier", "n_frontier", "work")            # outputs written whole: a fresh dict gets them uninitialised
     _table = staticmethod(assign_outputs)
+    _keep_table = staticmethod(assign_keep_outputs)                 # the table of a planner with ``r_keep``
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
         self.r_claim, self.max_claims = int(r_claim), int(max_claims)
         if not 0 <= self.r_claim <= 4096 or not 0 <= self.max_claims <= 4096:
             raise ValueError(f"invalid claim parameters (r_claim {r_claim}: 0..4096, max_claims {max_claims}: 0..4096)")
+        # the keep parameters: keywords, taken off before the parent sees them (the signature stays what it was)
+        keep = [frontier_planner_kwargs.pop(k, None) for k in ("r_keep", "keep_ratio16", "keep_slack")]
+        misspelt = sorted(k for k in frontier_planner_kwargs if "keep" in k)
+        if misspelt:
+            raise TypeError(f"unexpected keyword {misspelt}: the keep parameters are r_keep, keep_ratio16 and keep_slack")
+        if keep[0] is None:
+            if keep[1] is not None or keep[2] is not None:
+                raise ValueError("keep_ratio16 / keep_slack without r_keep: the keep phase is switched on by r_keep")
+            self.r_keep = self.keep_ratio16 = self.keep_slack = None
+        else:
+            if keep[1] is None or keep[2] is None:
+                raise ValueError("r_keep needs keep_ratio16 and keep_slack: they have no defaults, nobody has measured one")
+            self.r_keep, self.keep_ratio16, self.keep_slack = (int(v) for v in keep)
+            if not 0 <= self.r_keep <= 64 or not 16 <= self.keep_ratio16 <= 1024 or not 0 <= self.keep_slack <= 4096:
+                raise ValueError(f"invalid keep parameters (r_keep {keep[0]}: 0..64, keep_ratio16 {keep[1]}: 16..1024, "
+                                 f"keep_slack {keep[2]}: 0..4096)")
+            self._table = self._keep_table
         super().__init__(**frontier_planner_kwargs)
 
     def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None):
@@ -590,7 +621,20 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         integers, None = everybody): the robots that may claim; the others keep their nearest-frontier plan and take nothing
         from anybody.  Returns the parent's dict -- a robot that claimed has the sub_goals, n_sub, status, path_cost, target_cell
         and target of its path to the cell it claimed -- plus claim_round [B] (the round a robot won, -1 for everyone else),
-        n_claims [1] and ``work`` [W,H] (the call's scratch).  ``out``: that dict, to write into."""
+        n_claims [1] and ``work`` [W,H] (the call's scratch).  ``out``: that dict, to write into.
+        With ``r_keep`` set this is ``replan`` with no previous targets."""
+        return self._plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, None)
+
+    def replan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None, prev_target=None):
+        """``plan`` with memory (a planner with ``r_keep``; any other: ValueError).  ``prev_target`` [B] integers: per robot the
+        ``target_cell`` of the last plan on this same grid, anything outside 0..W*H-1 (-1, say) = none; None = nobody has one.  A
+        robot keeps what is left of that target by the keep rule ahead of the claim rounds.  Returns ``plan``'s dict plus kept [B]
+        int8 (1 = the robot kept its target; its claim_round counts like a winner's) and n_kept [1]."""
+        if self.r_keep is None:
+            raise ValueError("replan needs a planner with r_keep, keep_ratio16 and keep_slack")
+        return self._plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target)
+
+    def _plan(self, mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target):
         ev = self._map(mapper_or_evidence, origin, cell)[0]
         if ev.shape[0] != 1:
             raise ValueError(f"{ev.shape[0]} maps: the robots claim on ONE shared map")
@@ -603,22 +647,53 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
             if tuple(may_claim.shape) != (B,):
                 raise ValueError("may_claim must be [B]")
             may_claim = (may_claim != 0).to(torch.int8)
+        if self.r_keep is not None:
+            if prev_target is None:
+                if self._none is None or self._none.shape[0] < B:               # (made once: nothing is allocated in a capture
+                    if torch.cuda.is_current_stream_capturing():                #  that follows a call of this size)
+                        raise RuntimeError("the planner's 'no previous target' row must grow: run the call once before the capture")
+                    self._none = torch.full((max(B, 1),), -1, dtype=torch.int32, device=self.device)
+                prev_target = self._none[:B]
+            else:
+                prev_target = torch.as_tensor(prev_target)
+                if tuple(prev_target.shape) != (B,) or prev_target.dtype.is_floating_point or prev_target.dtype == torch.bool:
+                    raise ValueError("prev_target must be [B] integers")
+                prev_target = prev_target.to(device=self.device)
+                if prev_target.dtype != torch.int32:                            # whatever is no cell of an int32 grid is "none"
+                    prev_target = torch.where((prev_target >= 0) & (prev_target < W * H), prev_target, -1).to(torch.int32)
+                prev_target = prev_target.contiguous()
         table = self._table(B, W, H, S_max)
         if out is None:
             out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost", "target", "target_cell"), self.device, torch.zeros)
             out.update(_alloc(table, self._FRESH, self.device))
             out.update(claim_round=torch.full((B,), -1, dtype=torch.int32, device=self.device),
                        n_claims=torch.zeros((1,), dtype=torch.int32, device=self.device))
+            if self.r_keep is not None:
+                out.update(_alloc(table, ("kept", "n_kept"), self.device, torch.zeros))
         else:
             _check_table(table, out, self.device, "out")
         super().plan(mapper_or_evidence, start, origin, cell, S_max, out)      # (its table is part of this one)
         if B == 0:
             return out
         origin, cell, org_c, cell_c = self._placement(*self._map(mapper_or_evidence, origin, cell)[3:])
-        self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out)
+        if self.r_keep is None:
+            self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out)
+        else:
+            self._keep_claims(B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out)
         self._target(out, origin, cell, H)
         self.last = out
         return out
+
+    _none = None                # [>= B] int32 of -1: the prev_target of a plan without one
+
+    def _keep_claims(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out):
+        _lib.call("lipmpc_grid_frontier_assign_keep_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
+                  cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], start=start, may_claim=may_claim,
+                  prev_target=prev_target, r_inflate=self.r_inflate, r_claim=self.r_claim, r_keep=self.r_keep,
+                  keep_ratio16=self.keep_ratio16, keep_slack=self.keep_slack, max_claims=self.max_claims, max_seg=self.max_seg,
+                  S_max=S_max, work=out["work"],
+                  **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims", "kept", "n_kept")),
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
     def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
         _lib.call("lipmpc_grid_frontier_assign_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
@@ -634,6 +709,11 @@ def tiled_assign_outputs(B, W, H, S_max):
     table = assign_outputs(B, W, H, S_max)
     del table["work"]
     return dict(table, claims_settled=(torch.int32, (1,), False))
+
+
+def tiled_assign_keep_outputs(B, W, H, S_max):
+    """Outputs of a TiledCoordinatedFrontierPlanner with ``r_keep``: ``tiled_assign_outputs`` plus kept and n_kept."""
+    return dict(tiled_assign_outputs(B, W, H, S_max), kept=(torch.int8, (B,), True), n_kept=(torch.int32, (1,), True))
 
 
 CLAIM_MAX_LAUNCHES = 1 << 20    # max_claims * max_rounds of one lipmpc_grid_frontier_assign_tiled_batch
@@ -661,10 +741,14 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
     ``max_claims``) -- at that cap the dict is returned with ``claims_settled`` 0.
     The cost is fixed by the budget, not by what the fleet needs: ``max_claims`` * (budget + 4) + 3 launches per claim call.  On
     small maps the one-workgroup parent is faster; it stays the default.  The limits that remain: the claim rounds are sequential
-    and not gain-seeded, and there is no memory between plans."""
+    and not gain-seeded; ``plan`` has no memory between plans.
+    CLAIM HYSTERESIS: ``r_keep``, ``keep_ratio16``, ``keep_slack`` and ``replan(..., prev_target=)`` as the parent's, by
+    ``lipmpc_grid_frontier_assign_keep_tiled_batch``: the dict gains kept [B] and n_kept [1], ``rounds`` is the budget of every
+    SLOT (keep attempt or claim round), and a claim call costs ``max_claims`` * (budget + 5) + 3 launches."""
 
     _FRESH = ("field", "frontier", "n_frontier")
     _table = staticmethod(tiled_assign_outputs)
+    _keep_table = staticmethod(tiled_assign_keep_outputs)
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
         if self.rounds is not None and int(max_claims) * self.rounds > CLAIM_MAX_LAUNCHES:
@@ -678,20 +762,34 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
         self._settled(out, 1, "claims_settled")            # (B = 0: no call was made)
         return out
 
-    def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
+    def replan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None, prev_target=None):
+        """``CoordinatedFrontierPlanner.replan`` by the tiled calls: its dict without ``work``, plus ``settled`` and ``claims_settled`` [1]."""
+        out = super().replan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target)
+        self._settled(out, 1, "claims_settled")            # (B = 0: no call was made)
+        return out
+
+    def _keep_claims(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out):
+        self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target)
+
+    def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target=None):
         capturing = torch.cuda.is_current_stream_capturing()
         if self.rounds is None and capturing:
             raise RuntimeError("rounds=None reads `claims_settled` on the host: give the planner a fixed `rounds` to capture its calls")
-        work = self._workspace(self._claim_works, int(self.lib.lipmpc_grid_frontier_assign_tiled_workspace_bytes(W, H)),
-                               "lipmpc_grid_frontier_assign_tiled_workspace_bytes")
+        name, keep = "lipmpc_grid_frontier_assign_tiled_batch", {}
+        if prev_target is not None:
+            name = "lipmpc_grid_frontier_assign_keep_tiled_batch"
+            keep = dict(prev_target=prev_target, r_keep=self.r_keep, keep_ratio16=self.keep_ratio16, keep_slack=self.keep_slack,
+                        kept=out["kept"], n_kept=out["n_kept"])
+        size = name.replace("_batch", "_workspace_bytes")
+        work = self._workspace(self._claim_works, int(getattr(self.lib, size)(W, H)), size)
         done = self._settled(out, 1, "claims_settled")
         stream = torch.cuda.current_stream(self.device).cuda_stream
 
         def call(budget):
-            _lib.call("lipmpc_grid_frontier_assign_tiled_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
+            _lib.call(name, device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
                       cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], settled=out["settled"], start=start,
                       may_claim=may_claim, r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims,
-                      max_seg=self.max_seg, S_max=S_max, work=work, work_bytes=work.numel(), max_rounds=budget,
+                      max_seg=self.max_seg, S_max=S_max, work=work, work_bytes=work.numel(), max_rounds=budget, **keep,
                       **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
                       claims_settled=done, hip_stream=stream)
         if self.rounds is not None:

@@ -799,6 +799,55 @@ int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t W, int32_t 
                                       uint32_t* work, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                       int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, void* hip_stream);
 
+/* lipmpc_grid_frontier_assign_keep_batch (backward-compatible addition): CLAIM HYSTERESIS.  lipmpc_grid_frontier_assign_batch
+ * with a KEEP PHASE ahead of its greedy rounds: a robot that had a target at the last replan keeps what is left of it while it
+ * is still a source, still reachable and not much farther than the robot's nearest frontier.  One workgroup does the whole call.
+ * The arguments, S, U, passability and the path rule are lipmpc_grid_frontier_assign_batch's, plus:
+ *  prev_target [B] int32: a cell index i * H + j of this same W x H grid; a value outside 0..W*H-1 means "none"
+ *  r_keep 0..64, in cells;  keep_ratio16 16..1024, in sixteenths;  keep_slack 0..4096, in cells
+ *  kept [B] int8, n_kept [1] int32: written whole
+ * THE RULE:
+ *  - a SLOT is one relaxation of the whole map.  A call makes at most max_claims slots, keep attempts and greedy rounds counted
+ *    together.  k counts the slots that had a winner: claim_round still runs 0, 1, ... in the order won, and n_claims is the
+ *    number of winners, the kept ones included.
+ *  - keep phase: the robots b of U_0 whose start lies on the grid and whose prev_target is a cell, in ascending index, while
+ *    slots are left:
+ *      ANCHOR a_b = the cell of the current S within (i - i_p)^2 + (j - j_p)^2 <= r_keep^2 of the previous target p with the
+ *        least (d^2, cell index).  None: b is skipped and no slot is spent.  (The frontier recedes as the robot approaches:
+ *        r_keep is how far it may recede and still be the same target.)
+ *      one slot is spent.  keepfield = the least cost to {a_b} alone: the same relaxation, costs, no-corner-cut rule and
+ *        passability as a greedy round's field.
+ *      ENTRY s_b = the start cell if keepfield is finite there, else the snap in keepfield, as in a greedy round.  None: b is
+ *        not kept and stays in U.
+ *      near_b = the given field at the robot's entry into the GIVEN field (its start cell if finite there, else the snap
+ *        there; none: b is not kept).  b keeps its target iff, in 64 bits,
+ *            16 * keepfield[s_b] <= keep_ratio16 * near_b + 80 * keep_slack
+ *        (costs are in fifths of a cell).  Otherwise b stays in U for the greedy rounds.
+ *      on success the rows are written by the winner's path rule on keepfield (PATH_OVERFLOW included), target_cell = a_b,
+ *        claim_round[b] = k, kept[b] = 1; S loses the r_claim disc round a_b and U loses b.
+ *  - greedy phase: lipmpc_grid_frontier_assign_batch's rounds on what is left of S, U and the slots.
+ *  - every other robot gets kept[b] = 0.  n_kept[0] = the number of kept robots.
+ *  Hence: with every prev_target "none" all outputs but kept / n_kept equal lipmpc_grid_frontier_assign_batch's bit for bit;
+ *  the targets of two winners, kept or claimed, are more than r_claim apart (an anchor is taken from the current S);
+ *  keep_ratio16 = 16 with keep_slack = 0 keeps only a target that is as near as the nearest frontier; a failed keep attempt
+ *  changes nothing but that it spends a slot; two calls give identical bits.  The test compares with the NEAREST frontier, not
+ *  with what the greedy rounds would have handed the robot.
+ *  COST: one relaxation per slot, and per keep candidate a search of the clipped (2 r_keep + 1)^2 window.  The slot's field is
+ *  kept in LDS when 4 (2 (2 ceil(W H / 64) + 2) + 34 + W H) + 256 <= 163840 (34 words: the 22 of the assign kernels, three
+ *  more pointers, four scalars and the entry cell for the lane that walks, the count of U); a larger map is relaxed in `work`.
+ * Restated in numpy by tests/assign_keep_oracle.py; the device's outputs equal it bit for bit.
+ * All pointers DEVICE pointers but origin / cell (HOST); asynchronous on hip_stream; no allocation and no host synchronisation,
+ * so the call can be captured in a graph; every refusal is decided on the host before anything is enqueued.
+ * LIPMPC_E_ARG: what lipmpc_grid_frontier_assign_batch refuses as such, r_keep outside 0..64, keep_ratio16 outside 16..1024,
+ *  keep_slack outside 0..4096, a null prev_target, kept or n_kept.  Then LIPMPC_E_UNSUPPORTED and B = 0 as there. */
+int lipmpc_grid_frontier_assign_keep_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                           const uint8_t* frontier, const uint32_t* field, const double* start,
+                                           const int8_t* may_claim, const int32_t* prev_target, int32_t r_inflate, int32_t r_claim,
+                                           int32_t r_keep, int32_t keep_ratio16, int32_t keep_slack, int32_t max_claims,
+                                           int32_t max_seg, int32_t S_max, uint32_t* work, double* sub_goals, int32_t* n_sub,
+                                           int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                           int32_t* n_claims, int8_t* kept, int32_t* n_kept, void* hip_stream);
+
 /* INFORMED EXPLORER (backward-compatible addition): send explorers where they will see most.  The frontier path call sends a
  * robot to its NEAREST frontier cell, whatever that cell would reveal: a cell behind a wall stub is worth as much as one that
  * faces an open unknown half-plane.  These three calls add the expected-visibility utility of frontier exploration (Gonzalez-
@@ -1063,6 +1112,38 @@ int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, int32_t W, in
                                             int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes, int32_t max_rounds,
                                             double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
                                             int32_t* claim_round, int32_t* n_claims, int32_t* claims_settled, void* hip_stream);
+
+/* lipmpc_grid_frontier_assign_keep_tiled_batch (backward-compatible addition): CLAIM HYSTERESIS on large maps --
+ * lipmpc_grid_frontier_assign_keep_batch's rule, word for word, with every slot's field relaxed by tiled rounds.
+ *  The arguments of lipmpc_grid_frontier_assign_tiled_batch plus prev_target, r_keep, keep_ratio16, keep_slack, kept and n_kept
+ *  as lipmpc_grid_frontier_assign_keep_batch takes them.  work: at least
+ *  lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes(W, H) bytes, 8-byte aligned: the tiled claim call's layout with eight
+ *  more control words (the slot's mode, robot and anchor, the keep cursor, the keep count).
+ *  The host enqueues a fixed sequence: the two set-up kernels, then for every slot 0 .. max_claims - 1 the MODE kernel (one
+ *  workgroup: from the cursor on, the next robot of U with a previous target whose anchor exists in what is left of the sources --
+ *  candidates without one are passed over and spend nothing; none left: this and every later slot is a greedy round), the seed
+ *  (a keep slot seeds the anchor alone), max_rounds rounds and the settle kernel, the pick (a keep slot considers its robot
+ *  alone) and the take (a keeper has to pass the test; on success its rows, kept, the disc; a keep slot without an entry cell or
+ *  with a failed test ends without a winner and the call goes on), then the last kernel.  k is a control word that counts the
+ *  winners: the host's slot index is not the claim index.  A slot whose field does not settle within max_rounds stops the call.
+ *  THE COST, whatever the fleet needs: max_claims * (max_rounds + 5) + 3 launches; max_claims * max_rounds <= 2^20 as before.
+ *  - claims_settled[0] == 1: every output equals lipmpc_grid_frontier_assign_keep_batch's, bit for bit.
+ *  - claims_settled[0] == 0: settled[0] == 0 (then n_claims = n_kept = 0) or some slot's field did not settle: the keeps and
+ *    claims made so far are exactly the rule's first n_claims winners, and everyone else keeps the nearest-frontier plan.  A
+ *    repeat of the whole call with a larger budget reproduces them and goes on (what
+ *    lipmpc_grid_frontier_assign_tiled_batch says about rows applies).
+ *  LIPMPC_E_ARG: what lipmpc_grid_frontier_assign_tiled_batch and lipmpc_grid_frontier_assign_keep_batch refuse as such.
+ * lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes: as lipmpc_grid_frontier_assign_tiled_workspace_bytes. */
+int64_t lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes(int32_t W, int32_t H);
+int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                                 const uint8_t* frontier, const uint32_t* field, const int32_t* settled,
+                                                 const double* start, const int8_t* may_claim, const int32_t* prev_target,
+                                                 int32_t r_inflate, int32_t r_claim, int32_t r_keep, int32_t keep_ratio16,
+                                                 int32_t keep_slack, int32_t max_claims, int32_t max_seg, int32_t S_max, void* work,
+                                                 int64_t work_bytes, int32_t max_rounds, double* sub_goals, int32_t* n_sub,
+                                                 int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                                 int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled,
+                                                 void* hip_stream);
 
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
