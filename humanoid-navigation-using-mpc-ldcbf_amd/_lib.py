@@ -122,6 +122,19 @@ SIGNATURES = {
     "lipmpc_grid_frontier_path_tiled_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell evidence t_occ:i32 field "
                                                            "n_frontier settled start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub "
                                                            "status path_cost target_cell hip_stream"),
+    "lipmpc_grid_clearance_cost_batch": _sig(C.c_int, "device:int M:i64 W:i32 H:i32 occ evidence t_occ:i32 r_clear:i32 w_clear:i32 cost "
+                                                      "hip_stream"),
+    "lipmpc_grid_field_weighted_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 grid_shared:i32 origin cell occ cost goal r_inflate:i32 "
+                                                      "field field_status work work_bytes:i64 max_rounds:i32 resume:i32 settled hip_stream"),
+    "lipmpc_grid_frontier_field_weighted_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 evidence cost t_free:i32 t_occ:i32 "
+                                                               "r_inflate:i32 min_unknown:i32 frontier field n_frontier work "
+                                                               "work_bytes:i64 max_rounds:i32 resume:i32 settled hip_stream"),
+    "lipmpc_grid_path_weighted_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell occ grid_shared:i32 cost field "
+                                                     "field_status settled goal start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub "
+                                                     "status path_cost hip_stream"),
+    "lipmpc_grid_frontier_path_weighted_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell evidence cost t_occ:i32 field "
+                                                              "n_frontier settled start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals "
+                                                              "n_sub status path_cost target_cell hip_stream"),
     "lipmpc_grid_frontier_gain_tiled_lds_bytes": _sig(C.c_int64, "r_view:i32"),
     "lipmpc_grid_frontier_gain_tiled_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 evidence t_free:i32 t_occ:i32 frontier r_view:i32 "
                                                            "gain hip_stream"),

@@ -27,6 +27,10 @@
 //   tile_gain_kernel              one workgroup per (map, tile): the fan against bitmaps of the tile grown by r_view.
 //   tile_utility_*_kernel         the utility field's seeds for the rounds above; the path kernel with one more rule in front.
 //   claim_*_kernel                frontier_assign_*_kernel's rounds cut into kernels, each round's field relaxed by the rounds above.
+// and soft clearance (lipmpc_grid_clearance_cost_batch, lipmpc_grid_field_weighted_batch, lipmpc_grid_frontier_field_weighted_batch
+// and their path calls), at the very end:
+//   soft_cost_kernel              one workgroup per (map, tile): a byte per cell that decays with the distance to the nearest solid cell.
+//   soft_round_kernel             the tiled round with that byte added to what a cell takes; soft_*_descent_kernel walk down such a field.
 // Everything the kernels compare is an integer but the two floors that name a cell; the cell centres are one multiply and
 // one add, contraction off.  tests/field_oracle.py restates both contracts (Dijkstra) and the GPU tests hold every output to it
 // bit for bit.
@@ -2672,5 +2676,454 @@ extern "C" int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t 
                        path_cost, target_cell, claim_round, kept);
   }
   hipLaunchKernelGGL(keep_finish_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, w, claim_round, n_claims, n_kept, claims_settled);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+// =====================================================================================================================
+// SOFT CLEARANCE (lipmpc_grid_clearance_cost_batch, lipmpc_grid_field_weighted_batch, lipmpc_grid_frontier_field_weighted_batch and
+// their path calls): a byte per cell that a path pays when it LEAVES the cell, on top of the step.  The cost layer decays with the
+// distance to the nearest solid cell; the weighted fields are the tiled fields above with that byte added in the sweep, relaxed by
+// the same rounds -- set-up, seeds, flags and the settle kernel are the tiled calls' own, only the round kernel is new.
+//
+// WHY THE WEIGHTED ROUNDS GIVE WEIGHTED DIJKSTRA'S FIELD.  The argument of THE TILED FIELD carries over word for word; the cell
+// cost enters in ONE place: a value a cell takes is  k(c) + f(n) + step  for a legal move c -> n, which is the cost of the real
+// path "leave c, then n's path" in the metric where leaving c costs k(c) more.  Values are still path costs and still only fall,
+// so no flag set <=> a fixed point of  f(c) = k(c) + min over legal moves of f(n) + step,  f = 0 on the sources; its finite values
+// are >= the least cost (they are path costs) and <= it (induction along a least-cost path); k >= 0 is an integer, so the least
+// cost is unique and the bits are Dijkstra's.  The round guarantee's induction uses "the rest of a least-cost path is a least-cost
+// path" and "a tile relaxes to its local fixed point", both of which hold in the weighted metric.
+// NO WRAP: a stored value is the cost of a SIMPLE path (a value derived through the cell itself would be larger than the one it
+// holds), at most 2^24 - 1 moves of at most 7 + 248 each; a candidate adds one more: <= 255 * 2^24 < 2^32 - 1 = INF.
+namespace {
+
+constexpr int R_CLEAR_MAX = 31;                       // a disc row is at most 63 consecutive bits: one 64-bit window
+constexpr int SOFT_ROWS = TILE_W + 2 * R_CLEAR_MAX;   // 94 rows of 128 bits: the tile grown by r_clear
+static_assert(LIPMPC_COST_MAX == 248 && (7 + LIPMPC_COST_MAX) * (uint64_t)TILED_MAX_CELLS < INF, "a finite weighted value stays below INF");
+
+__device__ inline uint32_t soft_k(const uint8_t* __restrict__ cost, int c) { return min((uint32_t)cost[c], (uint32_t)LIPMPC_COST_MAX); }
+
+// THE COST LAYER.  blockIdx.x = map * tiles + tile; a thread owns the round kernel's eight cells.  The solid bits of the tile grown
+// by r_clear go into LDS by ballot (row rr = i - (i0 - r), bit b = j - (j0 - r); a cell outside the grid is not solid); per cell
+// and row the nearest set bit left and right of the centre of the 2 r + 1 bit window, rows by increasing |di| until di^2 >= the
+// best d2.  KIND 0: occ bytes; KIND 1: evidence >= t_occ.
+template <int KIND>
+__global__ void __launch_bounds__(TILE_THREADS) soft_cost_kernel(int W, int H, int tiles_j, int tiles, const uint8_t* __restrict__ occ,
+                                                                 const int32_t* __restrict__ evidence, int t_occ, int r, int w_clear,
+                                                                 uint8_t* __restrict__ cost) {
+  __shared__ uint64_t bm[SOFT_ROWS * 2];
+  const int64_t m = blockIdx.x / tiles;
+  const int tile = blockIdx.x - (int)m * tiles, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  const int64_t base = m * (int64_t)W * H;
+  const int rows = TILE_W + 2 * r;
+  int any = 0;
+  for (int h = wave; h < 2 * rows; h += TILE_THREADS / 64) {          // (h is uniform in a wave: every lane takes part in the ballot)
+    const int gi = i0 - r + (h >> 1), gj = j0 - r + (h & 1) * 64 + lane;
+    bool solid = false;
+    if ((unsigned)gi < (unsigned)W && (unsigned)gj < (unsigned)H) {
+      const int64_t g = base + (int64_t)gi * H + gj;
+      solid = KIND == 0 ? occ[g] != 0 : evidence[g] >= t_occ;
+    }
+    const uint64_t mb = __ballot(solid);
+    if (lane == 0) bm[h] = mb;
+    any |= mb != 0;
+  }
+  any = __syncthreads_or(any);
+  const int r2 = r * r, lj = lane, gj = j0 + lj;
+  const uint64_t mask = (2ull << (2 * r)) - 1, left = (1ull << r) - 1;          // 2 r + 1 <= 63 bits; the r bits below the centre
+#pragma unroll 1
+  for (int k = 0; k < TILE_OWN; ++k) {
+    const int li = k * TILE_ROWS + wave, gi = i0 + li;
+    if (gi >= W || gj >= H) continue;
+    int best = r2 + 1;
+    if (any) {
+#pragma unroll 1
+      for (int a = 0; a <= r && a * a < best; ++a) {
+#pragma unroll 1
+        for (int sgn = 0; sgn < (a ? 2 : 1); ++sgn) {
+          const uint64_t* row = bm + 2 * (li + r + (sgn ? -a : a));
+          const uint64_t win = ((row[0] >> lj) | (lj ? row[1] << (64 - lj) : 0ull)) & mask;     // bit t = column gj - r + t
+          const uint64_t hi = win >> r, lo = win & left;
+          if (hi) { const int d = __builtin_ctzll(hi); best = min(best, a * a + d * d); }
+          if (lo) { const int d = r - (63 - __builtin_clzll(lo)); best = min(best, a * a + d * d); }
+        }
+      }
+    }
+    cost[base + (int64_t)gi * H + gj] = best <= r2 ? (uint8_t)((uint32_t)(w_clear * (r2 - best)) / (uint32_t)r2) : (uint8_t)0;
+  }
+}
+
+// ONE WEIGHTED ROUND: tiled_round_kernel with the eight cost bytes of a thread's cells in one more register, added to what a cell
+// takes.  blockIdx.x = field * tiles + tile.  A source holds 0 and never falls, so it pays nothing.
+__global__ void __launch_bounds__(TILE_THREADS) soft_round_kernel(int W, int H, int tiles_j, int tiles, int64_t blk_stride,
+                                                                  const uint32_t* __restrict__ blk, int64_t cost_stride,
+                                                                  const uint8_t* __restrict__ cost, uint32_t* field, uint32_t* cur,
+                                                                  uint32_t* next) {
+  __shared__ uint32_t lf[HALO_CELLS];                 // field words, local index l = (li + 1) * HALO_H + lj + 1
+  __shared__ uint32_t lb[HALO_PADDED / 32 + 2];       // blocked bits by l; a cell outside the grid is blocked
+  __shared__ uint32_t rim;
+  const int64_t f = blockIdx.x / tiles;
+  const int tile = blockIdx.x - (int)f * tiles, tid = threadIdx.x, lane = tid & 63;
+  uint32_t* my_flag = cur + f * tiles + tile;
+  if (ld_agent(my_flag) == 0) return;                 // (one word for the whole workgroup: uniform)
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  const uint32_t* bl = blk + f * blk_stride;
+  const uint8_t* kc = cost + f * cost_stride;
+  uint32_t* fld = field + f * (int64_t)W * H;
+
+  for (int l0 = tid - lane; l0 < HALO_PADDED; l0 += TILE_THREADS) {
+    const int l = l0 + lane, li = l / HALO_H, lj = l - li * HALO_H;
+    const int gi = i0 + li - 1, gj = j0 + lj - 1;
+    const bool in = l < HALO_CELLS && (unsigned)gi < (unsigned)W && (unsigned)gj < (unsigned)H;
+    const int gc = in ? gi * H + gj : 0;
+    const uint32_t v = ld_agent(fld + gc);
+    const uint64_t mb = __ballot(!in || bit_of(bl, gc));
+    if (l < HALO_CELLS) lf[l] = in ? v : INF;
+    if (lane == 0) { lb[l0 >> 5] = (uint32_t)mb; lb[(l0 >> 5) + 1] = (uint32_t)(mb >> 32); }
+  }
+  if (tid == 0) rim = 0;
+  __syncthreads();                                    // (everybody has read the flag: it is cleared for the round after next)
+  if (tid == 0) st_agent(my_flag, 0u);
+
+  // the legal moves of my eight cells, a byte per cell (tiled_round_kernel's), and beside them their eight cost bytes, clamped
+  const int l_first = ((tid >> 6) + 1) * HALO_H + (tid & 63) + 1;
+  auto open_at = [&](int l) { return ((lb[l >> 5] >> (l & 31)) & 1u) ^ 1u; };       // 1 = unblocked
+  uint64_t moves = 0, costs = 0;
+#pragma unroll 1
+  for (int k = 0; k < TILE_OWN; ++k) {
+    const int l = l_first + k * TILE_ROWS * HALO_H;
+    const uint32_t up = open_at(l - HALO_H), dn = open_at(l + HALO_H), lt = open_at(l - 1), rt = open_at(l + 1);
+    const uint32_t m = (open_at(l - HALO_H - 1) & up & lt) | up << 1 | (open_at(l - HALO_H + 1) & up & rt) << 2 | lt << 3 | rt << 4 |
+                       (open_at(l + HALO_H - 1) & dn & lt) << 5 | dn << 6 | (open_at(l + HALO_H + 1) & dn & rt) << 7;
+    const uint32_t mine = m * open_at(l);
+    moves |= (uint64_t)mine << (8 * k);
+    const int gi = i0 + k * TILE_ROWS + (tid >> 6), gj = j0 + (tid & 63);            // (an unblocked cell is inside the grid)
+    if (mine) costs |= (uint64_t)soft_k(kc, gi * H + gj) << (8 * k);
+  }
+
+  // the sweeps of relax(), on my cells, the halo held
+  uint32_t fell = 0;
+  for (;;) {
+    int changed = 0;
+#pragma unroll 1
+    for (int k = 0; k < TILE_OWN; ++k) {                // (not unrolled: eight cells' lane masks at once overfill the scalar file)
+      const uint32_t m = (uint32_t)(moves >> (8 * k)) & 0xFFu;
+      if (m) {
+        const int l = l_first + k * TILE_ROWS * HALO_H;
+        auto via = [&](int bit, int off, uint32_t step) {
+          const uint32_t v = ld(lf + l + off);
+          return ((m >> bit) & 1u) && v != INF ? v + step : INF;
+        };
+        const uint32_t cur_v = ld(lf + l);
+        const uint32_t least = min(min(min(via(0, -HALO_H - 1, DIAGONAL), via(1, -HALO_H, AXIAL)), min(via(2, -HALO_H + 1, DIAGONAL), via(3, -1, AXIAL))),
+                                   min(min(via(4, 1, AXIAL), via(5, HALO_H - 1, DIAGONAL)), min(via(6, HALO_H, AXIAL), via(7, HALO_H + 1, DIAGONAL))));
+        const uint32_t best = least == INF ? INF : least + ((uint32_t)(costs >> (8 * k)) & 0xFFu);      // THE CELL COST ENTERS HERE
+        if (best < cur_v) { st(lf + l, best); changed = 1; fell |= 1u << k; }
+      }
+    }
+    if (!__syncthreads_or(changed)) break;
+  }
+
+  // write back what fell; which parts of the rim fell: bit 0 top, 1 bottom, 2 left, 3 right, 4..7 the corners
+  uint32_t r = 0;
+  const int lj = tid & 63;
+#pragma unroll
+  for (int k = 0; k < TILE_OWN; ++k)
+    if ((fell >> k) & 1u) {
+      const int li = k * TILE_ROWS + (tid >> 6);
+      st_agent(fld + (i0 + li) * H + j0 + lj, lf[l_first + k * TILE_ROWS * HALO_H]);
+      const bool top = li == 0, bot = li == TILE_W - 1, lft = lj == 0, rgt = lj == TILE_H - 1;
+      r |= (uint32_t)top | (uint32_t)bot << 1 | (uint32_t)lft << 2 | (uint32_t)rgt << 3 | (uint32_t)(top & lft) << 4 |
+           (uint32_t)(top & rgt) << 5 | (uint32_t)(bot & lft) << 6 | (uint32_t)(bot & rgt) << 7;
+    }
+  if (r) atomicOr(&rim, r);
+  __syncthreads();
+  if (tid < 8 && ((rim >> tid) & 1u)) {
+    const int di = tid == 0 || tid == 4 || tid == 5 ? -1 : tid == 1 || tid == 6 || tid == 7 ? 1 : 0;
+    const int dj = tid == 2 || tid == 4 || tid == 6 ? -1 : tid == 3 || tid == 5 || tid == 7 ? 1 : 0;
+    const int ni = ti + di, nj = tj + dj;
+    if ((unsigned)ni < (unsigned)(tiles / tiles_j) && (unsigned)nj < (unsigned)tiles_j) st_agent(next + f * tiles + ni * tiles_j + nj, 1u);
+  }
+}
+
+// the weighted descent's next cell: the first neighbour in the contract's order with a legal move and
+// field[n] + step + k(c) == field[c]; -1 if none
+__device__ inline int soft_descend(const uint32_t* __restrict__ fld, const uint8_t* __restrict__ kc, int W, int H, int c) {
+  const int i = c / H, j = c - i * H;
+  const uint32_t fc = fld[c], k = soft_k(kc, c);
+  for (int di = -1; di <= 1; ++di)
+    for (int dj = -1; dj <= 1; ++dj) {
+      if ((di == 0 && dj == 0) || (unsigned)(i + di) >= (unsigned)W || (unsigned)(j + dj) >= (unsigned)H) continue;
+      const int n = c + di * H + dj;
+      const uint32_t v = fld[n];
+      if (v == INF) continue;
+      const bool diag = di != 0 && dj != 0;
+      if (diag && (fld[c + di * H] == INF || fld[c + dj] == INF)) continue;
+      if (v < fc && fc - v == (diag ? DIAGONAL : AXIAL) + k) return n;
+    }
+  return -1;
+}
+
+// los() that also sums k over the cells it visits, both ends included; false (the sum meaningless) where the sight breaks
+__device__ inline bool soft_los(const uint32_t* __restrict__ fld, const uint8_t* __restrict__ kc, int H, int a, int b, uint32_t& sum) {
+  if (b < a) { const int t = a; a = b; b = t; }
+  const int ai = a / H, aj = a - ai * H, bi = b / H, bj = b - bi * H;
+  const int di = bi - ai, dj = bj - aj;
+  const int m = max(abs(di), abs(dj)), two_m = 2 * m;
+  sum = 0;
+  if (m == 0) { sum = soft_k(kc, a); return fld[a] != INF; }
+  int qi = 0, ri = m, qj = 0, rj = m;
+  for (int k = 0; k <= m; ++k) {
+    const int c = (ai + qi) * H + aj + qj;
+    if (fld[c] == INF) return false;
+    sum += soft_k(kc, c);
+    ri += 2 * di; rj += 2 * dj;
+    if (ri >= two_m) { ri -= two_m; ++qi; } else if (ri < 0) { ri += two_m; --qi; }
+    if (rj >= two_m) { rj -= two_m; ++qj; } else if (rj < 0) { rj += two_m; --qj; }
+  }
+  return true;
+}
+
+// walk() down a weighted field.  `pen`: the sum of k over the descended cells from the anchor (inclusive) to cur (exclusive), so
+// that (fld[a] - fld[cur]) - pen is the length in steps alone, which is what max_seg caps; a sub-goal is also set where the
+// straight segment would pay more penalty than the descended path did.  With k = 0 everywhere this is walk(), test for test.
+__device__ inline int soft_walk(const uint32_t* __restrict__ fld, const uint8_t* __restrict__ kc, int W, int H, int s, int max_seg,
+                                double ox, double oy, double dx, double dy, double* sg, int& last_cell) {
+  int count = 0;
+  auto emit = [&](int c) {
+    if (sg) centre(c, H, ox, oy, dx, dy, sg + 2 * count);
+    ++count;
+  };
+  last_cell = s;
+  if (fld[s] != 0) {
+    int a = s, prev = s, cur = soft_descend(fld, kc, W, H, s);
+    uint32_t pen = soft_k(kc, s);
+    while (cur >= 0) {
+      const bool last = fld[cur] == 0;
+      uint32_t seg = 0;
+      const bool sight = soft_los(fld, kc, H, a, cur, seg);
+      if (!sight || seg - soft_k(kc, cur) > pen || (fld[a] - fld[cur]) - pen >= (uint32_t)max_seg) {
+        if (prev != a) { emit(prev); a = prev; pen = soft_k(kc, prev); continue; }          // cur is looked at again from the new anchor
+        if (last) break;
+        emit(cur); a = cur; pen = 0;
+      }
+      if (last) break;
+      prev = cur;
+      pen += soft_k(kc, cur);
+      cur = soft_descend(fld, kc, W, H, cur);
+    }
+    if (cur < 0) return -1;
+    last_cell = cur;
+  }
+  return count + 1;
+}
+
+// One lane per robot: grid_path_body's rules, the walk down the weighted field.
+__global__ void __launch_bounds__(PATH_THREADS) soft_goal_descent_kernel(int64_t B, int one_field, int W, int H, int64_t occ_stride,
+                                                                         double ox, double oy, double dx, double dy,
+                                                                         const uint8_t* __restrict__ occ, const uint8_t* __restrict__ cost,
+                                                                         const uint32_t* __restrict__ field,
+                                                                         const int32_t* __restrict__ field_status,
+                                                                         const int32_t* __restrict__ settled,
+                                                                         const double* __restrict__ goal, const double* __restrict__ start,
+                                                                         int r_inflate, int max_seg, int S_max,
+                                                                         double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+                                                                         int32_t* __restrict__ status, double* __restrict__ path_cost) {
+  const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const int64_t f = one_field ? 0 : b;
+  const int ncells = W * H;
+  const uint32_t* fld = field + f * (int64_t)ncells;
+  const uint8_t* kc = cost + f * occ_stride;             // (the layer is shared exactly when the map is)
+  auto done = [&](int st_, int n, double c) { status[b] = st_; n_sub[b] = n; path_cost[b] = c; };
+  const double nan = __builtin_nan("");
+  if (settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan);
+  const int fs = field_status[f];
+  if (fs == LIPMPC_FIELD_GOAL_OUTSIDE) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan);
+  if (fs == LIPMPC_FIELD_GOAL_BLOCKED) return done(LIPMPC_RRT_GOAL_OCCUPIED, 0, nan);
+  int si = 0, sj = 0;
+  if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan);
+  int s = si * H + sj;
+  if (occ[f * occ_stride + s] != 0) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan);
+  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
+  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);
+  double* sg = sub_goals + b * (int64_t)S_max * 2;
+  int last_cell;
+  const int n = soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
+  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);                 // (a `field` that is no weighted field of this map and layer)
+  const double total = (double)fld[s] / 5.0;                          // penalties included
+  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, total);
+  soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  sg[2 * (n - 1)] = goal[2 * f];
+  sg[2 * (n - 1) + 1] = goal[2 * f + 1];
+  done(LIPMPC_RRT_FOUND, n, total);
+}
+
+// One lane per robot: frontier_path_body's rules, the walk down the weighted field.
+__global__ void __launch_bounds__(PATH_THREADS) soft_frontier_descent_kernel(int64_t B, int one_field, int W, int H, double ox, double oy,
+                                                                             double dx, double dy, const int32_t* __restrict__ evidence,
+                                                                             const uint8_t* __restrict__ cost, int t_occ,
+                                                                             const uint32_t* __restrict__ field,
+                                                                             const int32_t* __restrict__ n_frontier,
+                                                                             const int32_t* __restrict__ settled,
+                                                                             const double* __restrict__ start, int r_inflate, int max_seg,
+                                                                             int S_max, double* __restrict__ sub_goals,
+                                                                             int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
+                                                                             double* __restrict__ path_cost,
+                                                                             int32_t* __restrict__ target_cell) {
+  const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const int64_t f = one_field ? 0 : b;
+  const int ncells = W * H;
+  const uint32_t* fld = field + f * (int64_t)ncells;
+  const uint8_t* kc = cost + f * (int64_t)ncells;
+  auto done = [&](int st_, int n, double c, int target) { status[b] = st_; n_sub[b] = n; path_cost[b] = c; target_cell[b] = target; };
+  const double nan = __builtin_nan("");
+  if (settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan, -1);
+  int si = 0, sj = 0;
+  if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan, -1);
+  int s = si * H + sj;
+  if (evidence[f * (int64_t)ncells + s] >= t_occ) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan, -1);
+  if (n_frontier[f] == 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
+  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  double* sg = sub_goals + b * (int64_t)S_max * 2;
+  int last_cell;
+  const int n = soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
+  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
+  const double total = (double)fld[s] / 5.0;
+  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, total, last_cell);
+  soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
+  done(LIPMPC_RRT_FOUND, n, total, last_cell);
+}
+
+// tiled_rounds with the weighted round kernel
+int soft_rounds(hipStream_t s, int64_t F, int W, int H, int64_t blk_stride, int64_t cost_stride, const uint8_t* cost, const TiledLayout& l,
+                uint32_t* work, uint32_t* field, int max_rounds, int32_t* settled) {
+  const int tiles = (int)l.tiles, tiles_j = tiles_along(H, TILE_H);
+  uint32_t* flags[2] = {work + l.flags0, work + l.flags1};
+  for (int r = 0; r < max_rounds; ++r)
+    hipLaunchKernelGGL(soft_round_kernel, dim3((unsigned)(F * tiles)), dim3(TILE_THREADS), 0, s, W, H, tiles_j, tiles, blk_stride,
+                       work + l.blocked, cost_stride, cost, field, flags[r & 1], flags[(r + 1) & 1]);
+  hipLaunchKernelGGL(tiled_settle_kernel, dim3((unsigned)F), dim3(SETUP_THREADS), 0, s, tiles, max_rounds & 1, flags[0], flags[1], settled);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+}  // namespace
+
+extern "C" int lipmpc_grid_clearance_cost_batch(int device, int64_t M, int32_t W, int32_t H, const uint8_t* occ, const int32_t* evidence,
+                                                int32_t t_occ, int32_t r_clear, int32_t w_clear, uint8_t* cost, void* hip_stream) {
+  if (M < 0 || M > 0x7fffffff || W < 2 || H < 2 || r_clear < 1 || r_clear > R_CLEAR_MAX || w_clear < 0 || w_clear > LIPMPC_COST_MAX)
+    return LIPMPC_E_ARG;
+  if ((occ != nullptr) == (evidence != nullptr) || !cost || (evidence && (t_occ < 1 || t_occ > THRESHOLD_MAX))) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(M, W, H)) return rc;
+  if (M == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  const int tiles_j = tiles_along(H, TILE_H), tiles = tiles_along(W, TILE_W) * tiles_j;
+  const dim3 grid((unsigned)(M * tiles)), block(TILE_THREADS);
+  if (occ)
+    hipLaunchKernelGGL(soft_cost_kernel<0>, grid, block, 0, (hipStream_t)hip_stream, W, H, tiles_j, tiles, occ, evidence, t_occ, r_clear,
+                       w_clear, cost);
+  else
+    hipLaunchKernelGGL(soft_cost_kernel<1>, grid, block, 0, (hipStream_t)hip_stream, W, H, tiles_j, tiles, occ, evidence, t_occ, r_clear,
+                       w_clear, cost);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_field_weighted_batch(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin,
+                                                const double* cell, const uint8_t* occ, const uint8_t* cost, const double* goal,
+                                                int32_t r_inflate, uint32_t* field, int32_t* field_status, void* work, int64_t work_bytes,
+                                                int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
+    return LIPMPC_E_ARG;
+  if (!occ || !cost || !goal || !field || !field_status) return LIPMPC_E_ARG;
+  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const TiledLayout l = tiled_layout(F, W, H);
+  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  const int64_t maps = grid_shared ? 1 : F, blk_stride = grid_shared ? 0 : l.bm_words;
+  uint32_t* w = (uint32_t*)work;
+  if (!resume) {
+    hipLaunchKernelGGL(tiled_bitmaps_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles, occ,
+                       (const int32_t*)nullptr, 0, 0, w + l.solid, w + l.unknown, w + l.flags0, (int32_t*)nullptr);
+    hipLaunchKernelGGL(tiled_blocked_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
+                       w + l.solid, w + l.unknown, w + l.blocked);
+    hipLaunchKernelGGL(tiled_goal_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, blk_stride, ox, oy, dx,
+                       dy, goal, w + l.blocked, field, field_status, w + l.flags0, l.tiles);
+  }
+  return soft_rounds(s, F, W, H, blk_stride, grid_shared ? (int64_t)0 : (int64_t)ncells, cost, l, w, field, max_rounds, settled);
+}
+
+extern "C" int lipmpc_grid_frontier_field_weighted_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence,
+                                                         const uint8_t* cost, int32_t t_free, int32_t t_occ, int32_t r_inflate,
+                                                         int32_t min_unknown, uint8_t* frontier, uint32_t* field, int32_t* n_frontier,
+                                                         void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume,
+                                                         int32_t* settled, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
+      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || !cost || !field || !n_frontier)
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const TiledLayout l = tiled_layout(F, W, H);
+  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  uint32_t* w = (uint32_t*)work;
+  if (!resume) {
+    hipLaunchKernelGGL(tiled_bitmaps_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles,
+                       (const uint8_t*)nullptr, evidence, t_free, t_occ, w + l.solid, w + l.unknown, w + l.flags0, n_frontier);
+    hipLaunchKernelGGL(tiled_blocked_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
+                       w + l.solid, w + l.unknown, w + l.blocked);
+    hipLaunchKernelGGL(tiled_frontier_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, min_unknown,
+                       w + l.unknown, w + l.blocked, frontier, field, n_frontier, w + l.flags0, l.tiles);
+  }
+  return soft_rounds(s, F, W, H, l.bm_words, ncells, cost, l, w, field, max_rounds, settled);
+}
+
+extern "C" int lipmpc_grid_path_weighted_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                               const double* cell, const uint8_t* occ, int32_t grid_shared, const uint8_t* cost,
+                                               const uint32_t* field, const int32_t* field_status, const int32_t* settled,
+                                               const double* goal, const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
+                                               double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (!occ || !cost || !field || !field_status || !settled || !goal || !start || !sub_goals || !n_sub || !status || !path_cost)
+    return LIPMPC_E_ARG;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(soft_goal_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, ox, oy, dx, dy, occ, cost,
+                     field, field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_path_weighted_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                                        const double* cell, const int32_t* evidence, const uint8_t* cost, int32_t t_occ,
+                                                        const uint32_t* field, const int32_t* n_frontier, const int32_t* settled,
+                                                        const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
+                                                        double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                                        int32_t* target_cell, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (!evidence || !cost || !field || !n_frontier || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell)
+    return LIPMPC_E_ARG;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(soft_frontier_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, ox, oy, dx, dy, evidence, cost, t_occ, field, n_frontier, settled, start,
+                     r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }

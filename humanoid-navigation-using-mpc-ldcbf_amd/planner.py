@@ -25,6 +25,7 @@ by the tiled calls (``lipmpc_grid_frontier_assign_tiled_batch``; ``lipmpc_grid_f
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -39,7 +40,8 @@ RRT_STATUS_NAMES = ("FOUND", "NO_PATH", "START_OCCUPIED", "GOAL_OCCUPIED", "GRID
 
 
 FIELD_INF = 0xFFFFFFFF      # LIPMPC_FIELD_INF: a cell of a field that is blocked or has no path to the goal
-FIELD_NO_CAP = 0x7FFFFFFF   # max_seg of "no spacing cap": no field value reaches it (a field stays below 7 * 2^17)
+FIELD_NO_CAP = 0x7FFFFFFF   # max_seg of "no spacing cap": no field value reaches it (a field stays below 7 * 2^17); the weighted
+                            # path calls compare it with the length in steps alone, which stays below 7 * 2^24
 
 
 def tiled_info():
@@ -50,15 +52,39 @@ def tiled_info():
     return tw.value, th.value, cap.value
 
 
-class _TiledKeywords(type):
-    """The keyword-only ``tiled`` / ``rounds`` of the two field planners, taken off before ``__init__`` runs: the classes'
-    ``__init__`` signatures -- which callers hand on positionally and through ``**kwargs`` -- stay what they were."""
+COST_MAX, R_CLEAR_MAX = 248, 31     # LIPMPC_COST_MAX; the largest r_clear (a disc row of 63 bits is one 64-bit window)
 
-    def __call__(cls, *args, tiled: bool = False, rounds: int | None = None, **kwargs):
+
+class _TiledKeywords(type):
+    """The keyword-only ``tiled`` / ``rounds`` / ``r_clear`` / ``w_clear`` of the two field planners, taken off before ``__init__``
+    runs: the classes' ``__init__`` signatures -- which callers hand on positionally and through ``**kwargs`` -- stay what they were."""
+
+    def __call__(cls, *args, tiled: bool = False, rounds: int | None = None, r_clear: int | None = None, w_clear: int | None = None,
+                 **kwargs):
         self = cls.__new__(cls)
         self._init_tiled(tiled, rounds)
+        self._init_clearance(r_clear, w_clear)
         self.__init__(*args, **kwargs)
         return self
+
+
+def _cost_keyword(method):
+    """The keyword-only ``cost`` of ``field()``, ``plan_grid_batch()`` and ``plan()``: a caller's uint8 layer [M,W,H] (or [W,H] for
+    one map) in place of the clearance layer, taken off before the method runs so that its signature stays what it was."""
+
+    @functools.wraps(method)
+    def with_cost(self, *args, cost=None, **kwargs):
+        if cost is None:
+            return method(self, *args, **kwargs)
+        if not self._CLEARANCE or not self.tiled:
+            raise ValueError(f"{type(self).__name__}: cost= needs GridFieldPlanner or FrontierPlanner with tiled=True (the weighted "
+                             f"fields run on the tiled rounds only; the coordinated and the informed planners are unweighted)")
+        self._given_cost = cost
+        try:
+            return method(self, *args, **kwargs)
+        finally:
+            self._given_cost = None
+    return with_cost
 
 
 class _TiledRounds(metaclass=_TiledKeywords):
@@ -69,6 +95,8 @@ class _TiledRounds(metaclass=_TiledKeywords):
     host, so this raises under stream capture."""
 
     _TILED = True               # False: a subclass whose further calls keep the one-workgroup cap
+    _CLEARANCE = True           # False: a subclass whose further fields (claim rounds, utility field) are unweighted
+    _given_cost = None          # the ``cost=`` of the call that is running (_cost_keyword)
 
     def _init_tiled(self, tiled, rounds):
         self.tiled, self.rounds = bool(tiled), None if rounds is None else int(rounds)
@@ -78,6 +106,48 @@ class _TiledRounds(metaclass=_TiledKeywords):
         if self.rounds is not None and (not self.tiled or not 1 <= self.rounds <= 65536):
             raise ValueError(f"rounds {rounds}: 1..65536 or None, with tiled=True only")
         self._works = []            # every workspace ever handed to a call; the last one is the current one
+
+    def _init_clearance(self, r_clear, w_clear):
+        """SOFT CLEARANCE (include/lipmpc.h): ``r_clear`` 1..31 cells and ``w_clear`` 0..248, both or neither, no defaults (nobody
+        has measured one).  With them every field is the WEIGHTED one over the clearance layer of the map."""
+        self._costs = []            # the clearance layer's buffer: grown only, every buffer kept alive
+        self.r_clear = self.w_clear = None
+        if r_clear is None and w_clear is None:
+            return
+        if not self._CLEARANCE:
+            raise ValueError(f"{type(self).__name__}: r_clear / w_clear are not supported (the claim rounds and the utility field are "
+                             f"unweighted; soft clearance is GridFieldPlanner's and FrontierPlanner's, with tiled=True)")
+        if r_clear is None or w_clear is None:
+            raise ValueError("r_clear and w_clear go together: they have no defaults, nobody has measured one")
+        if not self.tiled:
+            raise ValueError("r_clear / w_clear need tiled=True: the weighted fields run on the tiled rounds only")
+        self.r_clear, self.w_clear = int(r_clear), int(w_clear)
+        if not 1 <= self.r_clear <= R_CLEAR_MAX or not 0 <= self.w_clear <= COST_MAX:
+            raise ValueError(f"invalid clearance parameters (r_clear {r_clear}: 1..{R_CLEAR_MAX}, w_clear {w_clear}: 0..{COST_MAX})")
+
+    def _clearance(self, M, W, H, occ=None, evidence=None, t_occ=0):
+        """The clearance layer [M,W,H] uint8 of M maps given as occ bytes or as evidence, in the planner's own buffer."""
+        if self.r_clear is None:
+            raise ValueError("the planner has no r_clear / w_clear")
+        need = M * W * H
+        if not self._costs or self._costs[-1].numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the clearance layer's buffer must grow: run the call once before the capture")
+            self._costs.append(torch.empty(need, dtype=torch.uint8, device=self.device))
+        cost = self._costs[-1][:need].view(M, W, H)
+        _lib.call("lipmpc_grid_clearance_cost_batch", device=self.device_index, M=M, W=W, H=H, occ=occ, evidence=evidence, t_occ=t_occ,
+                  r_clear=self.r_clear, w_clear=self.w_clear, cost=cost, hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+        return cost
+
+    def _layer(self, M, W, H, **solid):
+        """The cost layer of a call [M,W,H] -- the caller's ``cost=``, else the clearance layer -- or None: an unweighted planner."""
+        cost = self._given_cost
+        if cost is None:
+            return None if self.r_clear is None else self._clearance(M, W, H, **solid)
+        if not isinstance(cost, torch.Tensor) or cost.dtype != torch.uint8 or cost.device != self.device or not cost.is_contiguous() or \
+                tuple(cost.shape) not in ((M, W, H),) + (((W, H),) if M == 1 else ()):
+            raise ValueError(f"cost: a contiguous uint8 tensor [{M},{W},{H}]{' or [W,H]' if M == 1 else ''} on the planner's device")
+        return cost.view(M, W, H)
 
     def _settled(self, out, F, key="settled"):
         """out[key] [F] int32, made if the caller's dict has none."""
@@ -348,7 +418,14 @@ class GridFieldPlanner(_TiledRounds):
     every map size, up to 2^24 cells (include/lipmpc.h, TILED FIELDS) -- the same field bit for bit once ``settled``; ``rounds`` as
     ``_TiledRounds`` says; ``field()`` and ``plan_grid_batch()`` then return ``settled`` [F] too, and a robot whose field is not
     settled gets RRT_FIELD_UNSETTLED and no sub-goal.  ``UnknownEnvFleet.run_replanning`` treats that status as every status other
-    than RRT_FOUND: until a later replan settles the robot's working goal is its final goal, and nothing ends the run."""
+    than RRT_FOUND: until a later replan settles the robot's working goal is its final goal, and nothing ends the run.
+    Keyword-only ``r_clear`` (1..31 cells) / ``w_clear`` (0..248), both or neither, no defaults, with ``tiled=True`` only: SOFT
+    CLEARANCE (include/lipmpc.h).  Every plan then makes the clearance layer of the map -- a byte per cell that decays from ``w_clear``
+    on a solid cell to 0 at ``r_clear`` cells from the nearest one -- and the field and the paths are the WEIGHTED ones, in which
+    a path pays a cell's byte when it leaves the cell: paths keep clear of walls where there is room and still pass a door one cell
+    wide, which ``r_inflate`` = 1 would close.  ``field()``, ``plan_grid_batch()`` then return cost [M,W,H] too; the keyword
+    ``cost=`` of those methods takes any uint8 layer instead; ``clearance_cost(grid)`` returns the layer alone.  The cost is static
+    per plan, and path_cost includes it."""
 
     def __init__(self, r_inflate: int = 0, max_seg: int | None = None, device: int | None = None):
         if not torch.cuda.is_available():
@@ -371,16 +448,29 @@ class GridFieldPlanner(_TiledRounds):
     def _field(self, goal, grid, out):
         if self.tiled:
             ga = grid._args(goal.shape[0], self.device)
-            return self._run_tiled("lipmpc_grid_field_tiled_batch", goal.shape[0], ga.pop("W"), ga.pop("H"), out, **ga, goal=goal,
-                                   r_inflate=self.r_inflate, field=out["field"], field_status=out["field_status"])
+            F, W, H = goal.shape[0], ga.pop("W"), ga.pop("H")
+            cost = self._layer(1 if grid.shared else F, W, H, occ=ga["occ"])
+            name, more = "lipmpc_grid_field_tiled_batch", {}
+            if cost is not None:
+                name, more, out["cost"] = "lipmpc_grid_field_weighted_batch", dict(cost=cost), cost
+            return self._run_tiled(name, F, W, H, out, **ga, **more, goal=goal, r_inflate=self.r_inflate, field=out["field"],
+                                   field_status=out["field_status"])
         _lib.call("lipmpc_grid_field_batch", device=self.device_index, F=goal.shape[0], **grid._args(goal.shape[0], self.device), goal=goal,
                   r_inflate=self.r_inflate, field=out["field"], field_status=out["field_status"],
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
+    def clearance_cost(self, grid):
+        """The clearance layer of ``grid`` (a GridMap) alone: [M,W,H] uint8, M = 1 for a shared map.  It lives in the planner's
+        buffer: the next call that makes a layer overwrites it."""
+        grid = grid.to(self.device)
+        return self._clearance(1 if grid.shared else int(grid.occ.shape[0]), grid.W, grid.H, occ=grid.occ)
+
+    @_cost_keyword
     def field(self, goal, grid, out=None):
         """The cost-to-go fields of ``goal`` [F,2] on ``grid`` (a GridMap: shared, or one map per goal).  Returns dict(field
         [F,W,H] uint32 (FIELD_INF = blocked or cut off), status [F]: 0 OK, 1 the goal's cell is outside the grid, 2 it is blocked
-        -- then the whole field is FIELD_INF).  ``out``: dict(field, field_status) to write into."""
+        -- then the whole field is FIELD_INF).  ``out``: dict(field, field_status) to write into.  A weighted planner (``r_clear``, or
+        the keyword ``cost=``) adds cost [M,W,H]."""
         goal = self._goal(goal)
         F = goal.shape[0]
         grid = grid.to(self.device)
@@ -390,11 +480,13 @@ class GridFieldPlanner(_TiledRounds):
             out = _alloc(table, names, self.device)
         else:
             _check_table({k: table[k] for k in names}, out, self.device, "out")
+        out.pop("cost", None)
         self._field(goal, grid, out)
         if self.tiled:
-            return dict(field=out["field"], status=out["field_status"], settled=out["settled"])
+            return dict(field=out["field"], status=out["field_status"], settled=out["settled"], **({"cost": out["cost"]} if "cost" in out else {}))
         return dict(field=out["field"], status=out["field_status"])
 
+    @_cost_keyword
     def plan_grid_batch(self, goal, grid, start, S_max: int | None = 64, seeds=None, out=None):
         """Plan B robots from ``start`` [B,2] on ``grid``.  ``goal`` [B,2]: one field per robot (``grid`` shared or one map per
         robot); ``goal`` [1,2]: ONE field that every robot descends (``grid`` shared) -- the caller opts in by the shape, rows
@@ -402,7 +494,9 @@ class GridFieldPlanner(_TiledRounds):
         ``UnknownEnvFleet.run_replanning``.  Returns the dict of ``RrtStarPlanner.plan_grid_batch`` -- sub_goals [B,S_max,2] (rows
         past n_sub are 0 in a fresh ``out``, untouched in a given one; the last sub-goal is the goal itself, bit for bit), n_sub
         [B], status [B] (RRT_*), path_cost [B] (the path's length in cells) -- plus field [F,W,H] and field_status [F].
-        ``out``: that dict, to write into (a captured graph replays into the same buffers)."""
+        ``out``: that dict, to write into (a captured graph replays into the same buffers).
+        A weighted planner (``r_clear`` / ``w_clear``, or the keyword ``cost=`` [M,W,H] uint8 with ``tiled=True``) runs cost layer ->
+        weighted field -> weighted path and adds cost [M,W,H] to the dict; path_cost then includes the penalties."""
         goal = self._goal(goal)
         start = torch.as_tensor(start).to(device=self.device, dtype=torch.float64).contiguous()
         if start.dim() != 2 or start.shape[1] != 2:
@@ -422,9 +516,12 @@ class GridFieldPlanner(_TiledRounds):
             self._settled(out, F)
         if B == 0:
             return out
+        out.pop("cost", None)                              # (a dict that comes back: the layer is this call's or none)
         self._field(goal, grid, out)
         ga = grid._args(F, self.device)
         path = dict(lipmpc_grid_path_tiled_batch=dict(settled=out["settled"])) if self.tiled else dict(lipmpc_grid_path_batch={})
+        if "cost" in out:
+            path = dict(lipmpc_grid_path_weighted_batch=dict(settled=out["settled"], cost=out["cost"]))
         (name, more), = path.items()
         _lib.call(name, device=self.device_index, B=B, F=F, **ga, **more, field=out["field"], field_status=out["field_status"],
                   goal=goal, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
@@ -450,7 +547,12 @@ class FrontierPlanner(_TiledRounds):
     Keyword-only ``tiled`` / ``rounds``: as ``GridFieldPlanner``'s -- the tiled calls at every map size up to 2^24 cells, ``settled`` [F] in the
     dicts of ``field()`` and ``plan()``, RRT_FIELD_UNSETTLED (target_cell -1, target NaN) for a robot whose field is not settled.
     ``UnknownEnvFleet.run_exploring`` needs no change: its ``done`` reads RRT_NO_PATH only, so a robot whose replan came back
-    unsettled is parked until a later replan settles, and never ends the fleet."""
+    unsettled is parked until a later replan settles, and never ends the fleet.
+    Keyword-only ``r_clear`` / ``w_clear``: as ``GridFieldPlanner``'s, with ``tiled=True`` only -- the clearance layer from the solid
+    cells of the evidence (unknown cells carry no cost: it would eat the frontier), the weighted frontier field and the weighted
+    paths; ``field()`` and ``plan()`` return cost [F,W,H] too and take the keyword ``cost=``; ``clearance_cost(mapper)`` returns the
+    layer alone.  ``CoordinatedFrontierPlanner``, ``InformedFrontierPlanner`` and their large-map classes refuse these keywords: the
+    claim rounds and the utility field are unweighted."""
 
     def __init__(self, r_inflate: int = 2, min_unknown: int = 2, t_free: int | None = None, t_occ: int | None = None,
                  max_seg: int | None = None, device: int | None = None):
@@ -487,17 +589,28 @@ class FrontierPlanner(_TiledRounds):
     def _field(self, ev, t_free, t_occ, out):
         F, W, H = ev.shape
         if self.tiled:
-            return self._run_tiled("lipmpc_grid_frontier_field_tiled_batch", F, W, H, out, evidence=ev, t_free=t_free, t_occ=t_occ,
-                                   r_inflate=self.r_inflate, min_unknown=self.min_unknown, frontier=out["frontier"], field=out["field"],
-                                   n_frontier=out["n_frontier"])
+            cost = self._layer(F, W, H, evidence=ev, t_occ=t_occ) if self._CLEARANCE else None
+            name, more = "lipmpc_grid_frontier_field_tiled_batch", {}
+            if cost is not None:
+                name, more, out["cost"] = "lipmpc_grid_frontier_field_weighted_batch", dict(cost=cost), cost
+            return self._run_tiled(name, F, W, H, out, evidence=ev, **more, t_free=t_free, t_occ=t_occ, r_inflate=self.r_inflate,
+                                   min_unknown=self.min_unknown, frontier=out["frontier"], field=out["field"], n_frontier=out["n_frontier"])
         _lib.call("lipmpc_grid_frontier_field_batch", device=self.device_index, F=F, W=W, H=H, evidence=ev, t_free=t_free, t_occ=t_occ,
                   r_inflate=self.r_inflate, min_unknown=self.min_unknown, frontier=out["frontier"], field=out["field"],
                   n_frontier=out["n_frontier"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
+    def clearance_cost(self, mapper_or_evidence):
+        """The clearance layer of a mapper or an evidence tensor alone: [F,W,H] uint8 (solid = evidence >= t_occ; unknown cells are
+        no sources of cost).  It lives in the planner's buffer: the next call that makes a layer overwrites it."""
+        ev, _, t_occ, _, _ = self._map(mapper_or_evidence)
+        return self._clearance(*ev.shape, evidence=ev, t_occ=t_occ)
+
+    @_cost_keyword
     def field(self, mapper_or_evidence, out=None):
         """The frontier and the cost-to-go to it of an ``OccupancyMapper`` (shared or per-robot maps) or of an evidence tensor
         [W,H] / [F,W,H].  Returns dict(field [F,W,H] uint32 (0 on frontier cells, FIELD_INF = blocked or cut off), frontier
-        [F,W,H] uint8, n_frontier [F]: 0 = nothing left to explore, the whole field FIELD_INF).  ``out``: that dict, to write into."""
+        [F,W,H] uint8, n_frontier [F]: 0 = nothing left to explore, the whole field FIELD_INF).  ``out``: that dict, to write into.
+        A weighted planner (``r_clear``, or the keyword ``cost=``) adds cost [F,W,H]."""
         ev, t_free, t_occ, _, _ = self._map(mapper_or_evidence)
         table = frontier_outputs(0, *ev.shape, 1)
         names = ("field", "frontier", "n_frontier")
@@ -505,9 +618,11 @@ class FrontierPlanner(_TiledRounds):
             out = _alloc(table, names, self.device)
         else:
             _check_table({k: table[k] for k in names}, out, self.device, "out")
+        out.pop("cost", None)
         self._field(ev, t_free, t_occ, out)
-        return {k: out[k] for k in names + (("settled",) if self.tiled else ())}
+        return {k: out[k] for k in names + (("settled",) if self.tiled else ()) + (("cost",) if "cost" in out else ())}
 
+    @_cost_keyword
     def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None):
         """Plan B robots from ``start`` [B,2] to their nearest frontier: on a shared map (a mapper without ``per_robot``, an
         evidence tensor [W,H] or [1,W,H]) every robot descends the one field, else there are B maps.  ``origin`` / ``cell``: the
@@ -516,7 +631,10 @@ class FrontierPlanner(_TiledRounds):
         n_sub [B], status [B] (RRT_FOUND, RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID, RRT_START_OCCUPIED; RRT_NO_PATH: no frontier
         left, or none within reach), path_cost [B] in cells -- plus target [B,2] (the frontier cell's centre; NaN unless FOUND or
         PATH_OVERFLOW), target_cell [B] (its index i * H + j, else -1), n_frontier [F], field and frontier [F,W,H].
-        ``out``: that dict, to write into (a captured graph replays into the same buffers; nothing is allocated then)."""
+        ``out``: that dict, to write into (a captured graph replays into the same buffers; nothing is allocated then).
+        A weighted planner (``r_clear`` / ``w_clear``, or the keyword ``cost=`` [F,W,H] uint8 with ``tiled=True``) runs cost layer ->
+        weighted field -> weighted path and adds cost [F,W,H] to the dict: "nearest" is then nearest in the weighted metric, and
+        path_cost includes the penalties."""
         ev, t_free, t_occ, origin, cell = self._map(mapper_or_evidence, origin, cell)
         origin, cell, org_c, cell_c = self._placement(origin, cell)
         start = torch.as_tensor(start).to(device=self.device, dtype=torch.float64).contiguous()
@@ -535,9 +653,12 @@ class FrontierPlanner(_TiledRounds):
             self._settled(out, F)
         if B == 0:
             return out
+        out.pop("cost", None)                              # (a dict that comes back: the layer is this call's or none)
         self._field(ev, t_free, t_occ, out)
         path = dict(lipmpc_grid_frontier_path_tiled_batch=dict(settled=out["settled"])) if self.tiled else \
             dict(lipmpc_grid_frontier_path_batch={})
+        if "cost" in out:
+            path = dict(lipmpc_grid_frontier_path_weighted_batch=dict(settled=out["settled"], cost=out["cost"]))
         (name, more), = path.items()
         _lib.call(name, device=self.device_index, B=B, F=F, W=W, H=H, origin=C.addressof(org_c), **more,
                   cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ, field=out["field"], n_frontier=out["n_frontier"], start=start,
@@ -589,6 +710,7 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     have none either."""
 
     _TILED, _TILED_WHY, _TILED_CLASS = False, "the claim rounds keep", "TiledCoordinatedFrontierPlanner"
+    _CLEARANCE = False
     _FRESH = ("field", "frontier", "n_frontier", "work")            # outputs written whole: a fresh dict gets them uninitialised
     _table = staticmethod(assign_outputs)
     _keep_table = staticmethod(assign_keep_outputs)                 # the table of a planner with ``r_keep``
@@ -818,6 +940,7 @@ class InformedFrontierPlanner(FrontierPlanner):
     another target; a shared field sends robots that stand together to the same cell, as the parent does."""
 
     _TILED, _TILED_WHY, _TILED_CLASS = False, "the gain call and the utility field keep", "TiledInformedFrontierPlanner"
+    _CLEARANCE = False
     _SETTLED = ()               # what the large-map subclass adds to the dicts of gain() and field()
 
     def __init__(self, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, **frontier_planner_kwargs):

@@ -44,7 +44,10 @@ extern "C" {
                                 *    + lipmpc_grid_tiled_info / lipmpc_grid_tiled_workspace_bytes /
                                 *      lipmpc_grid_field_tiled_batch / lipmpc_grid_frontier_field_tiled_batch /
                                 *      lipmpc_grid_path_tiled_batch / lipmpc_grid_frontier_path_tiled_batch,
-                                *      LIPMPC_RRT_FIELD_UNSETTLED */
+                                *      LIPMPC_RRT_FIELD_UNSETTLED;
+                                *    + lipmpc_grid_clearance_cost_batch / lipmpc_grid_field_weighted_batch /
+                                *      lipmpc_grid_frontier_field_weighted_batch / lipmpc_grid_path_weighted_batch /
+                                *      lipmpc_grid_frontier_path_weighted_batch, LIPMPC_COST_MAX */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -940,7 +943,8 @@ int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, int64_t F, in
 
 /* TILED FIELDS (backward-compatible addition): the two cost-to-go fields above on LARGE maps, relaxed by many workgroups.  The
  * four calls above keep their cap of 2^17 cells and their one workgroup per field; the calls here take any map with
- * W * H <= 2^24 and W, H <= 4096 (a finite field value stays below 7 * 2^24), and compute THE SAME FIELD, bit for bit: the
+ * W * H <= 2^24 and W, H <= 4096 (a finite field value stays below 7 * 2^24; a WEIGHTED one, SOFT CLEARANCE below, below
+ * (7 + LIPMPC_COST_MAX) * 2^24 = 255 * 2^24 < 2^32 - 1), and compute THE SAME FIELD, bit for bit: the
  * least cost is unique.  The map is cut into tiles of tile_w x tile_h cells (along i and along j; lipmpc_grid_tiled_info).  The
  * calls' set-up kernels (bitmaps, the blocked bitmap by the disc test, seeds, tile flags, n_frontier, statuses) run one
  * workgroup per 256 cells; then a call enqueues ROUNDS.  One round is one kernel launch with one workgroup per (field, tile): a
@@ -1014,6 +1018,71 @@ int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int64_t F, int3
                                           const int32_t* n_frontier, const int32_t* settled, const double* start,
                                           int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                           int32_t* status, double* path_cost, int32_t* target_cell, void* hip_stream);
+
+/* SOFT CLEARANCE (backward-compatible addition): a per-cell traversal cost that decays with the distance to the nearest solid cell,
+ * and the two tiled fields and their paths in the metric that charges it.  r_inflate forbids cells; the cost layer prices them: a
+ * path keeps clear of walls where there is room and still passes a door that is one cell wide.  Everything is an integer.
+ *
+ * lipmpc_grid_clearance_cost_batch: the layer of M maps.  Exactly one of
+ *  occ       [M, W*H] uint8, solid = byte != 0, and
+ *  evidence  [M, W*H] int32, solid = e >= t_occ (t_occ 1..2^30, read with evidence only)
+ *  is non-null.  r_clear 1..31 (cells; a disc row is then at most 63 consecutive bits, one 64-bit window), w_clear
+ *  0..LIPMPC_COST_MAX.  With d2(c) the least (i - si)^2 + (j - sj)^2 over the solid cells (si, sj) INSIDE the grid (the map's edge is
+ *  not solid, as for r_inflate):
+ *  cost      [M, W*H] uint8 (output): 0 if d2 > r_clear^2 (or the map has no solid cell), else
+ *            (w_clear * (r_clear^2 - d2)) / r_clear^2 in integer division -- w_clear on a solid cell itself.
+ *  Unknown cells of an evidence grid are no sources of cost, for the reason they are not inflated: it would eat the frontier.
+ *  One workgroup per (map, tile); no workspace, no allocation, no host synchronisation, capturable.  LIPMPC_E_ARG: M < 0, W or
+ *  H < 2, r_clear or w_clear outside their ranges, both or neither of occ / evidence, a null cost, t_occ outside 1..2^30 with
+ *  evidence.  Then LIPMPC_E_UNSUPPORTED: the tiled caps, with M for F.  Then M = 0 enqueues nothing and returns 0.
+ *
+ * lipmpc_grid_field_weighted_batch, lipmpc_grid_frontier_field_weighted_batch: lipmpc_grid_field_tiled_batch's and
+ *  lipmpc_grid_frontier_field_tiled_batch's arguments, refusals, workspace, rounds, resume and settled, word for word, plus
+ *  cost      uint8 [grid_shared ? 1 : F, W*H] (the goal field), [F, W*H] (the frontier field): ANY byte layer, not only the one
+ *            above.  A byte above LIPMPC_COST_MAX is read as LIPMPC_COST_MAX; nothing scans the layer on the host.  Null:
+ *            LIPMPC_E_ARG.  A resume reads the same layer.
+ *  THE CONTRACT: with k(c) = min(cost[c], LIPMPC_COST_MAX), the field is the unique fixed point of
+ *      f(c) = k(c) + min over legal moves c -> n of (f(n) + step),   f = 0 on the sources,
+ *  moves, steps (5 / 7), the blocked rule and the no-corner-cut rule being the tiled calls': a cell pays its own cost when it is
+ *  LEFT, a source pays nothing.  settled[f] == 1: the field is that fixed point, bit for bit -- weighted Dijkstra's.  Before that
+ *  every finite word is the cost of a real path, and THE ROUND GUARANTEE holds with "least-cost" in the weighted metric.  A finite
+ *  value stays below (7 + LIPMPC_COST_MAX) * 2^24 = 255 * 2^24 < 2^32 - 1 = LIPMPC_FIELD_INF on the largest map: no addition
+ *  wraps (the unweighted fields stay below 7 * 2^24).  With an all-zero layer the output is the tiled calls', bit for bit.
+ *
+ * lipmpc_grid_path_weighted_batch, lipmpc_grid_frontier_path_weighted_batch: the tiled path calls' arguments, status rules (the
+ *  settled rule first), snap and refusals, plus the same `cost` (null with B > 0: LIPMPC_E_ARG).
+ *  THE DESCENT takes the first neighbour n in the contract's order with a legal move and f(n) + step + k(c) == f(c).
+ *  STRING PULLING keeps two sums: pen = the sum of k over the descended cells from the anchor (inclusive) to the current cell
+ *  (exclusive); seg_pen(a, cur) = the sum of k over the cells the segment rule visits between the two, minus k(cur).  A sub-goal
+ *  is set where the line of sight breaks, where seg_pen(a, cur) > pen (the straight segment would pay more penalty than the
+ *  descended path did), or where the length since the anchor WITH PENALTIES EXCLUDED, (f(a) - f(cur)) - pen, reaches max_seg -- so
+ *  max_seg counts steps only and 0x7FFFFFFF still means "no cap" although weighted values may exceed it.  Re-anchoring at the
+ *  previous cell sets pen = k(prev), at the current cell pen = 0; the segment between two adjacent cells always passes.
+ *  path_cost = f(s) / 5.0, PENALTIES INCLUDED: it is the weighted cost, not the length in cells.  The last sub-goal and
+ *  target_cell are the tiled calls'.  With an all-zero layer every output is the tiled path calls', bit for bit. */
+#define LIPMPC_COST_MAX 248
+int lipmpc_grid_clearance_cost_batch(int device, int64_t M, int32_t W, int32_t H, const uint8_t* occ, const int32_t* evidence,
+                                     int32_t t_occ, int32_t r_clear, int32_t w_clear, uint8_t* cost, void* hip_stream);
+int lipmpc_grid_field_weighted_batch(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin,
+                                     const double* cell, const uint8_t* occ, const uint8_t* cost, const double* goal,
+                                     int32_t r_inflate, uint32_t* field, int32_t* field_status, void* work, int64_t work_bytes,
+                                     int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream);
+int lipmpc_grid_frontier_field_weighted_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence,
+                                              const uint8_t* cost, int32_t t_free, int32_t t_occ, int32_t r_inflate,
+                                              int32_t min_unknown, uint8_t* frontier, uint32_t* field, int32_t* n_frontier,
+                                              void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume, int32_t* settled,
+                                              void* hip_stream);
+int lipmpc_grid_path_weighted_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell,
+                                    const uint8_t* occ, int32_t grid_shared, const uint8_t* cost, const uint32_t* field,
+                                    const int32_t* field_status, const int32_t* settled, const double* goal, const double* start,
+                                    int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
+                                    int32_t* status, double* path_cost, void* hip_stream);
+int lipmpc_grid_frontier_path_weighted_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                             const double* cell, const int32_t* evidence, const uint8_t* cost, int32_t t_occ,
+                                             const uint32_t* field, const int32_t* n_frontier, const int32_t* settled,
+                                             const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
+                                             double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                             int32_t* target_cell, void* hip_stream);
 
 /* TILED EXPLORERS (backward-compatible addition): the informed and the coordinated explorer on LARGE maps.  The three informed
  * calls and the claim call above keep their cap of 2^17 cells and their one workgroup per map; the calls here take what the tiled
