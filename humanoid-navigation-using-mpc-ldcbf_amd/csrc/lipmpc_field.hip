@@ -397,10 +397,17 @@ __device__ inline int walk(const uint32_t* __restrict__ fld, int W, int H, int s
   return count + 1;
 }
 
+// (the weighted walk of SOFT CLEARANCE, below)
+__device__ inline int soft_walk(const uint32_t* __restrict__ fld, const uint8_t* __restrict__ kc, int W, int H, int s, int max_seg,
+                                double ox, double oy, double dx, double dy, double* sg, int& last_cell);
+
 // One lane per robot.  `settled`: null, or the tiled field calls' word per field -- a robot whose field is not settled gets
-// LIPMPC_RRT_FIELD_UNSETTLED before any other rule.
+// LIPMPC_RRT_FIELD_UNSETTLED before any other rule.  WEIGHTED: the walk is soft_walk() down a weighted field, on the cost layer
+// `cost` (shared exactly when the map is); else `cost` is not read.
+template <bool WEIGHTED>
 __device__ __forceinline__ void grid_path_body(int64_t B, int one_field, int W, int H, int64_t occ_stride, double ox, double oy, double dx,
-                                               double dy, const uint8_t* __restrict__ occ, const uint32_t* __restrict__ field,
+                                               double dy, const uint8_t* __restrict__ occ, const uint8_t* __restrict__ cost,
+                                               const uint32_t* __restrict__ field,
                                                const int32_t* __restrict__ field_status, const int32_t* __restrict__ settled,
                                                const double* __restrict__ goal, const double* __restrict__ start, int r_inflate,
                                                int max_seg, int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
@@ -410,9 +417,10 @@ __device__ __forceinline__ void grid_path_body(int64_t B, int one_field, int W, 
   const int64_t f = one_field ? 0 : b;
   const int ncells = W * H;
   const uint32_t* fld = field + f * (int64_t)ncells;
-  auto done = [&](int st_, int n, double cost) { status[b] = st_; n_sub[b] = n; path_cost[b] = cost; };
+  const uint8_t* kc = WEIGHTED ? cost + f * occ_stride : nullptr;   // (the layer is shared exactly when the map is)
+  auto done = [&](int st_, int n, double c) { status[b] = st_; n_sub[b] = n; path_cost[b] = c; };
   const double nan = __builtin_nan("");
-  if (settled && settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan);
+  if ((WEIGHTED || settled) && settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan);       // (a weighted field has the word)
   const int fs = field_status[f];
   if (fs == LIPMPC_FIELD_GOAL_OUTSIDE) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan);
   if (fs == LIPMPC_FIELD_GOAL_BLOCKED) return done(LIPMPC_RRT_GOAL_OCCUPIED, 0, nan);
@@ -425,14 +433,17 @@ __device__ __forceinline__ void grid_path_body(int64_t B, int one_field, int W, 
   double* sg = sub_goals + b * (int64_t)S_max * 2;
   // the walk, twice: count the sub-goals, then -- if they fit -- write them (rows past n_sub stay untouched)
   int last_cell;
-  const int n = walk(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
-  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);                 // (a `field` that is no cost-to-go field of this map)
-  const double cost = (double)fld[s] / 5.0;
-  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, cost);
-  walk(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  int n;
+  if constexpr (WEIGHTED) n = soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
+  else n = walk(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
+  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);                 // (a `field` that is no cost-to-go field of this map and layer)
+  const double total = (double)fld[s] / 5.0;                          // penalties included
+  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, total);
+  if constexpr (WEIGHTED) soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  else walk(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
   sg[2 * (n - 1)] = goal[2 * f];                                      // the goal itself, not its cell's centre
   sg[2 * (n - 1) + 1] = goal[2 * f + 1];
-  done(LIPMPC_RRT_FOUND, n, cost);
+  done(LIPMPC_RRT_FOUND, n, total);
 }
 
 __global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int one_field, int W, int H, int64_t occ_stride, double ox,
@@ -443,14 +454,16 @@ __global__ void __launch_bounds__(PATH_THREADS) grid_path_kernel(int64_t B, int 
                                                                  int r_inflate, int max_seg, int S_max, double* __restrict__ sub_goals,
                                                                  int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
                                                                  double* __restrict__ path_cost) {
-  grid_path_body(B, one_field, W, H, occ_stride, ox, oy, dx, dy, occ, field, field_status, nullptr, goal, start, r_inflate, max_seg, S_max,
-                 sub_goals, n_sub, status, path_cost);
+  grid_path_body<false>(B, one_field, W, H, occ_stride, ox, oy, dx, dy, occ, nullptr, field, field_status, nullptr, goal, start, r_inflate,
+                        max_seg, S_max, sub_goals, n_sub, status, path_cost);
 }
 
 // One lane per robot: grid_path_kernel down a frontier field, to the centre of the first frontier cell reached.  `settled`: as
-// grid_path_body's.
+// grid_path_body's, and so are WEIGHTED and `cost` (a layer per field).
+template <bool WEIGHTED>
 __device__ __forceinline__ void frontier_path_body(int64_t B, int one_field, int W, int H, double ox, double oy, double dx, double dy,
-                                                   const int32_t* __restrict__ evidence, int t_occ, const uint32_t* __restrict__ field,
+                                                   const int32_t* __restrict__ evidence, const uint8_t* __restrict__ cost, int t_occ,
+                                                   const uint32_t* __restrict__ field,
                                                    const int32_t* __restrict__ n_frontier, const int32_t* __restrict__ settled,
                                                    const double* __restrict__ start, int r_inflate, int max_seg, int S_max,
                                                    double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
@@ -461,9 +474,9 @@ __device__ __forceinline__ void frontier_path_body(int64_t B, int one_field, int
   const int64_t f = one_field ? 0 : b;
   const int ncells = W * H;
   const uint32_t* fld = field + f * (int64_t)ncells;
-  auto done = [&](int st_, int n, double cost, int target) { status[b] = st_; n_sub[b] = n; path_cost[b] = cost; target_cell[b] = target; };
+  auto done = [&](int st_, int n, double c, int target) { status[b] = st_; n_sub[b] = n; path_cost[b] = c; target_cell[b] = target; };
   const double nan = __builtin_nan("");
-  if (settled && settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan, -1);
+  if ((WEIGHTED || settled) && settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan, -1);
   int si = 0, sj = 0;
   if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan, -1);
   int s = si * H + sj;
@@ -473,13 +486,16 @@ __device__ __forceinline__ void frontier_path_body(int64_t B, int one_field, int
   if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
   double* sg = sub_goals + b * (int64_t)S_max * 2;
   int last_cell;
-  const int n = walk(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
-  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);             // (a `field` that is no frontier field of this map)
-  const double cost = (double)fld[s] / 5.0;
-  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, cost, last_cell);
-  walk(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  int n;
+  if constexpr (WEIGHTED) n = soft_walk(fld, cost + f * (int64_t)ncells, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
+  else n = walk(fld, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
+  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);             // (a `field` that is no frontier field of this map and layer)
+  const double total = (double)fld[s] / 5.0;                          // penalties included
+  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, total, last_cell);
+  if constexpr (WEIGHTED) soft_walk(fld, cost + f * (int64_t)ncells, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
+  else walk(fld, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
   centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
-  done(LIPMPC_RRT_FOUND, n, cost, last_cell);
+  done(LIPMPC_RRT_FOUND, n, total, last_cell);
 }
 
 __global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, int one_field, int W, int H, double ox, double oy, double dx,
@@ -490,8 +506,8 @@ __global__ void __launch_bounds__(PATH_THREADS) frontier_path_kernel(int64_t B, 
                                                                      int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
                                                                      int32_t* __restrict__ status, double* __restrict__ path_cost,
                                                                      int32_t* __restrict__ target_cell) {
-  frontier_path_body(B, one_field, W, H, ox, oy, dx, dy, evidence, t_occ, field, n_frontier, nullptr, start, r_inflate, max_seg, S_max,
-                     sub_goals, n_sub, status, path_cost, target_cell);
+  frontier_path_body<false>(B, one_field, W, H, ox, oy, dx, dy, evidence, nullptr, t_occ, field, n_frontier, nullptr, start, r_inflate,
+                            max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1244,12 +1260,16 @@ __global__ void __launch_bounds__(PATH_THREADS) frontier_utility_path_kernel(
   done(LIPMPC_RRT_FOUND, n, cost, last_cell);
 }
 
+// E_ARG of a grid's placement
+bool bad_placement(const double* origin, const double* cell) {
+  if (!origin || !cell) return true;
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  return !(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY);
+}
+
 // what both entry points refuse about the grid: E_ARG, then the caps
 int grid_refusal(int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate) {
-  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
-    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
   if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
   return LIPMPC_OK;
 }
@@ -1663,10 +1683,15 @@ __global__ void __launch_bounds__(SETUP_THREADS) tiled_frontier_seed_kernel(int 
   if (lane == 0 && mine) atomicAdd(n_frontier + f, mine);            // (integers: the sum is the same in any order)
 }
 
-// ONE ROUND.  blockIdx.x = field * tiles + tile.
-__global__ void __launch_bounds__(TILE_THREADS) tiled_round_kernel(int W, int H, int tiles_j, int tiles, int64_t blk_stride,
-                                                                   const uint32_t* __restrict__ blk, uint32_t* field, uint32_t* cur,
-                                                                   uint32_t* next) {
+// the byte a path pays for leaving cell c, on top of the step (SOFT CLEARANCE, below)
+__device__ inline uint32_t soft_k(const uint8_t* __restrict__ cost, int c) { return min((uint32_t)cost[c], (uint32_t)LIPMPC_COST_MAX); }
+
+// ONE ROUND.  blockIdx.x = field * tiles + tile.  WEIGHTED: the eight cost bytes of a thread's cells ride in one more register and
+// are added to what a cell takes; a source holds 0 and never falls, so it pays nothing.  Else `cost` is not read.
+template <bool WEIGHTED>
+__device__ __forceinline__ void round_body(int W, int H, int tiles_j, int tiles, int64_t blk_stride, const uint32_t* __restrict__ blk,
+                                           int64_t cost_stride, const uint8_t* __restrict__ cost, uint32_t* field, uint32_t* cur,
+                                           uint32_t* next) {
   __shared__ uint32_t lf[HALO_CELLS];                 // field words, local index l = (li + 1) * HALO_H + lj + 1
   __shared__ uint32_t lb[HALO_PADDED / 32 + 2];       // blocked bits by l; a cell outside the grid is blocked
   __shared__ uint32_t rim;
@@ -1693,20 +1718,35 @@ __global__ void __launch_bounds__(TILE_THREADS) tiled_round_kernel(int W, int H,
   if (tid == 0) st_agent(my_flag, 0u);
 
   // the legal moves of my eight cells, a byte per cell, bit d = neighbour (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0),
-  // (1,1): the neighbour unblocked and, for a diagonal, both side cells unblocked.  0 for a blocked cell.
+  // (1,1): the neighbour unblocked and, for a diagonal, both side cells unblocked.  0 for a blocked cell.  WEIGHTED: beside them
+  // the cells' eight cost bytes, clamped.
   const int l_first = ((tid >> 6) + 1) * HALO_H + (tid & 63) + 1;
   auto open_at = [&](int l) { return ((lb[l >> 5] >> (l & 31)) & 1u) ^ 1u; };       // 1 = unblocked (integers: no lane masks to keep)
-  uint64_t moves = 0;
+  uint64_t moves = 0, costs = 0;
 #pragma unroll 1
   for (int k = 0; k < TILE_OWN; ++k) {
     const int l = l_first + k * TILE_ROWS * HALO_H;
     const uint32_t up = open_at(l - HALO_H), dn = open_at(l + HALO_H), lt = open_at(l - 1), rt = open_at(l + 1);
     const uint32_t m = (open_at(l - HALO_H - 1) & up & lt) | up << 1 | (open_at(l - HALO_H + 1) & up & rt) << 2 | lt << 3 | rt << 4 |
                        (open_at(l + HALO_H - 1) & dn & lt) << 5 | dn << 6 | (open_at(l + HALO_H + 1) & dn & rt) << 7;
-    moves |= (uint64_t)(m * open_at(l)) << (8 * k);
+    const uint32_t mine = m * open_at(l);
+    moves |= (uint64_t)mine << (8 * k);
+    if constexpr (WEIGHTED) {
+      const int gi = i0 + k * TILE_ROWS + (tid >> 6), gj = j0 + (tid & 63);          // (an unblocked cell is inside the grid)
+      if (mine) costs |= (uint64_t)soft_k(cost + f * cost_stride, gi * H + gj) << (8 * k);
+    }
   }
 
-  // the sweeps of relax(), on my cells, the halo held
+  // the sweeps of relax(), on my cells, the halo held.
+  // WHY THE WEIGHTED ROUNDS GIVE WEIGHTED DIJKSTRA'S FIELD.  The argument of THE TILED FIELD carries over word for word; the cell
+  // cost enters in ONE place: a value a cell takes is  k(c) + f(n) + step  for a legal move c -> n, which is the cost of the real
+  // path "leave c, then n's path" in the metric where leaving c costs k(c) more.  Values are still path costs and still only fall,
+  // so no flag set <=> a fixed point of  f(c) = k(c) + min over legal moves of f(n) + step,  f = 0 on the sources; its finite values
+  // are >= the least cost (they are path costs) and <= it (induction along a least-cost path); k >= 0 is an integer, so the least
+  // cost is unique and the bits are Dijkstra's.  The round guarantee's induction uses "the rest of a least-cost path is a least-cost
+  // path" and "a tile relaxes to its local fixed point", both of which hold in the weighted metric.
+  // NO WRAP: a stored value is the cost of a SIMPLE path (a value derived through the cell itself would be larger than the one it
+  // holds), at most 2^24 - 1 moves of at most 7 + 248 each; a candidate adds one more: <= 255 * 2^24 < 2^32 - 1 = INF.
   uint32_t fell = 0;
   for (;;) {
     int changed = 0;
@@ -1715,13 +1755,14 @@ __global__ void __launch_bounds__(TILE_THREADS) tiled_round_kernel(int W, int H,
       const uint32_t m = (uint32_t)(moves >> (8 * k)) & 0xFFu;
       if (m) {
         const int l = l_first + k * TILE_ROWS * HALO_H;
-        auto via = [&](int bit, int off, uint32_t cost) {
+        auto via = [&](int bit, int off, uint32_t step) {
           const uint32_t v = ld(lf + l + off);
-          return ((m >> bit) & 1u) && v != INF ? v + cost : INF;
+          return ((m >> bit) & 1u) && v != INF ? v + step : INF;
         };
         const uint32_t cur_v = ld(lf + l);
-        const uint32_t best = min(min(min(via(0, -HALO_H - 1, DIAGONAL), via(1, -HALO_H, AXIAL)), min(via(2, -HALO_H + 1, DIAGONAL), via(3, -1, AXIAL))),
-                                  min(min(via(4, 1, AXIAL), via(5, HALO_H - 1, DIAGONAL)), min(via(6, HALO_H, AXIAL), via(7, HALO_H + 1, DIAGONAL))));
+        uint32_t best = min(min(min(via(0, -HALO_H - 1, DIAGONAL), via(1, -HALO_H, AXIAL)), min(via(2, -HALO_H + 1, DIAGONAL), via(3, -1, AXIAL))),
+                            min(min(via(4, 1, AXIAL), via(5, HALO_H - 1, DIAGONAL)), min(via(6, HALO_H, AXIAL), via(7, HALO_H + 1, DIAGONAL))));
+        if constexpr (WEIGHTED) best = best == INF ? INF : best + ((uint32_t)(costs >> (8 * k)) & 0xFFu);      // THE CELL COST ENTERS HERE
         if (best < cur_v) { st(lf + l, best); changed = 1; fell |= 1u << k; }
       }
     }
@@ -1750,6 +1791,18 @@ __global__ void __launch_bounds__(TILE_THREADS) tiled_round_kernel(int W, int H,
   }
 }
 
+__global__ void __launch_bounds__(TILE_THREADS) tiled_round_kernel(
+    int W, int H, int tiles_j, int tiles, int64_t blk_stride, const uint32_t* __restrict__ blk, uint32_t* field, uint32_t* cur,
+    uint32_t* next) {
+  round_body<false>(W, H, tiles_j, tiles, blk_stride, blk, 0, nullptr, field, cur, next);
+}
+
+__global__ void __launch_bounds__(TILE_THREADS) soft_round_kernel(
+    int W, int H, int tiles_j, int tiles, int64_t blk_stride, const uint32_t* __restrict__ blk, int64_t cost_stride,
+    const uint8_t* __restrict__ cost, uint32_t* field, uint32_t* cur, uint32_t* next) {
+  round_body<true>(W, H, tiles_j, tiles, blk_stride, blk, cost_stride, cost, field, cur, next);
+}
+
 // after the call's last round: settled[f] = no flag of field f set in `live`; with `swap` the flags move to array 0, where the
 // next call's first round reads them.  blockIdx.x = field.
 __global__ void __launch_bounds__(SETUP_THREADS) tiled_settle_kernel(int tiles, int swap, uint32_t* flags0, uint32_t* flags1,
@@ -1776,8 +1829,8 @@ __global__ void __launch_bounds__(PATH_THREADS) tiled_goal_descent_kernel(int64_
                                                                           int r_inflate, int max_seg, int S_max,
                                                                           double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
                                                                           int32_t* __restrict__ status, double* __restrict__ path_cost) {
-  grid_path_body(B, one_field, W, H, occ_stride, ox, oy, dx, dy, occ, field, field_status, settled, goal, start, r_inflate, max_seg, S_max,
-                 sub_goals, n_sub, status, path_cost);
+  grid_path_body<false>(B, one_field, W, H, occ_stride, ox, oy, dx, dy, occ, nullptr, field, field_status, settled, goal, start, r_inflate,
+                        max_seg, S_max, sub_goals, n_sub, status, path_cost);
 }
 
 __global__ void __launch_bounds__(PATH_THREADS) tiled_frontier_descent_kernel(int64_t B, int one_field, int W, int H, double ox, double oy,
@@ -1790,8 +1843,28 @@ __global__ void __launch_bounds__(PATH_THREADS) tiled_frontier_descent_kernel(in
                                                                               int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
                                                                               double* __restrict__ path_cost,
                                                                               int32_t* __restrict__ target_cell) {
-  frontier_path_body(B, one_field, W, H, ox, oy, dx, dy, evidence, t_occ, field, n_frontier, settled, start, r_inflate, max_seg, S_max,
-                     sub_goals, n_sub, status, path_cost, target_cell);
+  frontier_path_body<false>(B, one_field, W, H, ox, oy, dx, dy, evidence, nullptr, t_occ, field, n_frontier, settled, start, r_inflate,
+                            max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
+}
+
+// the two path bodies, WEIGHTED (SOFT CLEARANCE, below)
+__global__ void __launch_bounds__(PATH_THREADS) soft_goal_descent_kernel(
+    int64_t B, int one_field, int W, int H, int64_t occ_stride, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ occ,
+    const uint8_t* __restrict__ cost, const uint32_t* __restrict__ field, const int32_t* __restrict__ field_status,
+    const int32_t* __restrict__ settled, const double* __restrict__ goal, const double* __restrict__ start, int r_inflate, int max_seg,
+    int S_max, double* __restrict__ sub_goals, int32_t* __restrict__ n_sub, int32_t* __restrict__ status, double* __restrict__ path_cost) {
+  grid_path_body<true>(B, one_field, W, H, occ_stride, ox, oy, dx, dy, occ, cost, field, field_status, settled, goal, start, r_inflate,
+                       max_seg, S_max, sub_goals, n_sub, status, path_cost);
+}
+
+__global__ void __launch_bounds__(PATH_THREADS) soft_frontier_descent_kernel(
+    int64_t B, int one_field, int W, int H, double ox, double oy, double dx, double dy, const int32_t* __restrict__ evidence,
+    const uint8_t* __restrict__ cost, int t_occ, const uint32_t* __restrict__ field, const int32_t* __restrict__ n_frontier,
+    const int32_t* __restrict__ settled, const double* __restrict__ start, int r_inflate, int max_seg, int S_max,
+    double* __restrict__ sub_goals, int32_t* __restrict__ n_sub, int32_t* __restrict__ status, double* __restrict__ path_cost,
+    int32_t* __restrict__ target_cell) {
+  frontier_path_body<true>(B, one_field, W, H, ox, oy, dx, dy, evidence, cost, t_occ, field, n_frontier, settled, start, r_inflate, max_seg,
+                           S_max, sub_goals, n_sub, status, path_cost, target_cell);
 }
 
 // the tiled calls' caps, after every E_ARG
@@ -1810,16 +1883,101 @@ int tiled_refusal(int64_t F, int32_t W, int32_t H, const void* work, int64_t wor
   return work_bytes < tiled_bytes(F, W, H) ? LIPMPC_E_ARG : LIPMPC_OK;
 }
 
-// the rounds and the settle kernel
+// the rounds and the settle kernel; with a cost layer (`cost` not null, `cost_stride` bytes from field to field) the weighted rounds
 int tiled_rounds(hipStream_t s, int64_t F, int W, int H, int64_t blk_stride, const TiledLayout& l, uint32_t* work, uint32_t* field,
-                 int max_rounds, int32_t* settled) {
+                 int max_rounds, int32_t* settled, const uint8_t* cost = nullptr, int64_t cost_stride = 0) {
   const int tiles = (int)l.tiles, tiles_j = tiles_along(H, TILE_H);
+  const dim3 grid((unsigned)(F * tiles)), block(TILE_THREADS);
   uint32_t* flags[2] = {work + l.flags0, work + l.flags1};
-  for (int r = 0; r < max_rounds; ++r)
-    hipLaunchKernelGGL(tiled_round_kernel, dim3((unsigned)(F * tiles)), dim3(TILE_THREADS), 0, s, W, H, tiles_j, tiles, blk_stride,
-                       work + l.blocked, field, flags[r & 1], flags[(r + 1) & 1]);
+  for (int r = 0; r < max_rounds; ++r) {
+    if (cost)
+      hipLaunchKernelGGL(soft_round_kernel, grid, block, 0, s, W, H, tiles_j, tiles, blk_stride, work + l.blocked, cost_stride, cost, field,
+                         flags[r & 1], flags[(r + 1) & 1]);
+    else
+      hipLaunchKernelGGL(tiled_round_kernel, grid, block, 0, s, W, H, tiles_j, tiles, blk_stride, work + l.blocked, field, flags[r & 1],
+                         flags[(r + 1) & 1]);
+  }
   hipLaunchKernelGGL(tiled_settle_kernel, dim3((unsigned)F), dim3(SETUP_THREADS), 0, s, tiles, max_rounds & 1, flags[0], flags[1], settled);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+// what a tiled field call derives from its shape: the workspace's layout, the set-up launches' blocks per map (a wave per 64 cells
+// of the padded map), the maps to set up and the stride of their blocked bitmaps (one map, stride 0, on a shared grid)
+struct TiledCall {
+  TiledLayout l;
+  int ncells, chunks;
+  int64_t maps, blk_stride;
+  uint32_t* w;
+};
+TiledCall tiled_call(int64_t F, int W, int H, bool shared, void* work) {
+  TiledCall t;
+  t.l = tiled_layout(F, W, H);
+  t.ncells = W * H;
+  t.chunks = ((int)(t.l.bm_words - 2) * 32 + SETUP_THREADS - 1) / SETUP_THREADS;
+  t.maps = shared ? 1 : F;
+  t.blk_stride = shared ? 0 : t.l.bm_words;
+  t.w = (uint32_t*)work;
+  return t;
+}
+
+// the first two set-up launches of the frontier kind (the frontier and the utility field): the bitmaps of the evidence, `counter`
+// cleared, then the blocked bitmap
+void frontier_bitmaps(hipStream_t s, const TiledCall& t, int64_t F, int W, int H, const int32_t* evidence, int t_free, int t_occ,
+                      int r_inflate, int32_t* counter) {
+  const TiledLayout& l = t.l;
+  const dim3 grid((unsigned)(F * t.chunks)), block(SETUP_THREADS);
+  hipLaunchKernelGGL(tiled_bitmaps_kernel<1>, grid, block, 0, s, t.ncells, t.chunks, F, l.tiles, (const uint8_t*)nullptr, evidence, t_free,
+                     t_occ, t.w + l.solid, t.w + l.unknown, t.w + l.flags0, counter);
+  hipLaunchKernelGGL(tiled_blocked_kernel<1>, grid, block, 0, s, W, H, t.chunks, r_inflate, t.w + l.solid, t.w + l.unknown, t.w + l.blocked);
+}
+
+// lipmpc_grid_field_tiled_batch and, `weighted`, lipmpc_grid_field_weighted_batch: a null `cost` is E_ARG for the latter alone
+int goal_field(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin, const double* cell,
+               const uint8_t* occ, bool weighted, const uint8_t* cost, const double* goal, int32_t r_inflate, uint32_t* field,
+               int32_t* field_status, void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume, int32_t* settled,
+               void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell))
+    return LIPMPC_E_ARG;
+  if (!occ || (weighted && !cost) || !goal || !field || !field_status) return LIPMPC_E_ARG;
+  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const TiledCall t = tiled_call(F, W, H, grid_shared != 0, work);
+  const TiledLayout& l = t.l;
+  if (!resume) {
+    const dim3 maps((unsigned)(t.maps * t.chunks)), block(SETUP_THREADS);
+    hipLaunchKernelGGL(tiled_bitmaps_kernel<0>, maps, block, 0, s, t.ncells, t.chunks, F, l.tiles, occ, (const int32_t*)nullptr, 0, 0,
+                       t.w + l.solid, t.w + l.unknown, t.w + l.flags0, (int32_t*)nullptr);
+    hipLaunchKernelGGL(tiled_blocked_kernel<0>, maps, block, 0, s, W, H, t.chunks, r_inflate, t.w + l.solid, t.w + l.unknown,
+                       t.w + l.blocked);
+    hipLaunchKernelGGL(tiled_goal_seed_kernel, dim3((unsigned)(F * t.chunks)), block, 0, s, W, H, t.chunks, t.blk_stride, origin[0],
+                       origin[1], cell[0], cell[1], goal, t.w + l.blocked, field, field_status, t.w + l.flags0, l.tiles);
+  }
+  return tiled_rounds(s, F, W, H, t.blk_stride, l, t.w, field, max_rounds, settled, weighted ? cost : nullptr,
+                      grid_shared ? (int64_t)0 : (int64_t)t.ncells);
+}
+
+// lipmpc_grid_frontier_field_tiled_batch and, `weighted`, lipmpc_grid_frontier_field_weighted_batch
+int frontier_field(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, bool weighted, const uint8_t* cost, int32_t t_free,
+                   int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier, uint32_t* field, int32_t* n_frontier,
+                   void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
+  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
+      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || (weighted && !cost) || !field ||
+      !n_frontier)
+    return LIPMPC_E_ARG;
+  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
+  if (F == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const TiledCall t = tiled_call(F, W, H, false, work);
+  const TiledLayout& l = t.l;
+  if (!resume) {
+    frontier_bitmaps(s, t, F, W, H, evidence, t_free, t_occ, r_inflate, n_frontier);
+    hipLaunchKernelGGL(tiled_frontier_seed_kernel, dim3((unsigned)(F * t.chunks)), dim3(SETUP_THREADS), 0, s, W, H, t.chunks, min_unknown,
+                       t.w + l.unknown, t.w + l.blocked, frontier, field, n_frontier, t.w + l.flags0, l.tiles);
+  }
+  return tiled_rounds(s, F, W, H, t.blk_stride, l, t.w, field, max_rounds, settled, weighted ? cost : nullptr, t.ncells);
 }
 
 }  // namespace
@@ -1842,53 +2000,16 @@ extern "C" int lipmpc_grid_field_tiled_batch(int device, int64_t F, int32_t W, i
                                              const double* cell, const uint8_t* occ, const double* goal, int32_t r_inflate,
                                              uint32_t* field, int32_t* field_status, void* work, int64_t work_bytes, int32_t max_rounds,
                                              int32_t resume, int32_t* settled, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
-    return LIPMPC_E_ARG;
-  if (!occ || !goal || !field || !field_status) return LIPMPC_E_ARG;
-  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
-  if (F == 0) return LIPMPC_OK;
-  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const TiledLayout l = tiled_layout(F, W, H);
-  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  const int64_t maps = grid_shared ? 1 : F, blk_stride = grid_shared ? 0 : l.bm_words;
-  uint32_t* w = (uint32_t*)work;
-  if (!resume) {
-    hipLaunchKernelGGL(tiled_bitmaps_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles, occ,
-                       (const int32_t*)nullptr, 0, 0, w + l.solid, w + l.unknown, w + l.flags0, (int32_t*)nullptr);
-    hipLaunchKernelGGL(tiled_blocked_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
-                       w + l.solid, w + l.unknown, w + l.blocked);
-    hipLaunchKernelGGL(tiled_goal_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, blk_stride, ox, oy, dx,
-                       dy, goal, w + l.blocked, field, field_status, w + l.flags0, l.tiles);
-  }
-  return tiled_rounds(s, F, W, H, blk_stride, l, w, field, max_rounds, settled);
+  return goal_field(device, F, W, H, grid_shared, origin, cell, occ, false, nullptr, goal, r_inflate, field, field_status, work, work_bytes,
+                    max_rounds, resume, settled, hip_stream);
 }
 
 extern "C" int lipmpc_grid_frontier_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
                                                       int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier,
                                                       uint32_t* field, int32_t* n_frontier, void* work, int64_t work_bytes,
                                                       int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
-      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || !field || !n_frontier)
-    return LIPMPC_E_ARG;
-  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
-  if (F == 0) return LIPMPC_OK;
-  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const TiledLayout l = tiled_layout(F, W, H);
-  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  uint32_t* w = (uint32_t*)work;
-  if (!resume) {
-    hipLaunchKernelGGL(tiled_bitmaps_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles,
-                       (const uint8_t*)nullptr, evidence, t_free, t_occ, w + l.solid, w + l.unknown, w + l.flags0, n_frontier);
-    hipLaunchKernelGGL(tiled_blocked_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
-                       w + l.solid, w + l.unknown, w + l.blocked);
-    hipLaunchKernelGGL(tiled_frontier_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, min_unknown,
-                       w + l.unknown, w + l.blocked, frontier, field, n_frontier, w + l.flags0, l.tiles);
-  }
-  return tiled_rounds(s, F, W, H, l.bm_words, l, w, field, max_rounds, settled);
+  return frontier_field(device, F, W, H, evidence, false, nullptr, t_free, t_occ, r_inflate, min_unknown, frontier, field, n_frontier, work,
+                        work_bytes, max_rounds, resume, settled, hip_stream);
 }
 
 extern "C" int lipmpc_grid_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell,
@@ -1897,17 +2018,15 @@ extern "C" int lipmpc_grid_path_tiled_batch(int device, int64_t B, int64_t F, in
                                             int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status,
                                             double* path_cost, void* hip_stream) {
   if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
-    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (!occ || !field || !field_status || !settled || !goal || !start || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(tiled_goal_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, ox, oy, dx, dy, occ, field,
-                     field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1],
+                     cell[0], cell[1], occ, field, field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
+                     path_cost);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
@@ -1917,18 +2036,15 @@ extern "C" int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int6
                                                      int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                                      int32_t* status, double* path_cost, int32_t* target_cell, void* hip_stream) {
   if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
-    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (!evidence || !field || !n_frontier || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell)
     return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(tiled_frontier_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, ox, oy, dx, dy, evidence, t_occ, field, n_frontier, settled, start,
-                     r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, field,
+                     n_frontier, settled, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
@@ -2116,20 +2232,26 @@ __global__ void __launch_bounds__(PATH_THREADS) tile_utility_descent_kernel(
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the coordinated claim by tiles (lipmpc_grid_frontier_assign_tiled_batch): assign_body's rounds cut into kernels, every field_k
-// relaxed by tiled_round_kernel.  The workspace: CLAIM_CTL control words, the impassable and the source bitmap, the two flag
-// arrays, then field_k.
+// relaxed by tiled_round_kernel.  The workspace: the control words, the impassable and the source bitmap, the two flag arrays, then
+// field_k.
+// CLAIM HYSTERESIS by tiles (lipmpc_grid_frontier_assign_keep_tiled_batch): per SLOT a mode kernel decides whose the slot is -- the
+// next keep candidate that has an anchor, else a greedy round -- and the KEEP forms of the bodies below read the mode.  The
+// workspace has KEEP_CTL control words in place of CLAIM_CTL; k is the control word CTL_CLAIMS, not the host's slot index.
+// Every kernel of the two calls but the set-up and the mode is a body<KEEP> behind a claim_ and a keep_ wrapper.
 constexpr int CLAIM_CTL = 8;                          // words 0, 1: the key (64 bits, 8-byte aligned as `work` is); then:
 constexpr int CTL_TARGET = 2, CTL_STOPPED = 3, CTL_CLAIMS = 4, CTL_UNSETTLED = 5, CTL_ROUND_SETTLED = 6, CTL_ANY_SOURCE = 7;
+constexpr int KEEP_CTL = 16;
+constexpr int CTL_MODE = 8, CTL_ROBOT = 9, CTL_ANCHOR = 10, CTL_CURSOR = 11, CTL_KEPT = 12;      // MODE: 1 = a keep slot, 0 = a greedy round
 constexpr int64_t CLAIM_MAX_LAUNCHES = 1 << 20;       // max_claims * max_rounds of one call
 
 struct ClaimLayout {
   int64_t bm_words, tiles, blocked, sources, flags0, flags1, field, words;
 };
-inline ClaimLayout claim_layout(int64_t W, int64_t H) {
+inline ClaimLayout claim_layout(int64_t W, int64_t H, int64_t ctl_words) {
   ClaimLayout l;
   l.bm_words = bitmap_words(W * H);
   l.tiles = (int64_t)tiles_along((int)W, TILE_W) * tiles_along((int)H, TILE_H);
-  l.blocked = CLAIM_CTL;
+  l.blocked = ctl_words;
   l.sources = l.blocked + l.bm_words;
   l.flags0 = l.sources + l.bm_words;
   l.flags1 = l.flags0 + l.tiles;
@@ -2137,7 +2259,7 @@ inline ClaimLayout claim_layout(int64_t W, int64_t H) {
   l.words = l.field + W * H;
   return l;
 }
-inline int64_t claim_bytes(int64_t W, int64_t H) { return 4 * claim_layout(W, H).words + 256; }
+inline int64_t claim_bytes(int64_t W, int64_t H, int64_t ctl_words) { return 4 * claim_layout(W, H, ctl_words).words + 256; }
 
 // once per call, over cells: impassable = the given field is INF, sources = the given frontier on passable cells, both by
 // ballots; both flag arrays cleared; the control words.  With max_claims == 0 or an unsettled given field the call is stopped
@@ -2175,13 +2297,17 @@ __global__ void __launch_bounds__(SETUP_THREADS) claim_setup_kernel(int ncells, 
   for (int64_t k = (int64_t)blockIdx.x * SETUP_THREADS + tid; k < total; k += step) flags[k] = 0;
 }
 
-// once per call, over robots: U_0 as assign_body encodes it, claim_round[b] = -2 - (start cell), -1 for everyone else
-__global__ void __launch_bounds__(SETUP_THREADS) claim_robots_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
-                                                                     const double* __restrict__ start,
-                                                                     const int8_t* __restrict__ may_claim, int max_claims,
-                                                                     const int32_t* __restrict__ status,
-                                                                     int32_t* __restrict__ claim_round) {
+// once per call, over robots: U_0 as assign_body encodes it, claim_round[b] = -2 - (start cell), -1 for everyone else.  KEEP:
+// nobody has kept anything, and the keep control words.
+template <bool KEEP>
+__device__ __forceinline__ void claim_robots_body(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
+                                                  const double* __restrict__ start, const int8_t* __restrict__ may_claim, int max_claims,
+                                                  const int32_t* __restrict__ status, int32_t* __restrict__ claim_round,
+                                                  int8_t* __restrict__ kept, uint32_t* __restrict__ ctl) {
   const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  if constexpr (KEEP) {
+    if (b == 0) { ctl[CTL_MODE] = 0; ctl[CTL_ROBOT] = 0; ctl[CTL_ANCHOR] = INF; ctl[CTL_CURSOR] = 0; ctl[CTL_KEPT] = 0; }
+  }
   if (b >= B) return;
   const int sb = status[b];
   int si = 0, sj = 0, v = -1;
@@ -2189,148 +2315,20 @@ __global__ void __launch_bounds__(SETUP_THREADS) claim_robots_kernel(int64_t B, 
       cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
     v = -2 - (si * H + sj);
   claim_round[b] = v;
+  if constexpr (KEEP) kept[b] = 0;
 }
 
-// the claim seed, blockIdx.x = tile: field_k = 0 on what is left of the sources and INF elsewhere on the tile's cells; the tile's
-// flag of the first round = some source among its cells or in its halo (what flag_round_seed sets), its flag of the second
-// array 0 -- each flag word has one writer, so nothing is cleared under another workgroup's hands
-__global__ void __launch_bounds__(TILE_THREADS) claim_seed_kernel(int W, int H, int tiles_j, uint32_t* __restrict__ ctl,
-                                                                  const uint32_t* __restrict__ src, uint32_t* __restrict__ field_k,
-                                                                  uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
-  if (ld_agent(ctl + CTL_STOPPED)) return;              // (both flag arrays are clear: whoever stopped the call cleared them)
-  const int tile = blockIdx.x, tid = threadIdx.x;
-  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
-  int own = 0, near = 0;
-  for (int l = tid; l < HALO_CELLS; l += TILE_THREADS) {
-    const int li = l / HALO_H, lj = l - li * HALO_H, i = i0 + li - 1, j = j0 + lj - 1;
-    if ((unsigned)i >= (unsigned)W || (unsigned)j >= (unsigned)H) continue;
-    const bool s = bit_of(src, i * H + j);
-    const bool inner = li >= 1 && li <= TILE_W && lj >= 1 && lj <= TILE_H;
-    if (inner) field_k[i * H + j] = s ? 0u : INF;
-    own |= s & inner;
-    near |= s;
-  }
-  near = __syncthreads_or(near);
-  if (tid == 0) { flags0[tile] = near != 0; flags1[tile] = 0; }
-  if (own) st_agent(ctl + CTL_ANY_SOURCE, 1u);
+__global__ void __launch_bounds__(SETUP_THREADS) claim_robots_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const double* __restrict__ start,
+    const int8_t* __restrict__ may_claim, int max_claims, const int32_t* __restrict__ status, int32_t* __restrict__ claim_round) {
+  claim_robots_body<false>(B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round, nullptr, nullptr);
 }
 
-// the pick, over robots: the least (cost << 32 | b) among the candidates of U_k, by a wave reduction and a 64-bit atomicMin.
-// Every workgroup finds the same answer to "are the rounds over" from words that earlier kernels wrote.
-__global__ void __launch_bounds__(SETUP_THREADS) claim_pick_kernel(int64_t B, int W, int H, int r_inflate, uint32_t* ctl,
-                                                                   const uint32_t* field_k, const int32_t* __restrict__ claim_round) {
-  if (ld_agent(ctl + CTL_STOPPED)) return;
-  const bool no_source = ld_agent(ctl + CTL_ANY_SOURCE) == 0, unsettled = ld_agent(ctl + CTL_ROUND_SETTLED) == 0;
-  if (no_source || unsettled) return;                   // (the claim kernel stops the call: it reads the same two words)
-  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
-  unsigned long long mine = ~0ull;
-  if (b < B) {
-    const int v = claim_round[b];
-    if (v <= -2) {
-      const int s = claim_cell(field_k, W, H, -2 - v, r_inflate);
-      if (s >= 0) mine = ((unsigned long long)ld(field_k + s) << 32) | (unsigned long long)b;
-    }
-  }
-  for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
-  if ((threadIdx.x & 63) == 0 && mine != ~0ull) atomicMin((unsigned long long*)ctl, mine);
-}
-
-// the claim, ONE workgroup: one lane walks the winner's path down field_k and writes its rows and claim_round; then everybody
-// clears the disc from the source bitmap.  Whatever happened, the kernel leaves both flag arrays clear, the key reset and the
-// "any source" word 0 for the next round's seed.
-__global__ void __launch_bounds__(FIELD_THREADS) claim_take_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
-                                                                   int r_inflate, int r_claim, int max_seg, int S_max, int k, int tiles,
-                                                                   uint32_t* ctl, uint32_t* src, const uint32_t* field_k, uint32_t* flags,
-                                                                   double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
-                                                                   int32_t* target_cell, int32_t* claim_round) {
-  const int tid = threadIdx.x;
-  const bool stopped = ctl[CTL_STOPPED] != 0, no_source = ctl[CTL_ANY_SOURCE] == 0, unsettled = ctl[CTL_ROUND_SETTLED] == 0;
-  const unsigned long long win = *(const unsigned long long*)ctl;
-  __syncthreads();                                      // (everybody has read the control words)
-  for (int t = tid; t < 2 * tiles; t += FIELD_THREADS) flags[t] = 0;
-  if (tid == 0) { ctl[0] = ctl[1] = INF; ctl[CTL_ANY_SOURCE] = 0; ctl[CTL_ROUND_SETTLED] = 1; }
-  if (stopped) return;
-  if (no_source || unsettled || win == ~0ull) {         // no source left, a field that did not settle, no candidate
-    if (tid == 0) { ctl[CTL_STOPPED] = 1; if (!no_source && unsettled) ctl[CTL_UNSETTLED] = 1; }
-    return;
-  }
-  const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
-  if (tid == 0) {
-    // one lane walks the winner's path, twice: count, then -- if the sub-goals fit -- write (rows past n_sub stay untouched)
-    const int s = claim_cell(field_k, W, H, -2 - claim_round[wb], r_inflate);
-    double* sg = sub_goals + wb * (int64_t)S_max * 2;
-    int last_cell = s, n = 0;
-    for (int pass = 0; pass < 2 && n >= 0 && n <= S_max; ++pass)
-      n = walk_in(field_k, W, H, s, max_seg, ox, oy, dx, dy, pass ? sg : nullptr, last_cell);
-    if (n > 0) {
-      if (n <= S_max) centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
-      status[wb] = n <= S_max ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
-      n_sub[wb] = n <= S_max ? n : 0;
-      path_cost[wb] = (double)ld(field_k + s) / 5.0;
-      target_cell[wb] = last_cell;
-      claim_round[wb] = k;
-      ctl[CTL_CLAIMS] = (uint32_t)(k + 1);
-    }
-    ctl[CTL_TARGET] = n > 0 ? (uint32_t)last_cell : INF;  // (a fixed point always has a descent: INF cannot happen)
-  }
-  __syncthreads();
-  const uint32_t t = ctl[CTL_TARGET];
-  int eligible = 0;
-  for (int64_t b = tid; b < B; b += FIELD_THREADS) eligible |= claim_round[b] <= -2;
-  const int more = __syncthreads_or(eligible);
-  if (t == INF || !more) {                              // U is used up
-    if (tid == 0) ctl[CTL_STOPPED] = 1;
-    return;
-  }
-  // S_{k+1}: the sources outside the winner's disc, clipped to the grid
-  const int ti = (int)t / H, tj = (int)t - ti * H, r2 = r_claim * r_claim;
-  const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
-  for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
-    const int i = c / H, j = c - i * H;
-    if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
-  }
-}
-
-// the last kernel, over robots: the followers (still in U), n_claims and claims_settled
-__global__ void __launch_bounds__(SETUP_THREADS) claim_finish_kernel(int64_t B, const uint32_t* __restrict__ ctl, int32_t* claim_round,
-                                                                     int32_t* __restrict__ n_claims, int32_t* __restrict__ claims_settled) {
-  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
-  if (b < B && claim_round[b] < -1) claim_round[b] = -1;
-  if (b == 0) { n_claims[0] = (int32_t)ctl[CTL_CLAIMS]; claims_settled[0] = ctl[CTL_UNSETTLED] == 0; }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// claim hysteresis by tiles (lipmpc_grid_frontier_assign_keep_tiled_batch): per SLOT a mode kernel decides whose the slot is --
-// the next keep candidate that has an anchor, else a greedy round -- and the claim kernels' siblings below read the mode.  The
-// workspace is the tiled claim call's with KEEP_CTL control words in place of CLAIM_CTL; k is the control word CTL_CLAIMS, not
-// the host's slot index.  tiled_round_kernel, tiled_settle_kernel and the kernels above are not touched.
-constexpr int KEEP_CTL = 16;
-constexpr int CTL_MODE = 8, CTL_ROBOT = 9, CTL_ANCHOR = 10, CTL_CURSOR = 11, CTL_KEPT = 12;      // MODE: 1 = a keep slot, 0 = a greedy round
-
-inline ClaimLayout keep_claim_layout(int64_t W, int64_t H) {
-  ClaimLayout l = claim_layout(W, H);
-  const int64_t more = KEEP_CTL - CLAIM_CTL;
-  l.blocked += more; l.sources += more; l.flags0 += more; l.flags1 += more; l.field += more; l.words += more;
-  return l;
-}
-inline int64_t keep_claim_bytes(int64_t W, int64_t H) { return 4 * keep_claim_layout(W, H).words + 256; }
-
-// once per call, over robots: claim_robots_kernel's U_0, nobody has kept anything, and the keep control words
-__global__ void __launch_bounds__(SETUP_THREADS) keep_robots_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
-                                                                    const double* __restrict__ start,
-                                                                    const int8_t* __restrict__ may_claim, int max_claims,
-                                                                    const int32_t* __restrict__ status, int32_t* __restrict__ claim_round,
-                                                                    int8_t* __restrict__ kept, uint32_t* __restrict__ ctl) {
-  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
-  if (b == 0) { ctl[CTL_MODE] = 0; ctl[CTL_ROBOT] = 0; ctl[CTL_ANCHOR] = INF; ctl[CTL_CURSOR] = 0; ctl[CTL_KEPT] = 0; }
-  if (b >= B) return;
-  const int sb = status[b];
-  int si = 0, sj = 0, v = -1;
-  if (max_claims > 0 && (sb == LIPMPC_RRT_FOUND || sb == LIPMPC_RRT_PATH_OVERFLOW) && (!may_claim || may_claim[b]) &&
-      cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
-    v = -2 - (si * H + sj);
-  claim_round[b] = v;
-  kept[b] = 0;
+__global__ void __launch_bounds__(SETUP_THREADS) keep_robots_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const double* __restrict__ start,
+    const int8_t* __restrict__ may_claim, int max_claims, const int32_t* __restrict__ status, int32_t* __restrict__ claim_round,
+    int8_t* __restrict__ kept, uint32_t* __restrict__ ctl) {
+  claim_robots_body<true>(B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round, kept, ctl);
 }
 
 // the mode of the next slot, ONE workgroup: from the cursor on, the first robot of U with a previous target that has an anchor in
@@ -2374,13 +2372,21 @@ __global__ void __launch_bounds__(FIELD_THREADS) keep_mode_kernel(int64_t B, int
   if (tid == 0) { ctl[CTL_MODE] = 0; ctl[CTL_ANCHOR] = INF; ctl[CTL_CURSOR] = (uint32_t)B; }
 }
 
-// claim_seed_kernel with the mode: a keep slot's only source is the anchor
-__global__ void __launch_bounds__(TILE_THREADS) keep_seed_kernel(int W, int H, int tiles_j, uint32_t* __restrict__ ctl,
-                                                                 const uint32_t* __restrict__ src, uint32_t* __restrict__ field_k,
-                                                                 uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
+// the claim seed, blockIdx.x = tile: field_k = 0 on what is left of the sources and INF elsewhere on the tile's cells; the tile's
+// flag of the first round = some source among its cells or in its halo (what flag_round_seed sets), its flag of the second
+// array 0 -- each flag word has one writer, so nothing is cleared under another workgroup's hands.  KEEP: a keep slot's only
+// source is the anchor.
+template <bool KEEP>
+__device__ __forceinline__ void claim_seed_body(int W, int H, int tiles_j, uint32_t* __restrict__ ctl, const uint32_t* __restrict__ src,
+                                                uint32_t* __restrict__ field_k, uint32_t* __restrict__ flags0,
+                                                uint32_t* __restrict__ flags1) {
   if (ld_agent(ctl + CTL_STOPPED)) return;              // (both flag arrays are clear: whoever stopped the call cleared them)
-  const bool keep = ld_agent(ctl + CTL_MODE) != 0;
-  const int anchor = (int)ld_agent(ctl + CTL_ANCHOR);
+  bool keep = false;
+  int anchor = 0;
+  if constexpr (KEEP) {
+    keep = ld_agent(ctl + CTL_MODE) != 0;
+    anchor = (int)ld_agent(ctl + CTL_ANCHOR);
+  }
   const int tile = blockIdx.x, tid = threadIdx.x;
   const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
   int own = 0, near = 0;
@@ -2398,14 +2404,33 @@ __global__ void __launch_bounds__(TILE_THREADS) keep_seed_kernel(int W, int H, i
   if (own) st_agent(ctl + CTL_ANY_SOURCE, 1u);
 }
 
-// claim_pick_kernel with the mode: in a keep slot the slot's robot is the only candidate
-__global__ void __launch_bounds__(SETUP_THREADS) keep_pick_kernel(int64_t B, int W, int H, int r_inflate, uint32_t* ctl,
-                                                                  const uint32_t* field_k, const int32_t* __restrict__ claim_round) {
+__global__ void __launch_bounds__(TILE_THREADS) claim_seed_kernel(
+    int W, int H, int tiles_j, uint32_t* __restrict__ ctl, const uint32_t* __restrict__ src, uint32_t* __restrict__ field_k,
+    uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
+  claim_seed_body<false>(W, H, tiles_j, ctl, src, field_k, flags0, flags1);
+}
+
+__global__ void __launch_bounds__(TILE_THREADS) keep_seed_kernel(
+    int W, int H, int tiles_j, uint32_t* __restrict__ ctl, const uint32_t* __restrict__ src, uint32_t* __restrict__ field_k,
+    uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
+  claim_seed_body<true>(W, H, tiles_j, ctl, src, field_k, flags0, flags1);
+}
+
+// the pick, over robots: the least (cost << 32 | b) among the candidates of U_k, by a wave reduction and a 64-bit atomicMin.
+// Every workgroup finds the same answer to "are the rounds over" from words that earlier kernels wrote.  KEEP: in a keep slot the
+// slot's robot is the only candidate.
+template <bool KEEP>
+__device__ __forceinline__ void claim_pick_body(int64_t B, int W, int H, int r_inflate, uint32_t* ctl, const uint32_t* field_k,
+                                                const int32_t* __restrict__ claim_round) {
   if (ld_agent(ctl + CTL_STOPPED)) return;
   const bool no_source = ld_agent(ctl + CTL_ANY_SOURCE) == 0, unsettled = ld_agent(ctl + CTL_ROUND_SETTLED) == 0;
-  if (no_source || unsettled) return;
-  const bool keep = ld_agent(ctl + CTL_MODE) != 0;
-  const int64_t only = ld_agent(ctl + CTL_ROBOT);
+  if (no_source || unsettled) return;                   // (the claim kernel stops the call: it reads the same two words)
+  bool keep = false;
+  int64_t only = 0;
+  if constexpr (KEEP) {
+    keep = ld_agent(ctl + CTL_MODE) != 0;
+    only = ld_agent(ctl + CTL_ROBOT);
+  }
   const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
   unsigned long long mine = ~0ull;
   if (b < B && (!keep || b == only)) {
@@ -2419,23 +2444,38 @@ __global__ void __launch_bounds__(SETUP_THREADS) keep_pick_kernel(int64_t B, int
   if ((threadIdx.x & 63) == 0 && mine != ~0ull) atomicMin((unsigned long long*)ctl, mine);
 }
 
-// claim_take_kernel with the mode, ONE workgroup: a keeper has to pass the test before its rows are written; a keep slot whose
-// robot has no entry or fails the test ends without a winner and without stopping the call.  k is the control word.
-__global__ void __launch_bounds__(FIELD_THREADS) keep_take_kernel(int64_t B, int W, int H, double ox, double oy, double dx, double dy,
-                                                                  int r_inflate, int r_claim, int keep_ratio16, int keep_slack, int max_seg,
-                                                                  int S_max, int tiles, uint32_t* ctl, uint32_t* src,
-                                                                  const uint32_t* field_k, const uint32_t* __restrict__ field,
-                                                                  uint32_t* flags, double* sub_goals, int32_t* n_sub, int32_t* status,
-                                                                  double* path_cost, int32_t* target_cell, int32_t* claim_round,
-                                                                  int8_t* kept) {
+__global__ void __launch_bounds__(SETUP_THREADS) claim_pick_kernel(
+    int64_t B, int W, int H, int r_inflate, uint32_t* ctl, const uint32_t* field_k, const int32_t* __restrict__ claim_round) {
+  claim_pick_body<false>(B, W, H, r_inflate, ctl, field_k, claim_round);
+}
+
+__global__ void __launch_bounds__(SETUP_THREADS) keep_pick_kernel(
+    int64_t B, int W, int H, int r_inflate, uint32_t* ctl, const uint32_t* field_k, const int32_t* __restrict__ claim_round) {
+  claim_pick_body<true>(B, W, H, r_inflate, ctl, field_k, claim_round);
+}
+
+// the claim, ONE workgroup: one lane walks the winner's path down field_k and writes its rows and claim_round; then everybody
+// clears the disc from the source bitmap.  Whatever happened, the kernel leaves both flag arrays clear, the key reset and the
+// "any source" word 0 for the next round's seed.  `slot`: k, the round's number, without KEEP.
+// KEEP: k is the control word; a keeper has to pass the test before its rows are written; a keep slot whose robot has no entry or
+// fails the test ends without a winner and without stopping the call.
+template <bool KEEP>
+__device__ __forceinline__ void claim_take_body(int64_t B, int W, int H, double ox, double oy, double dx, double dy, int r_inflate,
+                                                int r_claim, int keep_ratio16, int keep_slack, int max_seg, int S_max, int slot, int tiles,
+                                                uint32_t* ctl, uint32_t* src, const uint32_t* field_k, const uint32_t* __restrict__ field,
+                                                uint32_t* flags, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                                int32_t* target_cell, int32_t* claim_round, int8_t* kept) {
   const int tid = threadIdx.x;
   const bool stopped = ctl[CTL_STOPPED] != 0, no_source = ctl[CTL_ANY_SOURCE] == 0, unsettled = ctl[CTL_ROUND_SETTLED] == 0;
-  const bool keep = ctl[CTL_MODE] != 0;
-  const int k = (int)ctl[CTL_CLAIMS];
+  const bool keep = KEEP && ctl[CTL_MODE] != 0;
+  const int k = KEEP ? (int)ctl[CTL_CLAIMS] : slot;
   const unsigned long long win = *(const unsigned long long*)ctl;
   __syncthreads();                                      // (everybody has read the control words)
   for (int t = tid; t < 2 * tiles; t += FIELD_THREADS) flags[t] = 0;
-  if (tid == 0) { ctl[0] = ctl[1] = INF; ctl[CTL_ANY_SOURCE] = 0; ctl[CTL_ROUND_SETTLED] = 1; ctl[CTL_TARGET] = INF; }
+  if (tid == 0) {
+    ctl[0] = ctl[1] = INF; ctl[CTL_ANY_SOURCE] = 0; ctl[CTL_ROUND_SETTLED] = 1;
+    if constexpr (KEEP) ctl[CTL_TARGET] = INF;          // (without KEEP lane 0 writes the word below, whatever happens)
+  }
   if (stopped) return;
   if (no_source || unsettled || (win == ~0ull && !keep)) {      // no source left, a field that did not settle, no candidate
     if (tid == 0) { ctl[CTL_STOPPED] = 1; if (!no_source && unsettled) ctl[CTL_UNSETTLED] = 1; }
@@ -2443,34 +2483,33 @@ __global__ void __launch_bounds__(FIELD_THREADS) keep_take_kernel(int64_t B, int
   }
   if (win == ~0ull) return;                             // a keep slot whose anchor is out of the robot's reach: spent, nothing else
   const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
-  __syncthreads();                                      // (lane 0's reset of the target word comes before its new value)
+  if constexpr (KEEP) __syncthreads();                  // (lane 0's reset of the target word comes before its new value)
   if (tid == 0) {
+    // one lane walks the winner's path, twice: count, then -- if the sub-goals fit -- write (rows past n_sub stay untouched)
     const int cell = -2 - claim_round[wb];
     const int s = claim_cell(field_k, W, H, cell, r_inflate);
-    bool ok = s >= 0;
+    bool ok = s >= 0;                                   // (the pick found the winner's entry in the same words)
     if (keep) ok = keep_passes(field_k, field, W, H, cell, s, r_inflate, (uint32_t)keep_ratio16, (uint32_t)keep_slack);
-    if (ok) {
-      double* sg = sub_goals + wb * (int64_t)S_max * 2;
-      int last_cell = s, n = 0;
-      for (int pass = 0; pass < 2 && n >= 0 && n <= S_max; ++pass)
-        n = walk_in(field_k, W, H, s, max_seg, ox, oy, dx, dy, pass ? sg : nullptr, last_cell);
-      if (n > 0) {
-        if (n <= S_max) centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
-        status[wb] = n <= S_max ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
-        n_sub[wb] = n <= S_max ? n : 0;
-        path_cost[wb] = (double)ld(field_k + s) / 5.0;
-        target_cell[wb] = last_cell;
-        claim_round[wb] = k;
-        ctl[CTL_CLAIMS] = (uint32_t)(k + 1);
-        if (keep) { kept[wb] = 1; ctl[CTL_KEPT] += 1; }
-        ctl[CTL_TARGET] = (uint32_t)last_cell;
-      }
+    double* sg = sub_goals + wb * (int64_t)S_max * 2;
+    int last_cell = s, n = 0;
+    for (int pass = 0; ok && pass < 2 && n >= 0 && n <= S_max; ++pass)
+      n = walk_in(field_k, W, H, s, max_seg, ox, oy, dx, dy, pass ? sg : nullptr, last_cell);
+    if (n > 0) {
+      if (n <= S_max) centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
+      status[wb] = n <= S_max ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+      n_sub[wb] = n <= S_max ? n : 0;
+      path_cost[wb] = (double)ld(field_k + s) / 5.0;
+      target_cell[wb] = last_cell;
+      claim_round[wb] = k;
+      ctl[CTL_CLAIMS] = (uint32_t)(k + 1);
+      if (keep) { kept[wb] = 1; ctl[CTL_KEPT] += 1; }
     }
+    if (!KEEP || n > 0) ctl[CTL_TARGET] = n > 0 ? (uint32_t)last_cell : INF;
   }
   __syncthreads();
   const uint32_t t = ctl[CTL_TARGET];
-  if (t == INF) {                                       // a keeper that failed the test stays in U; (a winner always has a descent)
-    if (tid == 0 && !keep) ctl[CTL_STOPPED] = 1;
+  if (t == INF) {                                       // a keeper that failed the test stays in U; (a winner always has a descent:
+    if (tid == 0 && !keep) ctl[CTL_STOPPED] = 1;        // a greedy round without one stops the call, as "U is used up" does)
     return;
   }
   int eligible = 0;
@@ -2480,6 +2519,7 @@ __global__ void __launch_bounds__(FIELD_THREADS) keep_take_kernel(int64_t B, int
     if (tid == 0) ctl[CTL_STOPPED] = 1;
     return;
   }
+  // S_{k+1}: the sources outside the winner's disc, clipped to the grid
   const int ti = (int)t / H, tj = (int)t - ti * H, r2 = r_claim * r_claim;
   const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
   for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
@@ -2488,20 +2528,47 @@ __global__ void __launch_bounds__(FIELD_THREADS) keep_take_kernel(int64_t B, int
   }
 }
 
-// the last kernel, over robots: claim_finish_kernel's outputs and n_kept
-__global__ void __launch_bounds__(SETUP_THREADS) keep_finish_kernel(int64_t B, const uint32_t* __restrict__ ctl, int32_t* claim_round,
-                                                                    int32_t* __restrict__ n_claims, int32_t* __restrict__ n_kept,
-                                                                    int32_t* __restrict__ claims_settled) {
-  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
-  if (b < B && claim_round[b] < -1) claim_round[b] = -1;
-  if (b == 0) { n_claims[0] = (int32_t)ctl[CTL_CLAIMS]; n_kept[0] = (int32_t)ctl[CTL_KEPT]; claims_settled[0] = ctl[CTL_UNSETTLED] == 0; }
+__global__ void __launch_bounds__(FIELD_THREADS) claim_take_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, int r_inflate, int r_claim, int max_seg, int S_max, int k,
+    int tiles, uint32_t* ctl, uint32_t* src, const uint32_t* field_k, uint32_t* flags, double* sub_goals, int32_t* n_sub, int32_t* status,
+    double* path_cost, int32_t* target_cell, int32_t* claim_round) {
+  claim_take_body<false>(B, W, H, ox, oy, dx, dy, r_inflate, r_claim, 0, 0, max_seg, S_max, k, tiles, ctl, src, field_k, nullptr, flags,
+                         sub_goals, n_sub, status, path_cost, target_cell, claim_round, nullptr);
 }
 
-// E_ARG of a grid's placement
-bool bad_placement(const double* origin, const double* cell) {
-  if (!origin || !cell) return true;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  return !(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY);
+__global__ void __launch_bounds__(FIELD_THREADS) keep_take_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, int r_inflate, int r_claim, int keep_ratio16, int keep_slack,
+    int max_seg, int S_max, int tiles, uint32_t* ctl, uint32_t* src, const uint32_t* field_k, const uint32_t* __restrict__ field,
+    uint32_t* flags, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
+    int8_t* kept) {
+  claim_take_body<true>(B, W, H, ox, oy, dx, dy, r_inflate, r_claim, keep_ratio16, keep_slack, max_seg, S_max, 0, tiles, ctl, src, field_k,
+                        field, flags, sub_goals, n_sub, status, path_cost, target_cell, claim_round, kept);
+}
+
+// the last kernel, over robots: the followers (still in U), n_claims and claims_settled; KEEP: and n_kept
+template <bool KEEP>
+__device__ __forceinline__ void claim_finish_body(int64_t B, const uint32_t* __restrict__ ctl, int32_t* claim_round,
+                                                  int32_t* __restrict__ n_claims, int32_t* __restrict__ n_kept,
+                                                  int32_t* __restrict__ claims_settled) {
+  const int64_t b = (int64_t)blockIdx.x * SETUP_THREADS + threadIdx.x;
+  if (b < B && claim_round[b] < -1) claim_round[b] = -1;
+  if (b == 0) {
+    n_claims[0] = (int32_t)ctl[CTL_CLAIMS];
+    if constexpr (KEEP) n_kept[0] = (int32_t)ctl[CTL_KEPT];
+    claims_settled[0] = ctl[CTL_UNSETTLED] == 0;
+  }
+}
+
+__global__ void __launch_bounds__(SETUP_THREADS) claim_finish_kernel(
+    int64_t B, const uint32_t* __restrict__ ctl, int32_t* claim_round, int32_t* __restrict__ n_claims,
+    int32_t* __restrict__ claims_settled) {
+  claim_finish_body<false>(B, ctl, claim_round, n_claims, nullptr, claims_settled);
+}
+
+__global__ void __launch_bounds__(SETUP_THREADS) keep_finish_kernel(
+    int64_t B, const uint32_t* __restrict__ ctl, int32_t* claim_round, int32_t* __restrict__ n_claims, int32_t* __restrict__ n_kept,
+    int32_t* __restrict__ claims_settled) {
+  claim_finish_body<true>(B, ctl, claim_round, n_claims, n_kept, claims_settled);
 }
 
 }  // namespace
@@ -2539,18 +2606,14 @@ extern "C" int lipmpc_grid_frontier_utility_field_tiled_batch(int device, int64_
   if (F == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
-  const TiledLayout l = tiled_layout(F, W, H);
-  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  uint32_t* w = (uint32_t*)work;
+  const TiledCall t = tiled_call(F, W, H, false, work);
+  const TiledLayout& l = t.l;
   if (!resume) {
-    hipLaunchKernelGGL(tiled_bitmaps_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles,
-                       (const uint8_t*)nullptr, evidence, t_free, t_occ, w + l.solid, w + l.unknown, w + l.flags0, n_sources);
-    hipLaunchKernelGGL(tiled_blocked_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
-                       w + l.solid, w + l.unknown, w + l.blocked);
-    hipLaunchKernelGGL(tile_utility_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, w + l.blocked,
-                       frontier, gain, w_gain, g_cap, min_gain, ufield, n_sources, w + l.flags0, l.tiles);
+    frontier_bitmaps(s, t, F, W, H, evidence, t_free, t_occ, r_inflate, n_sources);
+    hipLaunchKernelGGL(tile_utility_seed_kernel, dim3((unsigned)(F * t.chunks)), dim3(SETUP_THREADS), 0, s, W, H, t.chunks, t.w + l.blocked,
+                       frontier, gain, w_gain, g_cap, min_gain, ufield, n_sources, t.w + l.flags0, l.tiles);
   }
-  return tiled_rounds(s, F, W, H, l.bm_words, l, w, ufield, max_rounds, settled);
+  return tiled_rounds(s, F, W, H, t.blk_stride, l, t.w, ufield, max_rounds, settled);
 }
 
 extern "C" int lipmpc_grid_frontier_utility_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -2576,10 +2639,82 @@ extern "C" int lipmpc_grid_frontier_utility_path_tiled_batch(int device, int64_t
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
+namespace {
+
+// what the keep call adds to the claim call's arguments
+struct KeepArgs {
+  const int32_t* prev_target;
+  int32_t r_keep, keep_ratio16, keep_slack;
+  int8_t* kept;
+  int32_t* n_kept;
+};
+
+// lipmpc_grid_frontier_assign_tiled_batch and, `keep` not null, lipmpc_grid_frontier_assign_keep_tiled_batch.  3 launches round
+// the slots, and per slot (the mode,) the seed, max_rounds rounds and their settle, the pick and the take:
+// max_claims * (max_rounds + 4) + 3, with the mode max_claims * (max_rounds + 5) + 3
+int claim_tiled(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell, const uint8_t* frontier,
+                const uint32_t* field, const int32_t* settled, const double* start, const int8_t* may_claim, int32_t r_inflate,
+                int32_t r_claim, int32_t max_claims, int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes, int32_t max_rounds,
+                double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                int32_t* n_claims, int32_t* claims_settled, const KeepArgs* keep, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
+      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS ||
+      (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
+    return LIPMPC_E_ARG;
+  if (keep && (keep->r_keep < 0 || keep->r_keep > R_KEEP_MAX || keep->keep_ratio16 < KEEP_RATIO_MIN || keep->keep_ratio16 > KEEP_RATIO_MAX ||
+               keep->keep_slack < 0 || keep->keep_slack > KEEP_SLACK_MAX || !keep->prev_target || !keep->kept || !keep->n_kept))
+    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  const int ctl_words = keep ? KEEP_CTL : CLAIM_CTL;
+  if (work_bytes < claim_bytes(W, H, ctl_words)) return LIPMPC_E_ARG;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const ClaimLayout c = claim_layout(W, H, ctl_words);
+  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
+  const dim3 robots((unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS)), setup(SETUP_THREADS), one(1), group(FIELD_THREADS);
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  uint32_t* w = (uint32_t*)work;
+  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
+  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
+  hipLaunchKernelGGL(claim_setup_kernel, dim3((unsigned)chunks), setup, 0, s, ncells, c.tiles, max_claims, frontier, field, settled, w,
+                     w + c.blocked, w + c.sources, w + c.flags0);
+  if (keep)
+    hipLaunchKernelGGL(keep_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round,
+                       keep->kept, w);
+  else
+    hipLaunchKernelGGL(claim_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round);
+  for (int slot = 0; slot < max_claims; ++slot) {
+    if (keep)
+      hipLaunchKernelGGL(keep_mode_kernel, one, group, 0, s, B, W, H, keep->r_keep, w, w + c.sources, claim_round, keep->prev_target);
+    hipLaunchKernelGGL(keep ? keep_seed_kernel : claim_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w,
+                       w + c.sources, w + c.field, w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
+    hipLaunchKernelGGL(keep ? keep_pick_kernel : claim_pick_kernel, robots, setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+    if (keep)
+      hipLaunchKernelGGL(keep_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, keep->keep_ratio16,
+                         keep->keep_slack, max_seg, S_max, tiles, w, w + c.sources, w + c.field, field, w + c.flags0, sub_goals, n_sub,
+                         status, path_cost, target_cell, claim_round, keep->kept);
+    else
+      hipLaunchKernelGGL(claim_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, max_seg, S_max, slot, tiles, w,
+                         w + c.sources, w + c.field, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell, claim_round);
+  }
+  if (keep)
+    hipLaunchKernelGGL(keep_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, keep->n_kept, claims_settled);
+  else
+    hipLaunchKernelGGL(claim_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, claims_settled);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+}  // namespace
+
 extern "C" int64_t lipmpc_grid_frontier_assign_tiled_workspace_bytes(int32_t W, int32_t H) {
   if (W < 2 || H < 2) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  return claim_bytes(W, H);
+  return claim_bytes(W, H, CLAIM_CTL);
 }
 
 extern "C" int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
@@ -2589,44 +2724,15 @@ extern "C" int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, in
                                                        int32_t max_rounds, double* sub_goals, int32_t* n_sub, int32_t* status,
                                                        double* path_cost, int32_t* target_cell, int32_t* claim_round, int32_t* n_claims,
                                                        int32_t* claims_settled, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
-      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS || (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
-    return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  if (work_bytes < claim_bytes(W, H)) return LIPMPC_E_ARG;
-  if (B == 0) return LIPMPC_OK;
-  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const ClaimLayout c = claim_layout(W, H);
-  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
-  const unsigned robots = (unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS);
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  uint32_t* w = (uint32_t*)work;
-  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
-  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
-  hipLaunchKernelGGL(claim_setup_kernel, dim3((unsigned)chunks), dim3(SETUP_THREADS), 0, s, ncells, c.tiles, max_claims, frontier, field,
-                     settled, w, w + c.blocked, w + c.sources, w + c.flags0);
-  hipLaunchKernelGGL(claim_robots_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims,
-                     status, claim_round);
-  for (int k = 0; k < max_claims; ++k) {
-    hipLaunchKernelGGL(claim_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, w + c.field,
-                       w + c.flags0, w + c.flags1);
-    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
-    hipLaunchKernelGGL(claim_pick_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
-    hipLaunchKernelGGL(claim_take_kernel, dim3(1), dim3(FIELD_THREADS), 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, max_seg, S_max, k,
-                       tiles, w, w + c.sources, w + c.field, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell, claim_round);
-  }
-  hipLaunchKernelGGL(claim_finish_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, w, claim_round, n_claims, claims_settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return claim_tiled(device, B, W, H, origin, cell, frontier, field, settled, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
+                     S_max, work, work_bytes, max_rounds, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims,
+                     claims_settled, nullptr, hip_stream);
 }
 
 extern "C" int64_t lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes(int32_t W, int32_t H) {
   if (W < 2 || H < 2) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  return keep_claim_bytes(W, H);
+  return claim_bytes(W, H, KEEP_CTL);
 }
 
 extern "C" int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin,
@@ -2639,68 +2745,24 @@ extern "C" int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t 
                                                             double* path_cost, int32_t* target_cell, int32_t* claim_round,
                                                             int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled,
                                                             void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
-      keep_slack > KEEP_SLACK_MAX || !frontier || !field || !settled || !start || !prev_target || !work || !sub_goals || !n_sub || !status ||
-      !path_cost || !target_cell || !claim_round || !n_claims || !kept || !n_kept || !claims_settled || ((uintptr_t)work & 7) != 0 ||
-      max_rounds < 1 || max_rounds > MAX_ROUNDS || (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
-    return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  if (work_bytes < keep_claim_bytes(W, H)) return LIPMPC_E_ARG;
-  if (B == 0) return LIPMPC_OK;
-  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const ClaimLayout c = keep_claim_layout(W, H);
-  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
-  const unsigned robots = (unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS);
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  uint32_t* w = (uint32_t*)work;
-  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
-  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
-  // 3 launches round the slots, and per slot the mode, the seed, max_rounds rounds and their settle, the pick and the take:
-  // max_claims * (max_rounds + 5) + 3
-  hipLaunchKernelGGL(claim_setup_kernel, dim3((unsigned)chunks), dim3(SETUP_THREADS), 0, s, ncells, c.tiles, max_claims, frontier, field,
-                     settled, w, w + c.blocked, w + c.sources, w + c.flags0);
-  hipLaunchKernelGGL(keep_robots_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims,
-                     status, claim_round, kept, w);
-  for (int slot = 0; slot < max_claims; ++slot) {
-    hipLaunchKernelGGL(keep_mode_kernel, dim3(1), dim3(FIELD_THREADS), 0, s, B, W, H, r_keep, w, w + c.sources, claim_round, prev_target);
-    hipLaunchKernelGGL(keep_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, w + c.field,
-                       w + c.flags0, w + c.flags1);
-    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
-    hipLaunchKernelGGL(keep_pick_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
-    hipLaunchKernelGGL(keep_take_kernel, dim3(1), dim3(FIELD_THREADS), 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, keep_ratio16,
-                       keep_slack, max_seg, S_max, tiles, w, w + c.sources, w + c.field, field, w + c.flags0, sub_goals, n_sub, status,
-                       path_cost, target_cell, claim_round, kept);
-  }
-  hipLaunchKernelGGL(keep_finish_kernel, dim3(robots), dim3(SETUP_THREADS), 0, s, B, w, claim_round, n_claims, n_kept, claims_settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  const KeepArgs keep = {prev_target, r_keep, keep_ratio16, keep_slack, kept, n_kept};
+  return claim_tiled(device, B, W, H, origin, cell, frontier, field, settled, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
+                     S_max, work, work_bytes, max_rounds, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims,
+                     claims_settled, &keep, hip_stream);
 }
 
 // =====================================================================================================================
 // SOFT CLEARANCE (lipmpc_grid_clearance_cost_batch, lipmpc_grid_field_weighted_batch, lipmpc_grid_frontier_field_weighted_batch and
 // their path calls): a byte per cell that a path pays when it LEAVES the cell, on top of the step.  The cost layer decays with the
 // distance to the nearest solid cell; the weighted fields are the tiled fields above with that byte added in the sweep, relaxed by
-// the same rounds -- set-up, seeds, flags and the settle kernel are the tiled calls' own, only the round kernel is new.
+// the same rounds -- set-up, seeds, flags and the settle kernel are the tiled calls' own, and the round is round_body's WEIGHTED form.
 //
-// WHY THE WEIGHTED ROUNDS GIVE WEIGHTED DIJKSTRA'S FIELD.  The argument of THE TILED FIELD carries over word for word; the cell
-// cost enters in ONE place: a value a cell takes is  k(c) + f(n) + step  for a legal move c -> n, which is the cost of the real
-// path "leave c, then n's path" in the metric where leaving c costs k(c) more.  Values are still path costs and still only fall,
-// so no flag set <=> a fixed point of  f(c) = k(c) + min over legal moves of f(n) + step,  f = 0 on the sources; its finite values
-// are >= the least cost (they are path costs) and <= it (induction along a least-cost path); k >= 0 is an integer, so the least
-// cost is unique and the bits are Dijkstra's.  The round guarantee's induction uses "the rest of a least-cost path is a least-cost
-// path" and "a tile relaxes to its local fixed point", both of which hold in the weighted metric.
-// NO WRAP: a stored value is the cost of a SIMPLE path (a value derived through the cell itself would be larger than the one it
-// holds), at most 2^24 - 1 moves of at most 7 + 248 each; a candidate adds one more: <= 255 * 2^24 < 2^32 - 1 = INF.
+// WHY THE WEIGHTED ROUNDS GIVE WEIGHTED DIJKSTRA'S FIELD, and why nothing wraps: in round_body, beside the line where the cost enters.
 namespace {
 
 constexpr int R_CLEAR_MAX = 31;                       // a disc row is at most 63 consecutive bits: one 64-bit window
 constexpr int SOFT_ROWS = TILE_W + 2 * R_CLEAR_MAX;   // 94 rows of 128 bits: the tile grown by r_clear
 static_assert(LIPMPC_COST_MAX == 248 && (7 + LIPMPC_COST_MAX) * (uint64_t)TILED_MAX_CELLS < INF, "a finite weighted value stays below INF");
-
-__device__ inline uint32_t soft_k(const uint8_t* __restrict__ cost, int c) { return min((uint32_t)cost[c], (uint32_t)LIPMPC_COST_MAX); }
 
 // THE COST LAYER.  blockIdx.x = map * tiles + tile; a thread owns the round kernel's eight cells.  The solid bits of the tile grown
 // by r_clear go into LDS by ballot (row rr = i - (i0 - r), bit b = j - (j0 - r); a cell outside the grid is not solid); per cell
@@ -2750,99 +2812,6 @@ __global__ void __launch_bounds__(TILE_THREADS) soft_cost_kernel(int W, int H, i
       }
     }
     cost[base + (int64_t)gi * H + gj] = best <= r2 ? (uint8_t)((uint32_t)(w_clear * (r2 - best)) / (uint32_t)r2) : (uint8_t)0;
-  }
-}
-
-// ONE WEIGHTED ROUND: tiled_round_kernel with the eight cost bytes of a thread's cells in one more register, added to what a cell
-// takes.  blockIdx.x = field * tiles + tile.  A source holds 0 and never falls, so it pays nothing.
-__global__ void __launch_bounds__(TILE_THREADS) soft_round_kernel(int W, int H, int tiles_j, int tiles, int64_t blk_stride,
-                                                                  const uint32_t* __restrict__ blk, int64_t cost_stride,
-                                                                  const uint8_t* __restrict__ cost, uint32_t* field, uint32_t* cur,
-                                                                  uint32_t* next) {
-  __shared__ uint32_t lf[HALO_CELLS];                 // field words, local index l = (li + 1) * HALO_H + lj + 1
-  __shared__ uint32_t lb[HALO_PADDED / 32 + 2];       // blocked bits by l; a cell outside the grid is blocked
-  __shared__ uint32_t rim;
-  const int64_t f = blockIdx.x / tiles;
-  const int tile = blockIdx.x - (int)f * tiles, tid = threadIdx.x, lane = tid & 63;
-  uint32_t* my_flag = cur + f * tiles + tile;
-  if (ld_agent(my_flag) == 0) return;                 // (one word for the whole workgroup: uniform)
-  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
-  const uint32_t* bl = blk + f * blk_stride;
-  const uint8_t* kc = cost + f * cost_stride;
-  uint32_t* fld = field + f * (int64_t)W * H;
-
-  for (int l0 = tid - lane; l0 < HALO_PADDED; l0 += TILE_THREADS) {
-    const int l = l0 + lane, li = l / HALO_H, lj = l - li * HALO_H;
-    const int gi = i0 + li - 1, gj = j0 + lj - 1;
-    const bool in = l < HALO_CELLS && (unsigned)gi < (unsigned)W && (unsigned)gj < (unsigned)H;
-    const int gc = in ? gi * H + gj : 0;
-    const uint32_t v = ld_agent(fld + gc);
-    const uint64_t mb = __ballot(!in || bit_of(bl, gc));
-    if (l < HALO_CELLS) lf[l] = in ? v : INF;
-    if (lane == 0) { lb[l0 >> 5] = (uint32_t)mb; lb[(l0 >> 5) + 1] = (uint32_t)(mb >> 32); }
-  }
-  if (tid == 0) rim = 0;
-  __syncthreads();                                    // (everybody has read the flag: it is cleared for the round after next)
-  if (tid == 0) st_agent(my_flag, 0u);
-
-  // the legal moves of my eight cells, a byte per cell (tiled_round_kernel's), and beside them their eight cost bytes, clamped
-  const int l_first = ((tid >> 6) + 1) * HALO_H + (tid & 63) + 1;
-  auto open_at = [&](int l) { return ((lb[l >> 5] >> (l & 31)) & 1u) ^ 1u; };       // 1 = unblocked
-  uint64_t moves = 0, costs = 0;
-#pragma unroll 1
-  for (int k = 0; k < TILE_OWN; ++k) {
-    const int l = l_first + k * TILE_ROWS * HALO_H;
-    const uint32_t up = open_at(l - HALO_H), dn = open_at(l + HALO_H), lt = open_at(l - 1), rt = open_at(l + 1);
-    const uint32_t m = (open_at(l - HALO_H - 1) & up & lt) | up << 1 | (open_at(l - HALO_H + 1) & up & rt) << 2 | lt << 3 | rt << 4 |
-                       (open_at(l + HALO_H - 1) & dn & lt) << 5 | dn << 6 | (open_at(l + HALO_H + 1) & dn & rt) << 7;
-    const uint32_t mine = m * open_at(l);
-    moves |= (uint64_t)mine << (8 * k);
-    const int gi = i0 + k * TILE_ROWS + (tid >> 6), gj = j0 + (tid & 63);            // (an unblocked cell is inside the grid)
-    if (mine) costs |= (uint64_t)soft_k(kc, gi * H + gj) << (8 * k);
-  }
-
-  // the sweeps of relax(), on my cells, the halo held
-  uint32_t fell = 0;
-  for (;;) {
-    int changed = 0;
-#pragma unroll 1
-    for (int k = 0; k < TILE_OWN; ++k) {                // (not unrolled: eight cells' lane masks at once overfill the scalar file)
-      const uint32_t m = (uint32_t)(moves >> (8 * k)) & 0xFFu;
-      if (m) {
-        const int l = l_first + k * TILE_ROWS * HALO_H;
-        auto via = [&](int bit, int off, uint32_t step) {
-          const uint32_t v = ld(lf + l + off);
-          return ((m >> bit) & 1u) && v != INF ? v + step : INF;
-        };
-        const uint32_t cur_v = ld(lf + l);
-        const uint32_t least = min(min(min(via(0, -HALO_H - 1, DIAGONAL), via(1, -HALO_H, AXIAL)), min(via(2, -HALO_H + 1, DIAGONAL), via(3, -1, AXIAL))),
-                                   min(min(via(4, 1, AXIAL), via(5, HALO_H - 1, DIAGONAL)), min(via(6, HALO_H, AXIAL), via(7, HALO_H + 1, DIAGONAL))));
-        const uint32_t best = least == INF ? INF : least + ((uint32_t)(costs >> (8 * k)) & 0xFFu);      // THE CELL COST ENTERS HERE
-        if (best < cur_v) { st(lf + l, best); changed = 1; fell |= 1u << k; }
-      }
-    }
-    if (!__syncthreads_or(changed)) break;
-  }
-
-  // write back what fell; which parts of the rim fell: bit 0 top, 1 bottom, 2 left, 3 right, 4..7 the corners
-  uint32_t r = 0;
-  const int lj = tid & 63;
-#pragma unroll
-  for (int k = 0; k < TILE_OWN; ++k)
-    if ((fell >> k) & 1u) {
-      const int li = k * TILE_ROWS + (tid >> 6);
-      st_agent(fld + (i0 + li) * H + j0 + lj, lf[l_first + k * TILE_ROWS * HALO_H]);
-      const bool top = li == 0, bot = li == TILE_W - 1, lft = lj == 0, rgt = lj == TILE_H - 1;
-      r |= (uint32_t)top | (uint32_t)bot << 1 | (uint32_t)lft << 2 | (uint32_t)rgt << 3 | (uint32_t)(top & lft) << 4 |
-           (uint32_t)(top & rgt) << 5 | (uint32_t)(bot & lft) << 6 | (uint32_t)(bot & rgt) << 7;
-    }
-  if (r) atomicOr(&rim, r);
-  __syncthreads();
-  if (tid < 8 && ((rim >> tid) & 1u)) {
-    const int di = tid == 0 || tid == 4 || tid == 5 ? -1 : tid == 1 || tid == 6 || tid == 7 ? 1 : 0;
-    const int dj = tid == 2 || tid == 4 || tid == 6 ? -1 : tid == 3 || tid == 5 || tid == 7 ? 1 : 0;
-    const int ni = ti + di, nj = tj + dj;
-    if ((unsigned)ni < (unsigned)(tiles / tiles_j) && (unsigned)nj < (unsigned)tiles_j) st_agent(next + f * tiles + ni * tiles_j + nj, 1u);
   }
 }
 
@@ -2918,98 +2887,6 @@ __device__ inline int soft_walk(const uint32_t* __restrict__ fld, const uint8_t*
   return count + 1;
 }
 
-// One lane per robot: grid_path_body's rules, the walk down the weighted field.
-__global__ void __launch_bounds__(PATH_THREADS) soft_goal_descent_kernel(int64_t B, int one_field, int W, int H, int64_t occ_stride,
-                                                                         double ox, double oy, double dx, double dy,
-                                                                         const uint8_t* __restrict__ occ, const uint8_t* __restrict__ cost,
-                                                                         const uint32_t* __restrict__ field,
-                                                                         const int32_t* __restrict__ field_status,
-                                                                         const int32_t* __restrict__ settled,
-                                                                         const double* __restrict__ goal, const double* __restrict__ start,
-                                                                         int r_inflate, int max_seg, int S_max,
-                                                                         double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
-                                                                         int32_t* __restrict__ status, double* __restrict__ path_cost) {
-  const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
-  if (b >= B) return;
-  const int64_t f = one_field ? 0 : b;
-  const int ncells = W * H;
-  const uint32_t* fld = field + f * (int64_t)ncells;
-  const uint8_t* kc = cost + f * occ_stride;             // (the layer is shared exactly when the map is)
-  auto done = [&](int st_, int n, double c) { status[b] = st_; n_sub[b] = n; path_cost[b] = c; };
-  const double nan = __builtin_nan("");
-  if (settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan);
-  const int fs = field_status[f];
-  if (fs == LIPMPC_FIELD_GOAL_OUTSIDE) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan);
-  if (fs == LIPMPC_FIELD_GOAL_BLOCKED) return done(LIPMPC_RRT_GOAL_OCCUPIED, 0, nan);
-  int si = 0, sj = 0;
-  if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan);
-  int s = si * H + sj;
-  if (occ[f * occ_stride + s] != 0) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan);
-  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
-  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);
-  double* sg = sub_goals + b * (int64_t)S_max * 2;
-  int last_cell;
-  const int n = soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
-  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan);                 // (a `field` that is no weighted field of this map and layer)
-  const double total = (double)fld[s] / 5.0;                          // penalties included
-  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, total);
-  soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
-  sg[2 * (n - 1)] = goal[2 * f];
-  sg[2 * (n - 1) + 1] = goal[2 * f + 1];
-  done(LIPMPC_RRT_FOUND, n, total);
-}
-
-// One lane per robot: frontier_path_body's rules, the walk down the weighted field.
-__global__ void __launch_bounds__(PATH_THREADS) soft_frontier_descent_kernel(int64_t B, int one_field, int W, int H, double ox, double oy,
-                                                                             double dx, double dy, const int32_t* __restrict__ evidence,
-                                                                             const uint8_t* __restrict__ cost, int t_occ,
-                                                                             const uint32_t* __restrict__ field,
-                                                                             const int32_t* __restrict__ n_frontier,
-                                                                             const int32_t* __restrict__ settled,
-                                                                             const double* __restrict__ start, int r_inflate, int max_seg,
-                                                                             int S_max, double* __restrict__ sub_goals,
-                                                                             int32_t* __restrict__ n_sub, int32_t* __restrict__ status,
-                                                                             double* __restrict__ path_cost,
-                                                                             int32_t* __restrict__ target_cell) {
-  const int64_t b = (int64_t)blockIdx.x * PATH_THREADS + threadIdx.x;
-  if (b >= B) return;
-  const int64_t f = one_field ? 0 : b;
-  const int ncells = W * H;
-  const uint32_t* fld = field + f * (int64_t)ncells;
-  const uint8_t* kc = cost + f * (int64_t)ncells;
-  auto done = [&](int st_, int n, double c, int target) { status[b] = st_; n_sub[b] = n; path_cost[b] = c; target_cell[b] = target; };
-  const double nan = __builtin_nan("");
-  if (settled[f] == 0) return done(LIPMPC_RRT_FIELD_UNSETTLED, 0, nan, -1);
-  int si = 0, sj = 0;
-  if (!cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj)) return done(LIPMPC_RRT_OUTSIDE_GRID, 0, nan, -1);
-  int s = si * H + sj;
-  if (evidence[f * (int64_t)ncells + s] >= t_occ) return done(LIPMPC_RRT_START_OCCUPIED, 0, nan, -1);
-  if (n_frontier[f] == 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
-  if (fld[s] == INF) s = snap(fld, W, H, si, sj, r_inflate);
-  if (s < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
-  double* sg = sub_goals + b * (int64_t)S_max * 2;
-  int last_cell;
-  const int n = soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, nullptr, last_cell);
-  if (n < 0) return done(LIPMPC_RRT_NO_PATH, 0, nan, -1);
-  const double total = (double)fld[s] / 5.0;
-  if (n > S_max) return done(LIPMPC_RRT_PATH_OVERFLOW, 0, total, last_cell);
-  soft_walk(fld, kc, W, H, s, max_seg, ox, oy, dx, dy, sg, last_cell);
-  centre(last_cell, H, ox, oy, dx, dy, sg + 2 * (n - 1));
-  done(LIPMPC_RRT_FOUND, n, total, last_cell);
-}
-
-// tiled_rounds with the weighted round kernel
-int soft_rounds(hipStream_t s, int64_t F, int W, int H, int64_t blk_stride, int64_t cost_stride, const uint8_t* cost, const TiledLayout& l,
-                uint32_t* work, uint32_t* field, int max_rounds, int32_t* settled) {
-  const int tiles = (int)l.tiles, tiles_j = tiles_along(H, TILE_H);
-  uint32_t* flags[2] = {work + l.flags0, work + l.flags1};
-  for (int r = 0; r < max_rounds; ++r)
-    hipLaunchKernelGGL(soft_round_kernel, dim3((unsigned)(F * tiles)), dim3(TILE_THREADS), 0, s, W, H, tiles_j, tiles, blk_stride,
-                       work + l.blocked, cost_stride, cost, field, flags[r & 1], flags[(r + 1) & 1]);
-  hipLaunchKernelGGL(tiled_settle_kernel, dim3((unsigned)F), dim3(SETUP_THREADS), 0, s, tiles, max_rounds & 1, flags[0], flags[1], settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
-}
-
 }  // namespace
 
 extern "C" int lipmpc_grid_clearance_cost_batch(int device, int64_t M, int32_t W, int32_t H, const uint8_t* occ, const int32_t* evidence,
@@ -3035,28 +2912,8 @@ extern "C" int lipmpc_grid_field_weighted_batch(int device, int64_t F, int32_t W
                                                 const double* cell, const uint8_t* occ, const uint8_t* cost, const double* goal,
                                                 int32_t r_inflate, uint32_t* field, int32_t* field_status, void* work, int64_t work_bytes,
                                                 int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
-    return LIPMPC_E_ARG;
-  if (!occ || !cost || !goal || !field || !field_status) return LIPMPC_E_ARG;
-  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
-  if (F == 0) return LIPMPC_OK;
-  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const TiledLayout l = tiled_layout(F, W, H);
-  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  const int64_t maps = grid_shared ? 1 : F, blk_stride = grid_shared ? 0 : l.bm_words;
-  uint32_t* w = (uint32_t*)work;
-  if (!resume) {
-    hipLaunchKernelGGL(tiled_bitmaps_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles, occ,
-                       (const int32_t*)nullptr, 0, 0, w + l.solid, w + l.unknown, w + l.flags0, (int32_t*)nullptr);
-    hipLaunchKernelGGL(tiled_blocked_kernel<0>, dim3((unsigned)(maps * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
-                       w + l.solid, w + l.unknown, w + l.blocked);
-    hipLaunchKernelGGL(tiled_goal_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, blk_stride, ox, oy, dx,
-                       dy, goal, w + l.blocked, field, field_status, w + l.flags0, l.tiles);
-  }
-  return soft_rounds(s, F, W, H, blk_stride, grid_shared ? (int64_t)0 : (int64_t)ncells, cost, l, w, field, max_rounds, settled);
+  return goal_field(device, F, W, H, grid_shared, origin, cell, occ, true, cost, goal, r_inflate, field, field_status, work, work_bytes,
+                    max_rounds, resume, settled, hip_stream);
 }
 
 extern "C" int lipmpc_grid_frontier_field_weighted_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence,
@@ -3064,25 +2921,8 @@ extern "C" int lipmpc_grid_frontier_field_weighted_batch(int device, int64_t F, 
                                                          int32_t min_unknown, uint8_t* frontier, uint32_t* field, int32_t* n_frontier,
                                                          void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume,
                                                          int32_t* settled, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
-      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || !cost || !field || !n_frontier)
-    return LIPMPC_E_ARG;
-  if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
-  if (F == 0) return LIPMPC_OK;
-  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const TiledLayout l = tiled_layout(F, W, H);
-  const int ncells = W * H, padded = (int)(l.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  uint32_t* w = (uint32_t*)work;
-  if (!resume) {
-    hipLaunchKernelGGL(tiled_bitmaps_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, ncells, chunks, F, l.tiles,
-                       (const uint8_t*)nullptr, evidence, t_free, t_occ, w + l.solid, w + l.unknown, w + l.flags0, n_frontier);
-    hipLaunchKernelGGL(tiled_blocked_kernel<1>, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, r_inflate,
-                       w + l.solid, w + l.unknown, w + l.blocked);
-    hipLaunchKernelGGL(tiled_frontier_seed_kernel, dim3((unsigned)(F * chunks)), dim3(SETUP_THREADS), 0, s, W, H, chunks, min_unknown,
-                       w + l.unknown, w + l.blocked, frontier, field, n_frontier, w + l.flags0, l.tiles);
-  }
-  return soft_rounds(s, F, W, H, l.bm_words, ncells, cost, l, w, field, max_rounds, settled);
+  return frontier_field(device, F, W, H, evidence, true, cost, t_free, t_occ, r_inflate, min_unknown, frontier, field, n_frontier, work,
+                        work_bytes, max_rounds, resume, settled, hip_stream);
 }
 
 extern "C" int lipmpc_grid_path_weighted_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -3091,18 +2931,15 @@ extern "C" int lipmpc_grid_path_weighted_batch(int device, int64_t B, int64_t F,
                                                const double* goal, const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
                                                double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, void* hip_stream) {
   if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
-    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!occ || !cost || !field || !field_status || !settled || !goal || !start || !sub_goals || !n_sub || !status || !path_cost)
-    return LIPMPC_E_ARG;
+  if (!occ || !cost || !field || !field_status || !settled || !goal || !start || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(soft_goal_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, ox, oy, dx, dy, occ, cost,
-                     field, field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1],
+                     cell[0], cell[1], occ, cost, field, field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
+                     path_cost);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
@@ -3113,17 +2950,14 @@ extern "C" int lipmpc_grid_frontier_path_weighted_batch(int device, int64_t B, i
                                                         double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                                         int32_t* target_cell, void* hip_stream) {
   if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || !origin || !cell || r_inflate < 0 || r_inflate > R_INFLATE_MAX) return LIPMPC_E_ARG;
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  if (!(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY))
-    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (!evidence || !cost || !field || !n_frontier || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell)
     return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(soft_frontier_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, ox, oy, dx, dy, evidence, cost, t_occ, field, n_frontier, settled, start,
-                     r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
+                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, cost, t_occ, field,
+                     n_frontier, settled, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
