@@ -146,18 +146,27 @@ __device__ __forceinline__ double vmax0(double x) {
   asm("v_max_f64 %0, 0, %1" : "=v"(r) : "v"(x));
   return r;
 }
+// Minimum / maximum over the group: the step across 4 lanes is a ROTATION of the row (row_ror:4, one move per word) where
+// a sum needs the xor-4 exchange (two bank-masked moves per word): after the two quad steps every lane holds its quad's
+// extremum Q_k; rotating by 4 gives min(Q_k, Q_k-1), rotating that by 8 all four.  v_min_f64 / v_max_f64 are exactly
+// associative and commutative -- no rounding; +0 / -0 and a NaN beside a number come out the same in any order -- so
+// every lane ends with the bits the xor tree gives it.
 template <int G> __device__ __forceinline__ double gmin(double x) {
-  x = vmin(x, gxor<G, 1>(x)); x = vmin(x, gxor<G, 2>(x)); x = vmin(x, gxor<G, 4>(x)); x = vmin(x, gxor<G, 8>(x));
+  x = vmin(x, gxor<G, 1>(x)); x = vmin(x, gxor<G, 2>(x));
+  x = vmin(x, dpp0<0x124>(x));                                // row_ror:4
+  x = vmin(x, gxor<G, 8>(x));
   if constexpr (G == 32) x = vmin(x, gxor<G, 16>(x));
   return x;
 }
 template <int G> __device__ __forceinline__ int gmin_int(int x) {
-  x = min(x, gxor<G, 1>(x)); x = min(x, gxor<G, 2>(x)); x = min(x, gxor<G, 4>(x)); x = min(x, gxor<G, 8>(x));
+  x = min(x, gxor<G, 1>(x)); x = min(x, gxor<G, 2>(x)); x = min(x, dpp0<0x124>(x)); x = min(x, gxor<G, 8>(x));
   if constexpr (G == 32) x = min(x, gxor<G, 16>(x));
   return x;
 }
 template <int G> __device__ __forceinline__ double gmax(double x) {
-  x = vmax(x, gxor<G, 1>(x)); x = vmax(x, gxor<G, 2>(x)); x = vmax(x, gxor<G, 4>(x)); x = vmax(x, gxor<G, 8>(x));
+  x = vmax(x, gxor<G, 1>(x)); x = vmax(x, gxor<G, 2>(x));
+  x = vmax(x, dpp0<0x124>(x));                                // row_ror:4
+  x = vmax(x, gxor<G, 8>(x));
   if constexpr (G == 32) x = vmax(x, gxor<G, 16>(x));
   return x;
 }

@@ -110,7 +110,8 @@
         for (int i = 0; i < NR; ++i) {
           const double r = act[i] ? -slk[i] : 0.0;      // G_A q - h_A
           wr[i] = -d[i] * slk[i];                       // rho r (d = rho on active rows, 0 elsewhere)
-          rmax_l = fmax(rmax_l, fabs(r));
+          // (vmax*, vmin: fmax / fmin without the canonicalisation of every selected operand, lipmpc_comm.hpp)
+          rmax_l = i == 0 ? vmax0_abs(r) : vmax_abs(rmax_l, r);
         }
         double ayx = 0.0, ayy = 0.0, awx = 0.0, awy = 0.0;
         if constexpr (STREAM) {
@@ -132,7 +133,7 @@
         const double eprev = eres;
         rd_g = gmax<G>(fabs(rd));
         r_g = gmax<G>(rmax_l);
-        eres = fmax(rd_g, r_g);
+        eres = vmax(rd_g, r_g);
         // converged, out of corrections, or stalled on its rounding floor below what the certificate needs (an
         // ill-conditioned working set sits at 1e-10 forever: four corrections of ~1.7 us each, per round, for nothing)
         const bool stop = (eres <= FIN_INNER_TOL) || (in == FIN_INNER) || (eres <= FIN_EPS && eres > FIN_STALL * eprev);
@@ -183,9 +184,10 @@
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
         const bool ta = act[i], ti = pres[i] & !ta;
-        ymin = fmin(ymin, ta ? y[i] : INFINITY);
-        ymax = fmax(ymax, ta ? y[i] : 0.0);
-        smin = fmin(smin, ti ? slk[i] : INFINITY);
+        const double ylo = ta ? y[i] : INFINITY, yhi = ta ? y[i] : 0.0, slo = ti ? slk[i] : INFINITY;
+        ymin = i == 0 ? fmin(ymin, ylo) : vmin(ymin, ylo);
+        ymax = i == 0 ? vmax0(yhi) : vmax(ymax, yhi);
+        smin = i == 0 ? fmin(smin, slo) : vmin(smin, slo);
       }
       if constexpr (STREAM) {
 #pragma unroll STREAM_UNROLL
@@ -252,7 +254,7 @@
             const double qabs = gmax<G>(fabs(qf));
             fin_done = true;
             certified = fok && (r_g <= FIN_EPS) && (rd_g <= FIN_EPS + FIN_DUAL_REL * ymax) && (smin >= -FIN_EPS) && (qabs < 1e300);
-            diag_cert = fmin(ymin, smin);      // how decisively the certificate holds (weakly active rows -> ~0)
+            diag_cert = vmin(ymin, smin);      // how decisively the certificate holds (weakly active rows -> ~0)
           }
         }
         diag_rounds = rnd + 1;

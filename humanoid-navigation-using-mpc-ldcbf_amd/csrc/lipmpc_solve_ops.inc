@@ -101,6 +101,15 @@
   // (= column j of Lt, by symmetry) and lanes l > j keep Lt[l][j] in Krow[j]; ipiv = 1/pivot.
   // Per (j, c) that is one row_newbcast move and one FMA, with f = 0 on lanes <= j instead of
   // predication.  Returns false on a non-positive pivot.
+  // G = 16: the pivot test is ONE running v_min_f64 per step (vmin, lipmpc_comm.hpp) and one comparison at the end, instead
+  // of a comparison and a lane-mask OR per step (and an SGPR pair live across the whole factorisation).  It returns what
+  // `ok = ok && (p_j > 0)` over all steps returns, for every input:
+  //  * no pivot is NaN: min_j p_j > 0 exactly when every p_j > 0 (-0, +0 and -inf fail both forms; a denormal passes both;
+  //    +inf passes the comparison in both -- as a pivot before the last its reciprocal is NaN, which is the next case);
+  //  * some pivot is NaN: v_min_f64 returns its other operand, so the minimum alone would miss it.  But a NaN pivot p_j makes
+  //    ip, then nf on every lane > j, then every K[cc], cc > j, on those lanes NaN (0 * NaN and inf * NaN are NaN too), so
+  //    p_{j+1} -- K[j+1] of lane j + 1 -- and every later pivot is NaN: a NaN anywhere is a NaN in the LAST pivot, which is
+  //    compared with 0 on its own.  (Pivots are results of FP arithmetic: never signalling.)
   double ipiv = 0.5;
   // broadcast inside the lane's own DPP row (16 lanes)
   auto bc16 = [](auto ic, double x) -> double {
@@ -115,6 +124,7 @@
     dpp_fence();
     double pnext = 0.0;                                   // G = 16: pivot of the next step, broadcast at the end of the step
     if constexpr (FUSED) pnext = gbcast<G, 0>(Krow[0]);
+    double pmin = pnext;                                  // G = 16: smallest pivot so far (NaN pivots skipped, see above)
     static_for<0, NV>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
       if constexpr (FUSED) {
@@ -123,7 +133,8 @@
         // "lookahead", tried in round 4 -- gains nothing: a dependent FP64 instruction costs 7 cycles against 4.6 for an
         // independent one, the chain is issue slots, not latency; profiles/r04_dev_tools/r04_iter_cost_lookahead_factorisation.txt.)
         const double pj = pnext;                          // gbcast<G, j>(Krow[j])
-        ok = ok && (pj > 0.0);
+        if constexpr (j > 0) pmin = vmin(pmin, pj);
+        if constexpr (j == NV - 1) ok = (pmin > 0.0) & (pj > 0.0);
         const double ip = fast_rcp(pj);
         const double nf = zero_unless(ln > j, Krow[j] * -ip);
         // ipiv ends as ip_l on lane l either way; (ln > j - 1) is the mask of the step before, (ln == j) one more compare.
