@@ -156,6 +156,17 @@ SIGNATURES = {
                                                                   "keep_ratio16:i32 keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work "
                                                                   "work_bytes:i64 max_rounds:i32 sub_goals n_sub status path_cost "
                                                                   "target_cell claim_round n_claims kept n_kept claims_settled hip_stream"),
+    # the wave-per-robot path calls: the weighted / tiled-utility calls' argument lists, cost and settled nullable
+    "lipmpc_grid_path_wave_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell occ grid_shared:i32 cost field "
+                                                 "field_status settled goal start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub "
+                                                 "status path_cost hip_stream"),
+    "lipmpc_grid_frontier_path_wave_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell evidence cost t_occ:i32 field "
+                                                          "n_frontier settled start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals "
+                                                          "n_sub status path_cost target_cell hip_stream"),
+    "lipmpc_grid_frontier_utility_path_wave_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell evidence t_occ:i32 frontier "
+                                                                  "gain ufield n_sources settled w_gain:i32 g_cap:i32 min_gain:i32 start "
+                                                                  "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost "
+                                                                  "target_cell target_gain hip_stream"),
     "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
                                              "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),

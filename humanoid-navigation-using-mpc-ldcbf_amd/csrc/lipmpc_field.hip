@@ -2961,3 +2961,9 @@ extern "C" int lipmpc_grid_frontier_path_weighted_batch(int device, int64_t B, i
                      n_frontier, settled, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
+
+// =====================================================================================================================
+// WAVE-PER-ROBOT PATH CALLS (lipmpc_grid_path_wave_batch, lipmpc_grid_frontier_path_wave_batch,
+// lipmpc_grid_frontier_utility_path_wave_batch): the path kernels above with a wavefront walking each robot's path; a section of its
+// own that shares this file's helpers and constants
+#include "lipmpc_field_wave.inc"

@@ -56,12 +56,14 @@ COST_MAX, R_CLEAR_MAX = 248, 31     # LIPMPC_COST_MAX; the largest r_clear (a di
 
 
 class _TiledKeywords(type):
-    """The keyword-only ``tiled`` / ``rounds`` / ``r_clear`` / ``w_clear`` of the two field planners, taken off before ``__init__``
-    runs: the classes' ``__init__`` signatures -- which callers hand on positionally and through ``**kwargs`` -- stay what they were."""
+    """The keyword-only ``tiled`` / ``rounds`` / ``r_clear`` / ``w_clear`` / ``paths`` of the two field planners, taken off before
+    ``__init__`` runs: the classes' ``__init__`` signatures -- which callers hand on positionally and through ``**kwargs`` -- stay what
+    they were."""
 
     def __call__(cls, *args, tiled: bool = False, rounds: int | None = None, r_clear: int | None = None, w_clear: int | None = None,
-                 **kwargs):
+                 paths: str = "lane", **kwargs):
         self = cls.__new__(cls)
+        self._init_paths(paths)
         self._init_tiled(tiled, rounds)
         self._init_clearance(r_clear, w_clear)
         self.__init__(*args, **kwargs)
@@ -106,6 +108,15 @@ class _TiledRounds(metaclass=_TiledKeywords):
         if self.rounds is not None and (not self.tiled or not 1 <= self.rounds <= 65536):
             raise ValueError(f"rounds {rounds}: 1..65536 or None, with tiled=True only")
         self._works = []            # every workspace ever handed to a call; the last one is the current one
+
+    def _init_paths(self, paths):
+        """WAVE-PER-ROBOT PATH CALLS (include/lipmpc.h): ``paths`` = "lane" (default), every path call is the one-lane call of the
+        planner's form; "wave": the wave call of the same contract in its place -- the same output dict, bit for bit, the same buffers
+        and stream, capturable wherever the lane form is.  It governs the planner's own path call (``plan_grid_batch`` / ``plan``); the
+        walks inside the coordinated planners' claim calls stay one lane per robot."""
+        if paths not in ("lane", "wave"):
+            raise ValueError(f"paths {paths!r}: 'lane' (one lane per robot, the default) or 'wave' (one wavefront per robot)")
+        self.paths = paths
 
     def _init_clearance(self, r_clear, w_clear):
         """SOFT CLEARANCE (include/lipmpc.h): ``r_clear`` 1..31 cells and ``w_clear`` 0..248, both or neither, no defaults (nobody
@@ -425,7 +436,10 @@ class GridFieldPlanner(_TiledRounds):
     a path pays a cell's byte when it leaves the cell: paths keep clear of walls where there is room and still pass a door one cell
     wide, which ``r_inflate`` = 1 would close.  ``field()``, ``plan_grid_batch()`` then return cost [M,W,H] too; the keyword
     ``cost=`` of those methods takes any uint8 layer instead; ``clearance_cost(grid)`` returns the layer alone.  The cost is static
-    per plan, and path_cost includes it."""
+    per plan, and path_cost includes it.
+    Keyword-only ``paths`` = "lane" (default) / "wave", in every form above: "wave" makes the path call by
+    ``lipmpc_grid_path_wave_batch`` -- one wavefront walks one robot's path (include/lipmpc.h, WAVE-PER-ROBOT PATH CALLS) --, the same
+    dict bit for bit, the same buffers and stream, capturable wherever the "lane" form is."""
 
     def __init__(self, r_inflate: int = 0, max_seg: int | None = None, device: int | None = None):
         if not torch.cuda.is_available():
@@ -522,6 +536,8 @@ class GridFieldPlanner(_TiledRounds):
         path = dict(lipmpc_grid_path_tiled_batch=dict(settled=out["settled"])) if self.tiled else dict(lipmpc_grid_path_batch={})
         if "cost" in out:
             path = dict(lipmpc_grid_path_weighted_batch=dict(settled=out["settled"], cost=out["cost"]))
+        if self.paths == "wave":
+            path = dict(lipmpc_grid_path_wave_batch=dict(settled=out["settled"] if self.tiled else None, cost=out.get("cost")))
         (name, more), = path.items()
         _lib.call(name, device=self.device_index, B=B, F=F, **ga, **more, field=out["field"], field_status=out["field_status"],
                   goal=goal, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
@@ -552,7 +568,10 @@ class FrontierPlanner(_TiledRounds):
     cells of the evidence (unknown cells carry no cost: it would eat the frontier), the weighted frontier field and the weighted
     paths; ``field()`` and ``plan()`` return cost [F,W,H] too and take the keyword ``cost=``; ``clearance_cost(mapper)`` returns the
     layer alone.  ``CoordinatedFrontierPlanner``, ``InformedFrontierPlanner`` and their large-map classes refuse these keywords: the
-    claim rounds and the utility field are unweighted."""
+    claim rounds and the utility field are unweighted.
+    Keyword-only ``paths`` = "lane" (default) / "wave": as ``GridFieldPlanner``'s, in every form
+    (``lipmpc_grid_frontier_path_wave_batch``); the informed classes take it for their utility path call
+    (``lipmpc_grid_frontier_utility_path_wave_batch``) and the coordinated classes for the nearest-frontier plan."""
 
     def __init__(self, r_inflate: int = 2, min_unknown: int = 2, t_free: int | None = None, t_occ: int | None = None,
                  max_seg: int | None = None, device: int | None = None):
@@ -659,6 +678,8 @@ class FrontierPlanner(_TiledRounds):
             dict(lipmpc_grid_frontier_path_batch={})
         if "cost" in out:
             path = dict(lipmpc_grid_frontier_path_weighted_batch=dict(settled=out["settled"], cost=out["cost"]))
+        if self.paths == "wave":
+            path = dict(lipmpc_grid_frontier_path_wave_batch=dict(settled=out["settled"] if self.tiled else None, cost=out.get("cost")))
         (name, more), = path.items()
         _lib.call(name, device=self.device_index, B=B, F=F, W=W, H=H, origin=C.addressof(org_c), **more,
                   cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ, field=out["field"], n_frontier=out["n_frontier"], start=start,
@@ -707,7 +728,9 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     nearest frontier plus ``keep_slack`` cells; a keeper takes its disc like a winner, and keep attempts and rounds share the
     ``max_claims`` relaxations.  Without ``r_keep`` the very calls of before are made.  What remains: the keep test compares with
     the NEAREST frontier, not with what the rounds would have handed the robot; followers have no memory; the informed planners
-    have none either."""
+    have none either.
+    Keyword-only ``paths`` = "wave" governs the nearest-frontier plan that precedes the claims; the walks inside the claim calls -- a
+    winner's or a keeper's path -- are unchanged, one lane per robot."""
 
     _TILED, _TILED_WHY, _TILED_CLASS = False, "the claim rounds keep", "TiledCoordinatedFrontierPlanner"
     _CLEARANCE = False
@@ -1017,9 +1040,12 @@ class InformedFrontierPlanner(FrontierPlanner):
 
     def _path(self, ev, t_occ, start, org_c, cell_c, S_max, out):
         F, W, H = ev.shape
-        _lib.call("lipmpc_grid_frontier_utility_path_batch", device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
+        name, more = "lipmpc_grid_frontier_utility_path_batch", {}
+        if self.paths == "wave":
+            name, more = "lipmpc_grid_frontier_utility_path_wave_batch", dict(settled=None)
+        _lib.call(name, device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
                   origin=C.addressof(org_c), cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ,
-                  **_named(out, ("frontier", "gain", "ufield", "n_sources")), w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain,
+                  **_named(out, ("frontier", "gain", "ufield", "n_sources")), **more, w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain,
                   start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "target_gain")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
@@ -1073,7 +1099,8 @@ class TiledInformedFrontierPlanner(_AlwaysTiled, InformedFrontierPlanner):
 
     def _path(self, ev, t_occ, start, org_c, cell_c, S_max, out):
         F, W, H = ev.shape
-        _lib.call("lipmpc_grid_frontier_utility_path_tiled_batch", device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
+        name = "lipmpc_grid_frontier_utility_path_wave_batch" if self.paths == "wave" else "lipmpc_grid_frontier_utility_path_tiled_batch"
+        _lib.call(name, device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
                   origin=C.addressof(org_c), cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ,
                   **_named(out, ("frontier", "gain", "ufield", "n_sources")), settled=out["usettled"], w_gain=self.w_gain, g_cap=self.g_cap,
                   min_gain=self.min_gain, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,

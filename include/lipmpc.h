@@ -47,7 +47,9 @@ extern "C" {
                                 *      LIPMPC_RRT_FIELD_UNSETTLED;
                                 *    + lipmpc_grid_clearance_cost_batch / lipmpc_grid_field_weighted_batch /
                                 *      lipmpc_grid_frontier_field_weighted_batch / lipmpc_grid_path_weighted_batch /
-                                *      lipmpc_grid_frontier_path_weighted_batch, LIPMPC_COST_MAX */
+                                *      lipmpc_grid_frontier_path_weighted_batch, LIPMPC_COST_MAX;
+                                *    + lipmpc_grid_path_wave_batch / lipmpc_grid_frontier_path_wave_batch /
+                                *      lipmpc_grid_frontier_utility_path_wave_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -1213,6 +1215,46 @@ int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t B, int32_t 
                                                  int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
                                                  int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled,
                                                  void* hip_stream);
+
+/* WAVE-PER-ROBOT PATH CALLS (backward-compatible addition): the path calls above with one wavefront (64 lanes) walking each
+ * robot's path where those walk it in one lane -- the sight tests 64 cells at a time, a descent step in one round of loads.  Every
+ * output is the named call's, bit for bit; only the time differs.  Three calls take the place of eight by way of NULLABLE inputs:
+ *  lipmpc_grid_path_wave_batch: the arguments of lipmpc_grid_path_weighted_batch.
+ *    cost null, settled null:  the contract of lipmpc_grid_path_batch (`field` from lipmpc_grid_field_batch)
+ *    cost null, settled given: the contract of lipmpc_grid_path_tiled_batch
+ *    cost given, settled given: the contract of lipmpc_grid_path_weighted_batch
+ *    cost given, settled null: LIPMPC_E_ARG (a weighted field has the word)
+ *  lipmpc_grid_frontier_path_wave_batch: the arguments of lipmpc_grid_frontier_path_weighted_batch, the same three forms --
+ *    lipmpc_grid_frontier_path_batch, lipmpc_grid_frontier_path_tiled_batch, lipmpc_grid_frontier_path_weighted_batch -- and the
+ *    same refusal.
+ *  lipmpc_grid_frontier_utility_path_wave_batch: the arguments of lipmpc_grid_frontier_utility_path_tiled_batch.
+ *    settled null: the contract of lipmpc_grid_frontier_utility_path_batch; given: of lipmpc_grid_frontier_utility_path_tiled_batch.
+ *  REFUSALS, all decided on the host before anything is enqueued, in this order in every form: LIPMPC_E_ARG for what the tiled path
+ *  calls refuse as such about scalars and the placement (max_seg < 5, S_max < 1, F not in {1, B}, origin / cell, t_occ, w_gain,
+ *  g_cap, min_gain) and for cost without settled; then the TILED caps -- W, H <= 4096, W * H <= 2^24, F * (W * H + 64) <= 2^31:
+ *  LIPMPC_E_UNSUPPORTED -- also in the forms that equal a one-workgroup call, whose cap of 2^17 cells belongs to the field's LDS (a
+ *  path call needs none sized to the map); then B == 0 returns LIPMPC_OK; then a null pointer other than the nullable ones is
+ *  LIPMPC_E_ARG.
+ *  A `field` that is no cost-to-go field of the map (stale, constant, another map's) ends as in the one-lane calls: the descent
+ *  takes strictly falling words only, so every walk ends within W * H steps.
+ *  What stays one lane per robot: the winner's walk inside the claim calls (lipmpc_grid_frontier_assign_*_batch) and the RRT* planner. */
+int lipmpc_grid_path_wave_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell,
+                                const uint8_t* occ, int32_t grid_shared, const uint8_t* cost, const uint32_t* field,
+                                const int32_t* field_status, const int32_t* settled, const double* goal, const double* start,
+                                int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                double* path_cost, void* hip_stream);
+int lipmpc_grid_frontier_path_wave_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                         const double* cell, const int32_t* evidence, const uint8_t* cost, int32_t t_occ,
+                                         const uint32_t* field, const int32_t* n_frontier, const int32_t* settled, const double* start,
+                                         int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
+                                         int32_t* status, double* path_cost, int32_t* target_cell, void* hip_stream);
+int lipmpc_grid_frontier_utility_path_wave_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
+                                                 const double* cell, const int32_t* evidence, int32_t t_occ, const uint8_t* frontier,
+                                                 const int32_t* gain, const uint32_t* ufield, const int32_t* n_sources,
+                                                 const int32_t* settled, int32_t w_gain, int32_t g_cap, int32_t min_gain,
+                                                 const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
+                                                 double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                                 int32_t* target_cell, int32_t* target_gain, void* hip_stream);
 
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
