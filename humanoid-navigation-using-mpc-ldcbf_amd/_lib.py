@@ -39,6 +39,11 @@ def _sig(restype, params):
 _STEP_OUT = "U X theta omega obj status iters active working"
 _GRID_SCAN = "resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 eps:f64 min_samples:i32"
 _SCAN = "resolution:i32 n_env:i32 v_env:i32 env_shared:i32 lidar_range:f64 eps:f64 min_samples:i32"
+_ASSIGN = ("device:int B:i64 W:i32 H:i32 origin cell frontier field start may_claim r_inflate:i32 r_claim:i32 max_claims:i32 max_seg:i32 "
+           "S_max:i32 work sub_goals n_sub status path_cost target_cell claim_round n_claims")
+_ASSIGN_TILED = ("device:int B:i64 W:i32 H:i32 origin cell frontier field settled start may_claim r_inflate:i32 r_claim:i32 max_claims:i32 "
+                 "max_seg:i32 S_max:i32 work work_bytes:i64 max_rounds:i32 sub_goals n_sub status path_cost target_cell claim_round n_claims "
+                 "claims_settled")
 
 # Every export of include/lipmpc.h with the header's own parameter names: the ONE statement of each argument list on the
 # Python side.  load() binds restype / argtypes from it, call() takes its arguments by these names, and
@@ -94,9 +99,8 @@ SIGNATURES = {
                                                       "frontier field n_frontier hip_stream"),
     "lipmpc_grid_frontier_path_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell evidence t_occ:i32 field n_frontier start "
                                                      "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost target_cell hip_stream"),
-    "lipmpc_grid_frontier_assign_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field start may_claim r_inflate:i32 "
-                                                       "r_claim:i32 max_claims:i32 max_seg:i32 S_max:i32 work sub_goals n_sub status path_cost "
-                                                       "target_cell claim_round n_claims hip_stream"),
+    "lipmpc_grid_frontier_assign_batch": _sig(C.c_int, f"{_ASSIGN} hip_stream"),
+    "lipmpc_grid_frontier_assign_utility_batch": _sig(C.c_int, f"{_ASSIGN} gain w_gain:i32 g_cap:i32 min_gain:i32 target_gain hip_stream"),
     "lipmpc_grid_frontier_assign_keep_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field start may_claim "
                                                             "prev_target r_inflate:i32 r_claim:i32 r_keep:i32 keep_ratio16:i32 "
                                                             "keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work sub_goals n_sub status "
@@ -146,10 +150,10 @@ SIGNATURES = {
                                                                    "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost "
                                                                    "target_cell target_gain hip_stream"),
     "lipmpc_grid_frontier_assign_tiled_workspace_bytes": _sig(C.c_int64, "W:i32 H:i32"),
-    "lipmpc_grid_frontier_assign_tiled_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field settled start may_claim "
-                                                             "r_inflate:i32 r_claim:i32 max_claims:i32 max_seg:i32 S_max:i32 work work_bytes:i64 "
-                                                             "max_rounds:i32 sub_goals n_sub status path_cost target_cell claim_round n_claims "
-                                                             "claims_settled hip_stream"),
+    "lipmpc_grid_frontier_assign_tiled_batch": _sig(C.c_int, f"{_ASSIGN_TILED} hip_stream"),
+    "lipmpc_grid_frontier_assign_utility_tiled_workspace_bytes": _sig(C.c_int64, "W:i32 H:i32"),
+    "lipmpc_grid_frontier_assign_utility_tiled_batch": _sig(C.c_int, f"{_ASSIGN_TILED} gain w_gain:i32 g_cap:i32 min_gain:i32 target_gain "
+                                                                     "hip_stream"),
     "lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes": _sig(C.c_int64, "W:i32 H:i32"),
     "lipmpc_grid_frontier_assign_keep_tiled_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field settled start "
                                                                   "may_claim prev_target r_inflate:i32 r_claim:i32 r_keep:i32 "

@@ -1260,6 +1260,214 @@ __global__ void __launch_bounds__(PATH_THREADS) frontier_utility_path_kernel(
   done(LIPMPC_RRT_FOUND, n, cost, last_cell);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// gain-seeded claims (lipmpc_grid_frontier_assign_utility_batch): the coordinated claim's rounds with the utility field's seeds
+// on what is left of the sources and the utility path's terminal test where the winner walks -- on a body of its own: the assign
+// and keep kernels above and their code objects stay what they were.  The source bitmap holds S_k (frontier, passable,
+// gain >= min_gain, outside every disc so far), so the terminal test is "a bit of S_k that holds its own seed" and `gain` is read
+// at source cells only; it stays in global memory.
+// LDS: the assign kernels' layout with UCLAIM_WORDS in place of ASSIGN_WORDS -- after the nine parked pairs come two more
+// pointers (gain, target_gain), four scalars -- the seed's w_gain and g_cap, which the round's seeding reads from here too (a
+// lane's registers hold them then, not the scalar file through every loop), and the walking lane's max_seg and S_max -- then
+// n_claims' pointer and the two scalars of a round's end, r_claim and max_claims
+constexpr int UCLAIM_WORDS = 34;
+__host__ __device__ inline int64_t uclaim_bitmap_words(int64_t ncells) { return 2 * bitmap_words(ncells) + UCLAIM_WORDS; }
+__host__ __device__ inline int64_t uclaim_lds_bytes(int64_t ncells, bool in_lds) {
+  return 4 * (uclaim_bitmap_words(ncells) + (in_lds ? ncells : 0));
+}
+
+inline bool uclaim_fits_lds(int64_t ncells) { return uclaim_lds_bytes(ncells, true) + LDS_SLACK <= LDS_LIMIT; }
+
+// walk_to() on whatever pointer the round's field lives behind, read with the sweeps' own loads
+template <typename FieldPtr, typename Terminal>
+__device__ __forceinline__ int walk_in_to(FieldPtr fld, int W, int H, int s, int max_seg, double ox, double oy, double dx, double dy,
+                                          double* sg, int& last_cell, Terminal terminal) {
+  int count = 0;
+  auto emit = [&](int c) {
+    if (sg) centre(c, H, ox, oy, dx, dy, sg + 2 * count);
+    ++count;
+  };
+  last_cell = s;
+  if (!terminal(s)) {
+    int a = s, prev = s, cur = descend_in(fld, W, H, s);
+    while (cur >= 0) {
+      const bool last = terminal(cur);
+      if (!los_in(fld, H, a, cur) || ld(fld + a) - ld(fld + cur) >= (uint32_t)max_seg) {
+        if (prev != a) { emit(prev); a = prev; continue; }
+        if (last) break;
+        emit(cur); a = cur;
+      }
+      if (last) break;
+      prev = cur;
+      cur = descend_in(fld, W, H, cur);
+    }
+    if (cur < 0) return -1;
+    last_cell = cur;
+  }
+  return count + 1;
+}
+
+// The whole call: assign_body with the three differences named above.  claim_round[b] holds -2 - (start cell) while b is in U.
+template <typename FieldPtr>
+__device__ __forceinline__ void assign_utility_body(FieldPtr fld, uint32_t* bm, int64_t B, int W, int H, double ox, double oy, double dx,
+                                                    double dy, const uint8_t* __restrict__ frontier, const uint32_t* __restrict__ field,
+                                                    const int32_t* __restrict__ gain, int w_gain, int g_cap, int min_gain,
+                                                    const double* __restrict__ start, const int8_t* __restrict__ may_claim,
+                                                    int r_inflate, int r_claim, int max_claims, int max_seg, int S_max,
+                                                    double* __restrict__ sub_goals, int32_t* __restrict__ n_sub,
+                                                    int32_t* __restrict__ status, double* __restrict__ path_cost,
+                                                    int32_t* __restrict__ target_cell, int32_t* __restrict__ target_gain,
+                                                    int32_t* claim_round, int32_t* __restrict__ n_claims) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  uint32_t *blk = bm, *src = bm + words, *tgt = bm + 2 * words + 2;
+  unsigned long long* key = (unsigned long long*)(bm + 2 * words);
+  uint32_t* parked = bm + 2 * words + 4;                  // 64-bit values as word pairs, then the two scalars
+  auto park = [&](int slot, unsigned long long v) { parked[2 * slot] = (uint32_t)v; parked[2 * slot + 1] = (uint32_t)(v >> 32); };
+  auto unpark = [&](int slot) { return ((unsigned long long)parked[2 * slot + 1] << 32) | parked[2 * slot]; };
+
+  // U_0, each robot with its start cell
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+    const int sb = status[b];
+    int si = 0, sj = 0, v = -1;
+    if (max_claims > 0 && (sb == LIPMPC_RRT_FOUND || sb == LIPMPC_RRT_PATH_OVERFLOW) && (!may_claim || may_claim[b]) &&
+        cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
+      v = -2 - (si * H + sj);
+    claim_round[b] = v;
+  }
+  int claims = 0;
+  if (max_claims > 0) {
+    // impassable = the given field is INF; sources = the utility field's: the given frontier, passable, gain >= min_gain
+    for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+      const int c = c0 + lane;
+      const bool pass = c < ncells && field[c] != INF;
+      bool s = false;
+      if (pass && frontier[c] != 0) s = gain[c] >= min_gain;
+      const uint64_t mb = __ballot(c < ncells && !pass), ms = __ballot(s);
+      if (lane == 0) {
+        blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32);
+        src[c0 >> 5] = (uint32_t)ms; src[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      }
+    }
+    if (tid < 2) { blk[words - 2 + tid] = 0; src[words - 2 + tid] = 0; }
+    if (tid == 0) {
+      *key = ~0ull;
+      park(0, __double_as_longlong(ox)); park(1, __double_as_longlong(oy)); park(2, __double_as_longlong(dx));
+      park(3, __double_as_longlong(dy));
+      park(4, (unsigned long long)sub_goals); park(5, (unsigned long long)n_sub); park(6, (unsigned long long)status);
+      park(7, (unsigned long long)path_cost); park(8, (unsigned long long)target_cell);
+      park(9, (unsigned long long)gain); park(10, (unsigned long long)target_gain);
+      parked[22] = (uint32_t)w_gain; parked[23] = (uint32_t)g_cap; parked[24] = (uint32_t)max_seg; parked[25] = (uint32_t)S_max;
+      park(13, (unsigned long long)n_claims); parked[28] = (uint32_t)r_claim; parked[29] = (uint32_t)max_claims;
+      tgt[1] = (uint32_t)r_inflate;                       // (the spare word beside the target)
+    }
+    __syncthreads();
+
+    for (int k = 0;; ++k) {
+      // ufield_k: its seed on what is left of the sources, relaxed to the fixed point
+      int any = 0;
+      {
+        const int32_t* gn = (const int32_t*)unpark(9);
+        const int ww = (int)parked[22], wcap = (int)parked[23];
+        for (int c = tid; c < ncells; c += FIELD_THREADS) {
+          const bool s = bit_of(src, c);
+          st(fld + c, s ? gain_seed(gn[c], ww, wcap) : INF);
+          any |= s;
+        }
+      }
+      if (!__syncthreads_or(any)) break;
+      relax(fld, blk, W, H);
+      // the candidates of U_k, and the least (cost, b) among them
+      unsigned long long mine = ~0ull;
+      int eligible = 0;
+      for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+        const int v = claim_round[b];
+        if (v > -2) continue;
+        ++eligible;
+        const int s = claim_cell(fld, W, H, -2 - v, (int)tgt[1]);
+        if (s >= 0) mine = min(mine, ((unsigned long long)ld(fld + s) << 32) | (unsigned long long)b);
+      }
+      for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
+      if (lane == 0 && mine != ~0ull) atomicMin(key, mine);
+      __syncthreads();
+      const unsigned long long win = *key;
+      if (win == ~0ull) break;                            // no candidate: the rounds end
+      const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
+      if (tid == 0) {
+        // one lane walks the winner's path, twice: count, then -- if the sub-goals fit -- write (rows past n_sub stay untouched)
+        const int s = claim_cell(fld, W, H, -2 - claim_round[wb], (int)tgt[1]);
+        const double wox = __longlong_as_double(unpark(0)), woy = __longlong_as_double(unpark(1));
+        const double wdx = __longlong_as_double(unpark(2)), wdy = __longlong_as_double(unpark(3));
+        const int wseg = (int)parked[24], wmax = (int)parked[25];
+        double* sg = (double*)unpark(4) + wb * (int64_t)wmax * 2;
+        const int32_t* wgain = (const int32_t*)unpark(9);
+        const int ww = (int)parked[22], wcap = (int)parked[23];
+        auto terminal = [&](int c) { return bit_of(src, c) && ld(fld + c) == gain_seed(wgain[c], ww, wcap); };
+        int last_cell = s, n = 0;
+        for (int pass = 0; pass < 2 && n >= 0 && n <= wmax; ++pass)
+          n = walk_in_to(fld, W, H, s, wseg, wox, woy, wdx, wdy, pass ? sg : nullptr, last_cell, terminal);
+        if (n > 0) {
+          if (n <= wmax) centre(last_cell, H, wox, woy, wdx, wdy, sg + 2 * (n - 1));
+          ((int32_t*)unpark(6))[wb] = n <= wmax ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+          ((int32_t*)unpark(5))[wb] = n <= wmax ? n : 0;
+          ((double*)unpark(7))[wb] = (double)(ld(fld + s) - ld(fld + last_cell)) / 5.0;
+          ((int32_t*)unpark(8))[wb] = last_cell;
+          ((int32_t*)unpark(10))[wb] = wgain[last_cell];
+          claim_round[wb] = k;
+        }
+        *tgt = n > 0 ? (uint32_t)last_cell : INF;         // (a fixed point always has a descent: INF cannot happen)
+      }
+      if ((wb & (FIELD_THREADS - 1)) == tid) --eligible;
+      const int more = __syncthreads_or(eligible);
+      const uint32_t t = *tgt;
+      if (tid == 0) *key = ~0ull;                         // (everybody has read it; the next minimum comes two barriers on)
+      if (t == INF) break;
+      ++claims;
+      if (!more || k + 1 >= (int)parked[29]) break;       // U or the allowance is used up
+      // S_{k+1}: the sources outside the winner's disc, clipped to the grid
+      const int rc = (int)parked[28];
+      const int ti = (int)t / H, tj = (int)t - ti * H, r2 = rc * rc;
+      const int i_lo = max(ti - rc, 0), i_hi = min(ti + rc, W - 1);
+      for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+        const int i = c / H, j = c - i * H;
+        if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+      }
+      __syncthreads();
+    }
+    // the followers: still in U
+    __syncthreads();
+    for (int64_t b = tid; b < B; b += FIELD_THREADS)
+      if (claim_round[b] < -1) claim_round[b] = -1;
+    if (tid == 0) ((int32_t*)unpark(13))[0] = claims;
+  } else if (tid == 0) {
+    n_claims[0] = 0;
+  }
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_utility_lds_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const int32_t* __restrict__ gain, int w_gain, int g_cap, int min_gain,
+    const double* __restrict__ start, const int8_t* __restrict__ may_claim, int r_inflate, int r_claim, int max_claims, int max_seg,
+    int S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* target_gain,
+    int32_t* claim_round, int32_t* __restrict__ n_claims) {
+  extern __shared__ uint32_t field_lds[];
+  assign_utility_body(field_lds + uclaim_bitmap_words((int64_t)W * H), field_lds, B, W, H, ox, oy, dx, dy, frontier, field, gain, w_gain,
+                      g_cap, min_gain, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max, sub_goals, n_sub, status,
+                      path_cost, target_cell, target_gain, claim_round, n_claims);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_utility_global_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const int32_t* __restrict__ gain, int w_gain, int g_cap, int min_gain,
+    const double* __restrict__ start, const int8_t* __restrict__ may_claim, int r_inflate, int r_claim, int max_claims, int max_seg,
+    int S_max, uint32_t* work, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+    int32_t* target_gain, int32_t* claim_round, int32_t* __restrict__ n_claims) {
+  extern __shared__ uint32_t field_lds[];
+  assign_utility_body(work, field_lds, B, W, H, ox, oy, dx, dy, frontier, field, gain, w_gain, g_cap, min_gain, start, may_claim,
+                      r_inflate, r_claim, max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, target_gain,
+                      claim_round, n_claims);
+}
+
 // E_ARG of a grid's placement
 bool bad_placement(const double* origin, const double* cell) {
   if (!origin || !cell) return true;
@@ -1488,6 +1696,40 @@ extern "C" int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, in
                      (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier,
                      gain, ufield, n_sources, w_gain, g_cap, min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
                      path_cost, target_cell, target_gain);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin,
+                                                         const double* cell, const uint8_t* frontier, const uint32_t* field,
+                                                         const double* start, const int8_t* may_claim, int32_t r_inflate,
+                                                         int32_t r_claim, int32_t max_claims, int32_t max_seg, int32_t S_max,
+                                                         uint32_t* work, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                                         double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                                         int32_t* n_claims, const int32_t* gain, int32_t w_gain, int32_t g_cap,
+                                                         int32_t min_gain, int32_t* target_gain, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !frontier || !field ||
+      !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round || !n_claims || !gain || !target_gain)
+    return LIPMPC_E_ARG;
+  if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t ncells = (int64_t)W * H;
+  const bool in_lds = uclaim_fits_lds(ncells);
+  const size_t lds = (size_t)uclaim_lds_bytes(ncells, in_lds);
+  if (in_lds) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_utility_lds_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return LIPMPC_E_HIP;
+    hipLaunchKernelGGL(frontier_assign_utility_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
+                       cell[1], frontier, field, gain, w_gain, g_cap, min_gain, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
+                       S_max, sub_goals, n_sub, status, path_cost, target_cell, target_gain, claim_round, n_claims);
+  } else {
+    hipLaunchKernelGGL(frontier_assign_utility_global_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
+                       cell[1], frontier, field, gain, w_gain, g_cap, min_gain, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
+                       S_max, work, sub_goals, n_sub, status, path_cost, target_cell, target_gain, claim_round, n_claims);
+  }
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
@@ -2571,6 +2813,146 @@ __global__ void __launch_bounds__(SETUP_THREADS) keep_finish_kernel(
   claim_finish_body<true>(B, ctl, claim_round, n_claims, n_kept, claims_settled);
 }
 
+// GAIN-SEEDED CLAIMS by tiles (lipmpc_grid_frontier_assign_utility_tiled_batch): the claim call's kernel sequence with three
+// kernels of its own -- the set-up (sources need gain >= min_gain), the seed (a source starts at its seed, not at 0) and the take
+// (the utility terminal rule, path_cost, target_gain).  The robots, pick and finish kernels and the rounds are the claim call's
+// own, launched as they are; the workspace is that call's, CLAIM_CTL control words.
+__global__ void __launch_bounds__(SETUP_THREADS) utility_assign_setup_kernel(int ncells, int64_t tiles, int max_claims,
+                                                                     const uint8_t* __restrict__ frontier,
+                                                                     const uint32_t* __restrict__ field,
+                                                                     const int32_t* __restrict__ gain, int min_gain,
+                                                                     const int32_t* __restrict__ settled, uint32_t* __restrict__ ctl,
+                                                                     uint32_t* __restrict__ blk, uint32_t* __restrict__ src,
+                                                                     uint32_t* __restrict__ flags) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  const int c = blockIdx.x * SETUP_THREADS + tid, c0 = c - lane;
+  if (c0 < padded) {
+    const bool pass = c < ncells && field[c] != INF;
+    bool source = false;
+    if (pass && frontier[c] != 0) source = gain[c] >= min_gain;
+    const uint64_t mb = __ballot(c < ncells && !pass), ms = __ballot(source);
+    if (lane == 0) {
+      blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32);
+      src[c0 >> 5] = (uint32_t)ms; src[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+    }
+  }
+  if (blockIdx.x == 0) {
+    if (tid < 2) { blk[words - 2 + tid] = 0; src[words - 2 + tid] = 0; }
+    if (tid == 2) {
+      const uint32_t unsettled = settled[0] == 0;
+      ctl[0] = ctl[1] = ctl[CTL_TARGET] = INF;
+      ctl[CTL_STOPPED] = unsettled | (uint32_t)(max_claims == 0);
+      ctl[CTL_CLAIMS] = 0;
+      ctl[CTL_UNSETTLED] = unsettled;
+      ctl[CTL_ROUND_SETTLED] = 1;
+      ctl[CTL_ANY_SOURCE] = 0;
+    }
+  }
+  const int64_t total = 2 * tiles, step = (int64_t)gridDim.x * SETUP_THREADS;
+  for (int64_t k = (int64_t)blockIdx.x * SETUP_THREADS + tid; k < total; k += step) flags[k] = 0;
+}
+
+// claim_seed_body without KEEP, a source starting at its seed (gain is read at source cells of the tile only)
+__global__ void __launch_bounds__(TILE_THREADS) utility_assign_seed_kernel(
+    int W, int H, int tiles_j, uint32_t* __restrict__ ctl, const uint32_t* __restrict__ src, const int32_t* __restrict__ gain, int w_gain,
+    int g_cap, uint32_t* __restrict__ field_k, uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
+  if (ld_agent(ctl + CTL_STOPPED)) return;              // (both flag arrays are clear: whoever stopped the call cleared them)
+  const int tile = blockIdx.x, tid = threadIdx.x;
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  int own = 0, near = 0;
+  for (int l = tid; l < HALO_CELLS; l += TILE_THREADS) {
+    const int li = l / HALO_H, lj = l - li * HALO_H, i = i0 + li - 1, j = j0 + lj - 1;
+    if ((unsigned)i >= (unsigned)W || (unsigned)j >= (unsigned)H) continue;
+    const bool s = bit_of(src, i * H + j);
+    const bool inner = li >= 1 && li <= TILE_W && lj >= 1 && lj <= TILE_H;
+    if (inner) field_k[i * H + j] = s ? gain_seed(gain[i * H + j], w_gain, g_cap) : INF;
+    own |= s & inner;
+    near |= s;
+  }
+  near = __syncthreads_or(near);
+  if (tid == 0) { flags0[tile] = near != 0; flags1[tile] = 0; }
+  if (own) st_agent(ctl + CTL_ANY_SOURCE, 1u);
+}
+
+// claim_take_body without KEEP, with the utility path's terminal test on the source bitmap (S_k until the disc below is cleared),
+// path_cost as the walk's length and target_gain
+__global__ void __launch_bounds__(FIELD_THREADS) utility_assign_take_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, int r_inflate, int r_claim, int max_seg, int S_max, int k,
+    int tiles, uint32_t* ctl, uint32_t* src, const uint32_t* field_k, const int32_t* __restrict__ gain, int w_gain, int g_cap,
+    uint32_t* flags, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* target_gain,
+    int32_t* claim_round) {
+  // what only the walking lane needs, parked in LDS as the one-workgroup kernels park it: held in scalar registers through the
+  // disc loop it would overfill that file
+  __shared__ uint32_t parked[32];
+  auto park = [&](int slot, unsigned long long v) { parked[2 * slot] = (uint32_t)v; parked[2 * slot + 1] = (uint32_t)(v >> 32); };
+  auto unpark = [&](int slot) { return ((unsigned long long)parked[2 * slot + 1] << 32) | parked[2 * slot]; };
+  const int tid = threadIdx.x;
+  const bool stopped = ctl[CTL_STOPPED] != 0, no_source = ctl[CTL_ANY_SOURCE] == 0, unsettled = ctl[CTL_ROUND_SETTLED] == 0;
+  const unsigned long long win = *(const unsigned long long*)ctl;
+  if (tid == 0) {
+    park(0, __double_as_longlong(ox)); park(1, __double_as_longlong(oy)); park(2, __double_as_longlong(dx));
+    park(3, __double_as_longlong(dy));
+    park(4, (unsigned long long)sub_goals); park(5, (unsigned long long)n_sub); park(6, (unsigned long long)status);
+    park(7, (unsigned long long)path_cost); park(8, (unsigned long long)target_cell); park(9, (unsigned long long)target_gain);
+    park(10, (unsigned long long)gain);
+    parked[22] = (uint32_t)w_gain; parked[23] = (uint32_t)g_cap; parked[24] = (uint32_t)max_seg; parked[25] = (uint32_t)S_max;
+  }
+  __syncthreads();                                      // (everybody has read the control words)
+  for (int t = tid; t < 2 * tiles; t += FIELD_THREADS) flags[t] = 0;
+  if (tid == 0) { ctl[0] = ctl[1] = INF; ctl[CTL_ANY_SOURCE] = 0; ctl[CTL_ROUND_SETTLED] = 1; }
+  if (stopped) return;
+  if (no_source || unsettled || win == ~0ull) {         // no source left, a field that did not settle, no candidate
+    if (tid == 0) { ctl[CTL_STOPPED] = 1; if (!no_source && unsettled) ctl[CTL_UNSETTLED] = 1; }
+    return;
+  }
+  const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
+  if (tid == 0) {
+    // one lane walks the winner's path, twice: count, then -- if the sub-goals fit -- write (rows past n_sub stay untouched)
+    const int s = claim_cell(field_k, W, H, -2 - claim_round[wb], r_inflate);
+    const double wox = __longlong_as_double(unpark(0)), woy = __longlong_as_double(unpark(1));
+    const double wdx = __longlong_as_double(unpark(2)), wdy = __longlong_as_double(unpark(3));
+    const int32_t* wgain = (const int32_t*)unpark(10);
+    const int ww = (int)parked[22], wcap = (int)parked[23], wseg = (int)parked[24], wmax = (int)parked[25];
+    auto terminal = [&](int c) { return bit_of(src, c) && ld(field_k + c) == gain_seed(wgain[c], ww, wcap); };
+    double* sg = (double*)unpark(4) + wb * (int64_t)wmax * 2;
+    int last_cell = s, n = 0;
+    for (int pass = 0; s >= 0 && pass < 2 && n >= 0 && n <= wmax; ++pass)
+      n = walk_in_to(field_k, W, H, s, wseg, wox, woy, wdx, wdy, pass ? sg : nullptr, last_cell, terminal);
+    if (n > 0) {
+      if (n <= wmax) centre(last_cell, H, wox, woy, wdx, wdy, sg + 2 * (n - 1));
+      ((int32_t*)unpark(6))[wb] = n <= wmax ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+      ((int32_t*)unpark(5))[wb] = n <= wmax ? n : 0;
+      ((double*)unpark(7))[wb] = (double)(ld(field_k + s) - ld(field_k + last_cell)) / 5.0;
+      ((int32_t*)unpark(8))[wb] = last_cell;
+      ((int32_t*)unpark(9))[wb] = wgain[last_cell];
+      claim_round[wb] = k;
+      ctl[CTL_CLAIMS] = (uint32_t)(k + 1);
+    }
+    ctl[CTL_TARGET] = n > 0 ? (uint32_t)last_cell : INF;
+  }
+  __syncthreads();
+  const uint32_t t = ctl[CTL_TARGET];
+  if (t == INF) {                                       // (a winner always has a descent: a round without one stops the call)
+    if (tid == 0) ctl[CTL_STOPPED] = 1;
+    return;
+  }
+  int eligible = 0;
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) eligible |= claim_round[b] <= -2;
+  const int more = __syncthreads_or(eligible);
+  if (!more) {                                          // U is used up
+    if (tid == 0) ctl[CTL_STOPPED] = 1;
+    return;
+  }
+  // S_{k+1}: the sources outside the winner's disc, clipped to the grid
+  const int ti = (int)t / H, tj = (int)t - ti * H, r2 = r_claim * r_claim;
+  const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
+  for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+    const int i = c / H, j = c - i * H;
+    if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t lipmpc_grid_frontier_gain_tiled_lds_bytes(int32_t r_view) {
@@ -2749,6 +3131,59 @@ extern "C" int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t 
   return claim_tiled(device, B, W, H, origin, cell, frontier, field, settled, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
                      S_max, work, work_bytes, max_rounds, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims,
                      claims_settled, &keep, hip_stream);
+}
+
+extern "C" int64_t lipmpc_grid_frontier_assign_utility_tiled_workspace_bytes(int32_t W, int32_t H) {
+  if (W < 2 || H < 2) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  return claim_bytes(W, H, CLAIM_CTL);
+}
+
+// claim_tiled's sequence without the keep forms: 3 launches round the rounds, and per round the seed, max_rounds rounds and their
+// settle, the pick and the take: max_claims * (max_rounds + 4) + 3
+extern "C" int lipmpc_grid_frontier_assign_utility_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin,
+                                                               const double* cell, const uint8_t* frontier, const uint32_t* field,
+                                                               const int32_t* settled, const double* start, const int8_t* may_claim,
+                                                               int32_t r_inflate, int32_t r_claim, int32_t max_claims, int32_t max_seg,
+                                                               int32_t S_max, void* work, int64_t work_bytes, int32_t max_rounds,
+                                                               double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
+                                                               int32_t* target_cell, int32_t* claim_round, int32_t* n_claims,
+                                                               int32_t* claims_settled, const int32_t* gain, int32_t w_gain,
+                                                               int32_t g_cap, int32_t min_gain, int32_t* target_gain, void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
+      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS ||
+      (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX ||
+      min_gain < 0 || min_gain > G_CAP_MAX || !gain || !target_gain)
+    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  if (work_bytes < claim_bytes(W, H, CLAIM_CTL)) return LIPMPC_E_ARG;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const ClaimLayout c = claim_layout(W, H, CLAIM_CTL);
+  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
+  const dim3 robots((unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS)), setup(SETUP_THREADS), one(1), group(FIELD_THREADS);
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  uint32_t* w = (uint32_t*)work;
+  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
+  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
+  hipLaunchKernelGGL(utility_assign_setup_kernel, dim3((unsigned)chunks), setup, 0, s, ncells, c.tiles, max_claims, frontier, field, gain, min_gain,
+                     settled, w, w + c.blocked, w + c.sources, w + c.flags0);
+  hipLaunchKernelGGL(claim_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round);
+  for (int k = 0; k < max_claims; ++k) {
+    hipLaunchKernelGGL(utility_assign_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, gain, w_gain,
+                       g_cap, w + c.field, w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
+    hipLaunchKernelGGL(claim_pick_kernel, robots, setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+    hipLaunchKernelGGL(utility_assign_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, max_seg, S_max, k, tiles, w,
+                       w + c.sources, w + c.field, gain, w_gain, g_cap, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell,
+                       target_gain, claim_round);
+  }
+  hipLaunchKernelGGL(claim_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, claims_settled);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 
 // =====================================================================================================================

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import inspect
 
 import numpy as np
 import torch
@@ -237,6 +238,13 @@ def informed_outputs(B, F, W, H, S_max):
     i32 = torch.int32
     return dict(frontier_outputs(B, F, W, H, S_max), gain=(i32, (F, W, H), True), ufield=(torch.uint32, (F, W, H), True),
                 n_sources=(i32, (F,), True), target_gain=(i32, (B,), True))
+
+
+def assign_utility_outputs(B, W, H, S_max):
+    """Outputs of a CoordinatedFrontierPlanner with the gain keywords: ``assign_outputs`` plus the informed plan's gain and ufield
+    [1,W,H], n_sources [1] and target_gain [B]."""
+    table = informed_outputs(B, 1, W, H, S_max)
+    return dict(assign_outputs(B, W, H, S_max), **{k: table[k] for k in ("gain", "ufield", "n_sources", "target_gain")})
 
 
 def plan_outputs(B, S_max, max_cells, n_samples):
@@ -730,13 +738,24 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     the NEAREST frontier, not with what the rounds would have handed the robot; followers have no memory; the informed planners
     have none either.
     Keyword-only ``paths`` = "wave" governs the nearest-frontier plan that precedes the claims; the walks inside the claim calls -- a
-    winner's or a keeper's path -- are unchanged, one lane per robot."""
+    winner's or a keeper's path -- are unchanged, one lane per robot.
+    GAIN-SEEDED CLAIMS (keywords ``r_view`` 1..64, ``w_gain`` 0..65535, ``g_cap`` 1..16384, all three or none, no defaults: nobody
+    has measured one; ``min_gain`` 0..16384, default 0; ``lipmpc_grid_frontier_assign_utility_batch``): the robots claim apart
+    what reveals most.  ``plan`` runs frontier field -> gain -> utility field -> utility path (``InformedFrontierPlanner``'s
+    calls and parameters) -> the claim rounds with every round's field seeded as the utility field is and the winner's walk ended
+    as the utility path's is; the discount stays the ``r_claim`` disc, no gain is recomputed after a claim.  The dict gains gain
+    and ufield [1,W,H], n_sources [1] and target_gain [B]; followers keep their utility plan.  ``w_gain`` = 0 with ``min_gain`` =
+    0 gives the plain claims, bit for bit.  ``paths`` = "wave" governs the utility path call only.  There is no hysteresis for
+    these claims: the gain keywords with ``r_keep`` / ``keep_ratio16`` / ``keep_slack``, and ``replan``, raise ValueError; so do
+    ``r_clear`` / ``w_clear`` / ``cost=``, as for every coordinated planner.  Without the keywords the very calls of before are made."""
 
     _TILED, _TILED_WHY, _TILED_CLASS = False, "the claim rounds keep", "TiledCoordinatedFrontierPlanner"
     _CLEARANCE = False
     _FRESH = ("field", "frontier", "n_frontier", "work")            # outputs written whole: a fresh dict gets them uninitialised
     _table = staticmethod(assign_outputs)
     _keep_table = staticmethod(assign_keep_outputs)                 # the table of a planner with ``r_keep``
+    _gain_table = staticmethod(assign_utility_outputs)              # the table of a planner with ``r_view``
+    _informed = None                                                # the class whose gain, utility field and utility path calls run
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
         self.r_claim, self.max_claims = int(r_claim), int(max_claims)
@@ -747,6 +766,28 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         misspelt = sorted(k for k in frontier_planner_kwargs if "keep" in k)
         if misspelt:
             raise TypeError(f"unexpected keyword {misspelt}: the keep parameters are r_keep, keep_ratio16 and keep_slack")
+        # the gain parameters, likewise
+        gain = [frontier_planner_kwargs.pop(k, None) for k in ("r_view", "w_gain", "g_cap", "min_gain")]
+        misspelt = sorted(k for k in frontier_planner_kwargs if any(w in k for w in ("gain", "view", "cap")) or
+                          (gain != [None] * 4 and k not in inspect.signature(FrontierPlanner.__init__).parameters))
+        if misspelt:
+            raise TypeError(f"unexpected keyword {misspelt}: the gain parameters are r_view, w_gain, g_cap and min_gain")
+        if all(v is None for v in gain[:3]):
+            if gain[3] is not None:
+                raise ValueError("min_gain without r_view, w_gain and g_cap: the gain-seeded claims are switched on by those three")
+            self.r_view = self.w_gain = self.g_cap = self.min_gain = None
+        else:
+            if any(v is None for v in gain[:3]):
+                raise ValueError("r_view, w_gain and g_cap go together: they have no defaults, nobody has measured one")
+            if keep != [None, None, None]:
+                raise ValueError("the gain keywords with r_keep / keep_ratio16 / keep_slack: there is no hysteresis for gain-seeded "
+                                 "claims")
+            self.r_view, self.w_gain, self.g_cap, self.min_gain = (int(v) for v in gain[:3] + [gain[3] or 0])
+            if not 1 <= self.r_view <= 64 or not 0 <= self.w_gain <= 65535 or not 1 <= self.g_cap <= 16384 or \
+                    not 0 <= self.min_gain <= 16384:
+                raise ValueError(f"invalid gain parameters (r_view {gain[0]}: 1..64, w_gain {gain[1]}: 0..65535, g_cap {gain[2]}: "
+                                 f"1..16384, min_gain {gain[3]}: 0..16384)")
+            self._table = self._gain_table
         if keep[0] is None:
             if keep[1] is not None or keep[2] is not None:
                 raise ValueError("keep_ratio16 / keep_slack without r_keep: the keep phase is switched on by r_keep")
@@ -761,13 +802,15 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
             self._table = self._keep_table
         super().__init__(**frontier_planner_kwargs)
 
+    @_cost_keyword
     def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None):
         """``FrontierPlanner.plan`` on a shared map (anything else: ValueError), then the claims.  ``may_claim`` [B] (bool or
         integers, None = everybody): the robots that may claim; the others keep their nearest-frontier plan and take nothing
         from anybody.  Returns the parent's dict -- a robot that claimed has the sub_goals, n_sub, status, path_cost, target_cell
         and target of its path to the cell it claimed -- plus claim_round [B] (the round a robot won, -1 for everyone else),
         n_claims [1] and ``work`` [W,H] (the call's scratch).  ``out``: that dict, to write into.
-        With ``r_keep`` set this is ``replan`` with no previous targets."""
+        With ``r_keep`` set this is ``replan`` with no previous targets.  With the gain keywords the plan that precedes the claims is
+        ``InformedFrontierPlanner.plan``'s and the dict gains gain, ufield [1,W,H], n_sources [1] and target_gain [B]."""
         return self._plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, None)
 
     def replan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None, prev_target=None):
@@ -775,6 +818,8 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         ``target_cell`` of the last plan on this same grid, anything outside 0..W*H-1 (-1, say) = none; None = nobody has one.  A
         robot keeps what is left of that target by the keep rule ahead of the claim rounds.  Returns ``plan``'s dict plus kept [B]
         int8 (1 = the robot kept its target; its claim_round counts like a winner's) and n_kept [1]."""
+        if self.r_view is not None:
+            raise ValueError("replan on a planner with the gain keywords: there is no hysteresis for gain-seeded claims")
         if self.r_keep is None:
             raise ValueError("replan needs a planner with r_keep, keep_ratio16 and keep_slack")
         return self._plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target)
@@ -815,8 +860,13 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
                        n_claims=torch.zeros((1,), dtype=torch.int32, device=self.device))
             if self.r_keep is not None:
                 out.update(_alloc(table, ("kept", "n_kept"), self.device, torch.zeros))
+            if self.r_view is not None:
+                out.update(_alloc(table, ("gain", "ufield", "n_sources"), self.device))
+                out["target_gain"] = torch.full((B,), -1, dtype=torch.int32, device=self.device)
         else:
             _check_table(table, out, self.device, "out")
+        if self.r_view is not None:
+            return self._plan_gain(mapper_or_evidence, start, origin, cell, S_max, out, may_claim)
         super().plan(mapper_or_evidence, start, origin, cell, S_max, out)      # (its table is part of this one)
         if B == 0:
             return out
@@ -828,6 +878,34 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         self._target(out, origin, cell, H)
         self.last = out
         return out
+
+    def _plan_gain(self, mapper_or_evidence, start, origin, cell, S_max, out, may_claim):
+        """The gain-seeded plan into ``out``: frontier field -> gain -> utility field -> utility path -> the claims."""
+        informed = self._informed or InformedFrontierPlanner
+        ev, t_free, t_occ, origin, cell = self._map(mapper_or_evidence, origin, cell)
+        origin, cell, org_c, cell_c = self._placement(origin, cell)
+        B, (_, W, H) = start.shape[0], ev.shape
+        if self.tiled:
+            self._settled(out, 1)
+        if B == 0:
+            return out
+        self._classes = t_free, t_occ                      # (what the tiled utility field call classifies the evidence by)
+        self._field(ev, t_free, t_occ, out)
+        informed._gain(self, ev, t_free, t_occ, out)
+        informed._ufield(self, ev, out)
+        informed._path(self, ev, t_occ, start, org_c, cell_c, S_max, out)
+        self._gain_claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out)
+        self._target(out, origin, cell, H)
+        self.last = out
+        return out
+
+    def _gain_claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
+        _lib.call("lipmpc_grid_frontier_assign_utility_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
+                  cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], start=start, may_claim=may_claim,
+                  r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims, max_seg=self.max_seg, S_max=S_max,
+                  work=out["work"], **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
+                  gain=out["gain"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, target_gain=out["target_gain"],
+                  hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
     _none = None                # [>= B] int32 of -1: the prev_target of a plan without one
 
@@ -861,6 +939,14 @@ def tiled_assign_keep_outputs(B, W, H, S_max):
     return dict(tiled_assign_outputs(B, W, H, S_max), kept=(torch.int8, (B,), True), n_kept=(torch.int32, (1,), True))
 
 
+def tiled_assign_utility_outputs(B, W, H, S_max):
+    """Outputs of a TiledCoordinatedFrontierPlanner with the gain keywords: ``assign_utility_outputs`` without ``work`` and with
+    claims_settled; ``settled`` and ``usettled`` [1] come as in ``TiledInformedFrontierPlanner``."""
+    table = assign_utility_outputs(B, W, H, S_max)
+    del table["work"]
+    return dict(table, claims_settled=(torch.int32, (1,), False))
+
+
 CLAIM_MAX_LAUNCHES = 1 << 20    # max_claims * max_rounds of one lipmpc_grid_frontier_assign_tiled_batch
 
 
@@ -886,25 +972,37 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
     ``max_claims``) -- at that cap the dict is returned with ``claims_settled`` 0.
     The cost is fixed by the budget, not by what the fleet needs: ``max_claims`` * (budget + 4) + 3 launches per claim call.  On
     small maps the one-workgroup parent is faster; it stays the default.  The limits that remain: the claim rounds are sequential
-    and not gain-seeded; ``plan`` has no memory between plans.
+    (gain-seeded with the gain keywords, below); ``plan`` has no memory between plans.
     CLAIM HYSTERESIS: ``r_keep``, ``keep_ratio16``, ``keep_slack`` and ``replan(..., prev_target=)`` as the parent's, by
     ``lipmpc_grid_frontier_assign_keep_tiled_batch``: the dict gains kept [B] and n_kept [1], ``rounds`` is the budget of every
-    SLOT (keep attempt or claim round), and a claim call costs ``max_claims`` * (budget + 5) + 3 launches."""
+    SLOT (keep attempt or claim round), and a claim call costs ``max_claims`` * (budget + 5) + 3 launches.
+    GAIN-SEEDED CLAIMS: ``r_view``, ``w_gain``, ``g_cap`` and ``min_gain`` as the parent's, by ``TiledInformedFrontierPlanner``'s calls
+    and ``lipmpc_grid_frontier_assign_utility_tiled_batch``: the dict gains gain, ufield, n_sources, target_gain and ``usettled``
+    [1] (the utility field), ``rounds`` is the budget of the two fields and of every claim round, and a claim call costs
+    ``max_claims`` * (budget + 4) + 3 launches as without the keywords."""
 
     _FRESH = ("field", "frontier", "n_frontier")
     _table = staticmethod(tiled_assign_outputs)
     _keep_table = staticmethod(tiled_assign_keep_outputs)
+    _gain_table = staticmethod(tiled_assign_utility_outputs)
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
         if self.rounds is not None and int(max_claims) * self.rounds > CLAIM_MAX_LAUNCHES:
             raise ValueError(f"max_claims {max_claims} * rounds {self.rounds}: at most 2^20, the launches of one claim call")
         super().__init__(r_claim, max_claims, **frontier_planner_kwargs)
         self._claim_works = []      # the claim call's own workspace: grown only, every buffer kept alive
+        self._uworks = []           # the utility field's own workspace (a planner with the gain keywords)
+        self._informed = self._informed or TiledInformedFrontierPlanner
 
+    @_cost_keyword
     def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None):
         """``CoordinatedFrontierPlanner.plan`` by the tiled calls: its dict without ``work``, plus ``settled`` and ``claims_settled`` [1]."""
+        if self.r_view is not None and out is not None:
+            self._settled(out, 1, "usettled")
         out = super().plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim)
         self._settled(out, 1, "claims_settled")            # (B = 0: no call was made)
+        if self.r_view is not None:
+            self._settled(out, 1, "usettled")
         return out
 
     def replan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None, prev_target=None):
@@ -916,11 +1014,17 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
     def _keep_claims(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out):
         self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target)
 
-    def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target=None):
+    def _gain_claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
+        self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out, gain=True)
+
+    def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target=None, gain=False):
         capturing = torch.cuda.is_current_stream_capturing()
         if self.rounds is None and capturing:
             raise RuntimeError("rounds=None reads `claims_settled` on the host: give the planner a fixed `rounds` to capture its calls")
         name, keep = "lipmpc_grid_frontier_assign_tiled_batch", {}
+        if gain:
+            name = "lipmpc_grid_frontier_assign_utility_tiled_batch"
+            keep = dict(gain=out["gain"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, target_gain=out["target_gain"])
         if prev_target is not None:
             name = "lipmpc_grid_frontier_assign_keep_tiled_batch"
             keep = dict(prev_target=prev_target, r_keep=self.r_keep, keep_ratio16=self.keep_ratio16, keep_slack=self.keep_slack,

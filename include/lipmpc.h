@@ -943,6 +943,60 @@ int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, int64_t F, in
                                             int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                             int32_t* target_cell, int32_t* target_gain, void* hip_stream);
 
+/* lipmpc_grid_frontier_assign_utility_batch (backward-compatible addition): GAIN-SEEDED CLAIMS.  The claim rounds of
+ * lipmpc_grid_frontier_assign_batch seed every round's field with 0, so a robot wins a sliver behind a wall stub as readily as a
+ * cell that faces an open unknown half-plane; the utility path call knows what a cell reveals, but its one shared field herds
+ * robots that stand together.  This call joins the two: the rounds are the assign call's, each round's field is seeded as the
+ * utility field is, and the winner's walk ends as the utility path's does.  The discount stays the r_claim disc: no gain is
+ * recomputed after a claim.  One workgroup does the whole call.
+ * The arguments are lipmpc_grid_frontier_assign_batch's in their order, and ahead of hip_stream:
+ *  gain [W,H] int32: lipmpc_grid_frontier_gain_batch's output (F = 1) -- or any int32 array; only read
+ *  w_gain 0..65535;  g_cap 1..16384;  min_gain 0..16384
+ *  target_gain [B] int32: read, and rewritten for the robots that claim
+ *  sub_goals, n_sub, status, path_cost, target_cell, target_gain: the outputs of lipmpc_grid_frontier_utility_path_batch (F = 1)
+ *    for the same map, gain parameters and start
+ * THE RULE:
+ *  - passable(c) <=> the given field[c] != LIPMPC_FIELD_INF, as in the assign call: `field` is read for passability only.
+ *  - S_0 = the utility field's sources: frontier[c] != 0 && passable(c) && gain[c] >= min_gain (gain[c] as stored).
+ *  - seed(c) = (w_gain * (g_cap - min(max(gain[c], 0), g_cap))) >> 4, the utility field's.
+ *  - U_0 as in the assign call: may_claim[b] != 0 and status[b] FOUND or PATH_OVERFLOW.
+ *  - round k = 0, 1, ... runs while k < max_claims, U_k is not empty and S_k is not empty:
+ *      ufield_k[c] = the least, over s in S_k, of seed(s) + the cost from c to s, relaxed by the call itself, round 0 included.
+ *      every b in U_k: s_b = its start cell if ufield_k is finite there, else the snap in ufield_k (window r_inflate + 1, key
+ *        (d^2, field, index)); cost_b = ufield_k[s_b].  With no candidate the rounds end.
+ *      the winner is the candidate with the least (cost_b, b).  Its rows are written by the path rule of
+ *        lipmpc_grid_frontier_utility_path_batch on ufield_k with terminal(c) <=> c in S_k && ufield_k[c] == seed(c); the
+ *        terminal test is made before a descending neighbour is looked for; descent order, string pulling, max_seg, S_max and
+ *        the centre expression are unchanged.  A PATH_OVERFLOW winner writes nothing to sub_goals and claims like any other.
+ *      for the winner: path_cost = (ufield_k[s_b] - ufield_k[c_L]) / 5.0, target_cell = c_L, target_gain = gain[c_L] as
+ *        stored, claim_round = k.
+ *      S_{k+1} = S_k without the r_claim disc round c_L (clipped to the grid); U_{k+1} = U_k without the winner.
+ *  - every other robot keeps every output the utility path call gave it and gets claim_round = -1.
+ *  - n_claims[0] = the number of rounds that had a winner.
+ *  Hence: with w_gain = 0 and min_gain = 0 every output the two calls share equals lipmpc_grid_frontier_assign_batch's, bit for
+ *  bit, whatever gain holds at or above 0 (a negative stored gain is no source at any min_gain); max_claims = 0 writes only claim_round = -1 and n_claims = 0; the round-0 winner's rows equal what
+ *  the utility path call wrote for it; the targets of two winners are more than r_claim apart; the winning cost_b does not
+ *  decrease from round to round (S only shrinks, so no ufield_k value falls); a min_gain that leaves no source gives
+ *  n_claims = 0; two calls give identical bits.  There is no memory between calls and no hysteresis for these claims.
+ *  COST: the assign call's -- one relaxation of the whole map per claim, sequential.  ufield_k is kept in LDS when it fits
+ *  beside two bitmaps (impassable, S_k) and 34 words (the assign kernels' 22, three more pointers -- gain, target_gain,
+ *  n_claims -- and six scalars: w_gain, g_cap, max_seg, S_max, r_claim, max_claims):
+ *  4 (2 (2 ceil(W H / 64) + 2) + 34 + W H) + 256 <= 163840; a larger map is relaxed in `work`.
+ *  gain stays in global memory and is read at source cells only.
+ * Restated in numpy by tests/assign_utility_oracle.py; the device's outputs equal it bit for bit.
+ * All pointers DEVICE pointers but origin / cell (HOST); asynchronous on hip_stream; no allocation and no host synchronisation,
+ * so the call can be captured in a graph; every refusal is decided on the host before anything is enqueued.
+ * LIPMPC_E_ARG: what lipmpc_grid_frontier_assign_batch refuses as such, w_gain outside 0..65535, g_cap outside 1..16384,
+ *  min_gain outside 0..16384, any null pointer but may_claim.  Then LIPMPC_E_UNSUPPORTED (W * H > 2^17, W > 4096 or H > 4096).
+ *  Then B = 0 enqueues nothing and returns 0. */
+int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                              const uint8_t* frontier, const uint32_t* field, const double* start,
+                                              const int8_t* may_claim, int32_t r_inflate, int32_t r_claim, int32_t max_claims,
+                                              int32_t max_seg, int32_t S_max, uint32_t* work, double* sub_goals, int32_t* n_sub,
+                                              int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                              int32_t* n_claims, const int32_t* gain, int32_t w_gain, int32_t g_cap, int32_t min_gain,
+                                              int32_t* target_gain, void* hip_stream);
+
 /* TILED FIELDS (backward-compatible addition): the two cost-to-go fields above on LARGE maps, relaxed by many workgroups.  The
  * four calls above keep their cap of 2^17 cells and their one workgroup per field; the calls here take any map with
  * W * H <= 2^24 and W, H <= 4096 (a finite field value stays below 7 * 2^24; a WEIGHTED one, SOFT CLEARANCE below, below
@@ -1215,6 +1269,37 @@ int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t B, int32_t 
                                                  int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
                                                  int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled,
                                                  void* hip_stream);
+
+/* lipmpc_grid_frontier_assign_utility_tiled_batch (backward-compatible addition): GAIN-SEEDED CLAIMS on large maps --
+ * lipmpc_grid_frontier_assign_utility_batch's rule, word for word, with every round's field relaxed by tiled rounds.
+ *  The arguments of lipmpc_grid_frontier_assign_tiled_batch in their order and, ahead of hip_stream, gain [W,H], w_gain, g_cap,
+ *  min_gain and target_gain [B] as lipmpc_grid_frontier_assign_utility_batch takes them.  sub_goals .. target_cell and
+ *  target_gain: the outputs of lipmpc_grid_frontier_utility_path_tiled_batch (F = 1).  settled, passability ("the given field[c]
+ *  != INF"), work and its layout, max_rounds and claims_settled are the tiled claim call's; work: at least
+ *  lipmpc_grid_frontier_assign_utility_tiled_workspace_bytes(W, H) bytes, 8-byte aligned.
+ *  The host enqueues lipmpc_grid_frontier_assign_tiled_batch's sequence with three kernels of this call's own in it: the set-up
+ *  (a source needs gain >= min_gain), the claim seed (a source starts at seed(c), not at 0; gain is read at source cells only)
+ *  and the claim (the walk ends by terminal(c) <=> c in S_k && ufield_k[c] == seed(c); path_cost, target_gain).  The robots'
+ *  set-up, the rounds, the settle kernel, the pick and the last kernel are that call's, launched as they are.
+ *  THE COST, whatever the fleet needs: max_claims * (max_rounds + 4) + 3 launches; max_claims * max_rounds <= 2^20.
+ *  - claims_settled[0] == 1: every output equals lipmpc_grid_frontier_assign_utility_batch's, bit for bit.
+ *  - claims_settled[0] == 0: settled[0] == 0 (then n_claims = 0) or some round's field did not settle within max_rounds: the
+ *    claims made so far are exactly the rule's first n_claims rounds, and everyone else keeps the utility plan.  A repeat of the
+ *    whole call with a larger budget reproduces them and goes on (what lipmpc_grid_frontier_assign_tiled_batch says about rows
+ *    applies).
+ *  LIPMPC_E_ARG: what lipmpc_grid_frontier_assign_tiled_batch refuses as such, the three gain parameters out of range, a null
+ *   gain or target_gain.  Then LIPMPC_E_UNSUPPORTED (W * H > 2^24, W > 4096 or H > 4096), then LIPMPC_E_ARG for a work_bytes
+ *   below the size call's, then B = 0 returns 0, as there.
+ * lipmpc_grid_frontier_assign_utility_tiled_workspace_bytes: as lipmpc_grid_frontier_assign_tiled_workspace_bytes. */
+int64_t lipmpc_grid_frontier_assign_utility_tiled_workspace_bytes(int32_t W, int32_t H);
+int lipmpc_grid_frontier_assign_utility_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                                    const uint8_t* frontier, const uint32_t* field, const int32_t* settled,
+                                                    const double* start, const int8_t* may_claim, int32_t r_inflate, int32_t r_claim,
+                                                    int32_t max_claims, int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes,
+                                                    int32_t max_rounds, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                                    double* path_cost, int32_t* target_cell, int32_t* claim_round, int32_t* n_claims,
+                                                    int32_t* claims_settled, const int32_t* gain, int32_t w_gain, int32_t g_cap,
+                                                    int32_t min_gain, int32_t* target_gain, void* hip_stream);
 
 /* WAVE-PER-ROBOT PATH CALLS (backward-compatible addition): the path calls above with one wavefront (64 lanes) walking each
  * robot's path where those walk it in one lane -- the sight tests 64 cells at a time, a descent step in one round of loads.  Every
