@@ -351,7 +351,11 @@ int lipmpc_rollout_batch(lipmpc_handle* h, int64_t B, int32_t k_max, int32_t mpc
  * outputs
  *  obs_xy [B,n_obs_max,v_max,2], obs_nv [B,n_obs_max]: CCW rings of the inferred obstacles, cluster order
  *  n_inferred [B]; overflow [B] = 1 if clusters/vertices did not fit (n_obs_max, v_max), if more than 384 true
- *  obstacles were within range of the robot, or if an env_nv entry exceeded v_env (the surplus is dropped, never read)
+ *  obstacles were within range of the robot, or if an env_nv entry exceeded v_env (the surplus is dropped, never read),
+ *  or if a ring of more than 152 edges was within range of the robot: such a ring is skipped as a whole -- the readings,
+ *  labels and rings are those of the map without it -- and the scan is flagged.  "Within range" is the conservative test the
+ *  scan lists its obstacles by: the ring's bounding circle (round the mean of its vertices) comes within lidar_range.  Of
+ *  more than 384 obstacles within range the first 384 in list order are scanned.
  *  hits [B,resolution,2] (NaN = no reading) or NULL; labels [B,resolution] (-2 no reading, -1 noise, k cluster) or NULL
  */
 int lipmpc_lidar_sense_batch(int device, int64_t B, int32_t resolution, int32_t n_env, int32_t v_env,
