@@ -44,6 +44,12 @@ _ASSIGN = ("device:int B:i64 W:i32 H:i32 origin cell frontier field start may_cl
 _ASSIGN_TILED = ("device:int B:i64 W:i32 H:i32 origin cell frontier field settled start may_claim r_inflate:i32 r_claim:i32 max_claims:i32 "
                  "max_seg:i32 S_max:i32 work work_bytes:i64 max_rounds:i32 sub_goals n_sub status path_cost target_cell claim_round n_claims "
                  "claims_settled")
+_ASSIGN_KEEP = ("device:int B:i64 W:i32 H:i32 origin cell frontier field start may_claim prev_target r_inflate:i32 r_claim:i32 r_keep:i32 "
+                "keep_ratio16:i32 keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work sub_goals n_sub status path_cost target_cell "
+                "claim_round n_claims kept n_kept")
+_ASSIGN_KEEP_TILED = ("device:int B:i64 W:i32 H:i32 origin cell frontier field settled start may_claim prev_target r_inflate:i32 r_claim:i32 "
+                      "r_keep:i32 keep_ratio16:i32 keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work work_bytes:i64 max_rounds:i32 "
+                      "sub_goals n_sub status path_cost target_cell claim_round n_claims kept n_kept claims_settled")
 
 # Every export of include/lipmpc.h with the header's own parameter names: the ONE statement of each argument list on the
 # Python side.  load() binds restype / argtypes from it, call() takes its arguments by these names, and
@@ -101,10 +107,9 @@ SIGNATURES = {
                                                      "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost target_cell hip_stream"),
     "lipmpc_grid_frontier_assign_batch": _sig(C.c_int, f"{_ASSIGN} hip_stream"),
     "lipmpc_grid_frontier_assign_utility_batch": _sig(C.c_int, f"{_ASSIGN} gain w_gain:i32 g_cap:i32 min_gain:i32 target_gain hip_stream"),
-    "lipmpc_grid_frontier_assign_keep_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field start may_claim "
-                                                            "prev_target r_inflate:i32 r_claim:i32 r_keep:i32 keep_ratio16:i32 "
-                                                            "keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work sub_goals n_sub status "
-                                                            "path_cost target_cell claim_round n_claims kept n_kept hip_stream"),
+    "lipmpc_grid_frontier_assign_keep_batch": _sig(C.c_int, f"{_ASSIGN_KEEP} hip_stream"),
+    "lipmpc_grid_frontier_assign_keep_utility_batch": _sig(C.c_int, f"{_ASSIGN_KEEP} gain ufield w_gain:i32 g_cap:i32 min_gain:i32 "
+                                                                    "target_gain hip_stream"),
     "lipmpc_grid_frontier_gain_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 evidence t_free:i32 t_occ:i32 frontier r_view:i32 gain "
                                                      "hip_stream"),
     "lipmpc_grid_frontier_utility_field_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 frontier field gain w_gain:i32 g_cap:i32 "
@@ -155,11 +160,10 @@ SIGNATURES = {
     "lipmpc_grid_frontier_assign_utility_tiled_batch": _sig(C.c_int, f"{_ASSIGN_TILED} gain w_gain:i32 g_cap:i32 min_gain:i32 target_gain "
                                                                      "hip_stream"),
     "lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes": _sig(C.c_int64, "W:i32 H:i32"),
-    "lipmpc_grid_frontier_assign_keep_tiled_batch": _sig(C.c_int, "device:int B:i64 W:i32 H:i32 origin cell frontier field settled start "
-                                                                  "may_claim prev_target r_inflate:i32 r_claim:i32 r_keep:i32 "
-                                                                  "keep_ratio16:i32 keep_slack:i32 max_claims:i32 max_seg:i32 S_max:i32 work "
-                                                                  "work_bytes:i64 max_rounds:i32 sub_goals n_sub status path_cost "
-                                                                  "target_cell claim_round n_claims kept n_kept claims_settled hip_stream"),
+    "lipmpc_grid_frontier_assign_keep_tiled_batch": _sig(C.c_int, f"{_ASSIGN_KEEP_TILED} hip_stream"),
+    "lipmpc_grid_frontier_assign_keep_utility_tiled_workspace_bytes": _sig(C.c_int64, "W:i32 H:i32"),
+    "lipmpc_grid_frontier_assign_keep_utility_tiled_batch": _sig(C.c_int, f"{_ASSIGN_KEEP_TILED} gain ufield usettled w_gain:i32 g_cap:i32 "
+                                                                          "min_gain:i32 target_gain hip_stream"),
     # the wave-per-robot path calls: the weighted / tiled-utility calls' argument lists, cost and settled nullable
     "lipmpc_grid_path_wave_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell occ grid_shared:i32 cost field "
                                                  "field_status settled goal start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub "

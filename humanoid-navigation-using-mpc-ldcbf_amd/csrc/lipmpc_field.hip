@@ -1468,6 +1468,264 @@ __global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_utility_global_
                       claim_round, n_claims);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// claim hysteresis for the gain-seeded claims (lipmpc_grid_frontier_assign_keep_utility_batch): assign_keep_body's slot loop with
+// assign_utility_body's sources, seeds, terminal walk and target_gain -- on a body of its own: every kernel above and its code
+// object stays what it was.  A keep slot's field is a single source, the anchor, that starts at ITS seed, so both sides of the
+// test are utilities: the given `ufield` at the robot's entry into it stands where the keep call reads the given field.
+// LDS: the assign kernels' layout with KEEPU_WORDS in place of ASSIGN_WORDS -- the key, the target and the chunk's next candidate
+// as in the keep kernels; then sixteen parked pairs (the keep body's twelve with `ufield` where the given field was, then gain,
+// target_gain, n_claims and n_kept), ten scalars (keep_ratio16, keep_slack, max_seg, S_max, w_gain, g_cap, r_claim, r_keep,
+// r_inflate, max_claims: what the slot loop reads once a slot), the slot's entry cell and the count of U
+constexpr int KEEPU_WORDS = 48;
+__host__ __device__ inline int64_t keepu_bitmap_words(int64_t ncells) { return 2 * bitmap_words(ncells) + KEEPU_WORDS; }
+__host__ __device__ inline int64_t keepu_lds_bytes(int64_t ncells, bool in_lds) {
+  return 4 * (keepu_bitmap_words(ncells) + (in_lds ? ncells : 0));
+}
+
+inline bool keepu_fits_lds(int64_t ncells) { return keepu_lds_bytes(ncells, true) + LDS_SLACK <= LDS_LIMIT; }
+
+// a value a lane holds for itself, in a vector register: the entry cell and the anchor are the same in all lanes, and with the walk's
+// arithmetic on them done in the scalar file they would overfill it (the bar is no spill of either kind).  No instruction.
+__device__ __forceinline__ int per_lane(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+template <typename FieldPtr>
+__device__ __forceinline__ void assign_keep_utility_body(
+    FieldPtr fld, uint32_t* bm, int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const int32_t* __restrict__ gain, const uint32_t* __restrict__ ufield, int w_gain, int g_cap,
+    int min_gain, const double* __restrict__ start, const int8_t* __restrict__ may_claim, const int32_t* __restrict__ prev_target,
+    int r_inflate, int r_claim, int r_keep, int keep_ratio16, int keep_slack, int max_claims, int max_seg, int S_max,
+    double* __restrict__ sub_goals, int32_t* __restrict__ n_sub, int32_t* __restrict__ status, double* __restrict__ path_cost,
+    int32_t* __restrict__ target_cell, int32_t* __restrict__ target_gain, int32_t* claim_round, int32_t* __restrict__ n_claims,
+    int8_t* __restrict__ kept, int32_t* __restrict__ n_kept) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncells = W * H, words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  uint32_t *blk = bm, *src = bm + words, *tgt = bm + 2 * words + 2, *next = bm + 2 * words + 3;
+  unsigned long long* key = (unsigned long long*)(bm + 2 * words);
+  uint32_t* parked = bm + 2 * words + 4;                  // 64-bit values as word pairs, then the scalars
+  auto park = [&](int slot, unsigned long long v) { parked[2 * slot] = (uint32_t)v; parked[2 * slot + 1] = (uint32_t)(v >> 32); };
+  auto unpark = [&](int slot) { return ((unsigned long long)parked[2 * slot + 1] << 32) | parked[2 * slot]; };
+
+  // U_0, each robot with its start cell (assign_body's encoding in claim_round); nobody has kept anything yet
+  int in_u = 0;
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+    const int sb = status[b];
+    int si = 0, sj = 0, v = -1;
+    if (max_claims > 0 && (sb == LIPMPC_RRT_FOUND || sb == LIPMPC_RRT_PATH_OVERFLOW) && (!may_claim || may_claim[b]) &&
+        cell_of(start[2 * b], start[2 * b + 1], ox, oy, dx, dy, W, H, si, sj))
+      v = -2 - (si * H + sj);
+    claim_round[b] = v;
+    kept[b] = 0;
+    in_u += v <= -2;
+  }
+  int claims = 0, keeps = 0, slots = 0;
+  if (max_claims > 0) {
+    // impassable = the given field is INF; sources = the utility field's: the given frontier, passable, gain >= min_gain
+    for (int c0 = tid - lane; c0 < padded; c0 += FIELD_THREADS) {
+      const int c = c0 + lane;
+      const bool pass = c < ncells && field[c] != INF;
+      bool s = false;
+      if (pass && frontier[c] != 0) s = gain[c] >= min_gain;
+      const uint64_t mb = __ballot(c < ncells && !pass), ms = __ballot(s);
+      if (lane == 0) {
+        blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32);
+        src[c0 >> 5] = (uint32_t)ms; src[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+      }
+    }
+    if (tid < 2) { blk[words - 2 + tid] = 0; src[words - 2 + tid] = 0; }
+    if (tid == 0) {
+      *key = ~0ull;
+      *next = INF;
+      parked[43] = 0;
+      park(0, __double_as_longlong(ox)); park(1, __double_as_longlong(oy)); park(2, __double_as_longlong(dx));
+      park(3, __double_as_longlong(dy));
+      park(4, (unsigned long long)sub_goals); park(5, (unsigned long long)n_sub); park(6, (unsigned long long)status);
+      park(7, (unsigned long long)path_cost); park(8, (unsigned long long)target_cell);
+      park(9, (unsigned long long)kept); park(10, (unsigned long long)ufield); park(11, (unsigned long long)prev_target);
+      park(12, (unsigned long long)gain); park(13, (unsigned long long)target_gain);
+      park(14, (unsigned long long)n_claims); park(15, (unsigned long long)n_kept);
+      parked[32] = (uint32_t)keep_ratio16; parked[33] = (uint32_t)keep_slack; parked[34] = (uint32_t)max_seg; parked[35] = (uint32_t)S_max;
+      parked[36] = (uint32_t)w_gain; parked[37] = (uint32_t)g_cap; parked[38] = (uint32_t)r_claim; parked[39] = (uint32_t)r_keep;
+      parked[40] = (uint32_t)r_inflate; parked[41] = (uint32_t)max_claims;
+    }
+    __syncthreads();
+    // |U|: counted once, one less with every winner -- when the last of U has won, kept or claimed, no further slot is begun
+    if (in_u) atomicAdd(parked + 43, (uint32_t)in_u);
+    __syncthreads();
+    int left = (int)parked[43];
+
+    // (one lane) the rows of robot wb, who enters the slot's field at s and wins as number k: the utility winner's path rule --
+    // in a keep slot (a >= 0) the walk ends at the anchor and nowhere else, in a greedy round at the first source of what is
+    // left that holds its own seed.  Returns the target cell, or -1 (a fixed point always has a descent: it cannot happen)
+    auto write_rows = [&](int64_t wb, int s, int k, int a) {
+      const double wox = __longlong_as_double(unpark(0)), woy = __longlong_as_double(unpark(1));
+      const double wdx = __longlong_as_double(unpark(2)), wdy = __longlong_as_double(unpark(3));
+      const int wmax = (int)parked[35], wseg = (int)parked[34];
+      const int32_t* wgain = (const int32_t*)unpark(12);
+      const int ww = (int)parked[36], wcap = (int)parked[37];
+      auto terminal = [&](int c) { return a >= 0 ? c == a : bit_of(src, c) && ld(fld + c) == gain_seed(wgain[c], ww, wcap); };
+      double* sg = (double*)unpark(4) + wb * (int64_t)wmax * 2;
+      int last_cell = s, n = 0;
+      for (int pass = 0; pass < 2 && n >= 0 && n <= wmax; ++pass)
+        n = walk_in_to(fld, W, H, s, wseg, wox, woy, wdx, wdy, pass ? sg : nullptr, last_cell, terminal);
+      if (n <= 0) return -1;
+      if (n <= wmax) centre(last_cell, H, wox, woy, wdx, wdy, sg + 2 * (n - 1));
+      ((int32_t*)unpark(6))[wb] = n <= wmax ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+      ((int32_t*)unpark(5))[wb] = n <= wmax ? n : 0;
+      ((double*)unpark(7))[wb] = (double)(ld(fld + s) - ld(fld + last_cell)) / 5.0;
+      ((int32_t*)unpark(8))[wb] = last_cell;
+      ((int32_t*)unpark(13))[wb] = wgain[last_cell];
+      claim_round[wb] = k;
+      return last_cell;
+    };
+    // the sources outside the disc of r_claim round cell t, clipped to the grid
+    auto take_disc = [&](int t) {
+      const int rc = (int)parked[38];
+      const int ti = t / H, tj = t - ti * H, r2 = rc * rc;
+      const int i_lo = max(ti - rc, 0), i_hi = min(ti + rc, W - 1);
+      for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+        const int i = c / H, j = c - i * H;
+        if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+      }
+      __syncthreads();
+    };
+
+    // THE SLOTS: assign_keep_body's loop, one for both phases, so that the relaxation and the walk are compiled once
+    auto is_candidate = [&](int64_t b) {
+      return b < B && claim_round[b] <= -2 && is_cell(((const int32_t*)unpark(11))[b], ncells);
+    };
+    int64_t base = 0;
+    int cursor = 0;
+    bool keeping = true, candidate = is_candidate(tid);
+    while (slots < (int)parked[41] && left > 0) {
+      int a = -1;
+      int64_t wb = 0;
+      while (keeping) {
+        if (candidate && tid >= cursor) atomicMin(next, (uint32_t)tid);
+        __syncthreads();
+        const uint32_t nx = *next;
+        __syncthreads();                                  // everybody has read it
+        if (nx == INF) {                                  // the chunk is done
+          base += FIELD_THREADS;
+          cursor = 0;
+          keeping = base < B;
+          candidate = keeping && is_candidate(base + tid);
+          continue;
+        }
+        if (tid == 0) *next = INF;                        // (the next minimum comes at least two barriers on)
+        cursor = (int)nx + 1;
+        wb = base + nx;
+        // the anchor: the source within r_keep of the previous target with the least (d^2, cell)
+        const unsigned long long mine = anchor_key(src, ((const int32_t*)unpark(11))[wb], (int)parked[39], W, H);
+        if (lane == 0 && mine != ~0ull) atomicMin(key, mine);
+        __syncthreads();
+        const unsigned long long found = *key;
+        __syncthreads();                                  // everybody has read it
+        if (found == ~0ull) continue;                     // nothing is left of the target: no slot is spent
+        if (tid == 0) *key = ~0ull;
+        a = (int)(found & 0xFFFFFFFFull);
+        break;
+      }
+      ++slots;
+      // the slot's field: the anchor alone at its seed, or what is left of the sources at theirs
+      int any = 0;
+      {
+        const int32_t* gn = (const int32_t*)unpark(12);
+        const int ww = (int)parked[36], wcap = (int)parked[37];
+        for (int c = tid; c < ncells; c += FIELD_THREADS) {
+          const bool s = a >= 0 ? c == a : bit_of(src, c);
+          st(fld + c, s ? gain_seed(gn[c], ww, wcap) : INF);
+          any |= s;
+        }
+      }
+      if (!__syncthreads_or(any)) break;
+      relax(fld, blk, W, H);
+      if (a < 0) {
+        // the candidates of U, and the least (cost, b) among them
+        unsigned long long mine = ~0ull;
+        for (int64_t b = tid; b < B; b += FIELD_THREADS) {
+          const int v = claim_round[b];
+          if (v > -2) continue;
+          const int s = claim_cell(fld, W, H, -2 - v, (int)parked[40]);
+          if (s >= 0) mine = min(mine, ((unsigned long long)ld(fld + s) << 32) | (unsigned long long)b);
+        }
+        for (int o = 32; o; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor(mine, o));
+        if (lane == 0 && mine != ~0ull) atomicMin(key, mine);
+        __syncthreads();
+        const unsigned long long win = *key;
+        if (win == ~0ull) break;                          // no candidate: the rounds end
+        wb = (int64_t)(win & 0xFFFFFFFFull);
+      }
+      if (tid == 0) {
+        // where wb enters the slot's field; a keeper also has to pass the test, against the given ufield at its entry into that
+        const int cell = -2 - claim_round[wb];
+        const int wr = (int)parked[40];
+        const int s = claim_cell(fld, W, H, cell, wr);
+        bool ok = s >= 0;
+        if (a >= 0) ok = keep_passes(fld, (const uint32_t*)unpark(10), W, H, cell, s, wr, parked[32], parked[33]);
+        parked[42] = ok ? (uint32_t)s : INF;
+      }
+      __syncthreads();
+      const uint32_t entry = parked[42];
+      if (tid == 0) *key = ~0ull;                         // (everybody has read it; the next minimum comes two barriers on)
+      if (entry == INF) {
+        if (a >= 0) continue;                             // not kept: the robot stays in U, the slot is spent
+        break;
+      }
+      if (tid == 0) {
+        const int last = write_rows(wb, per_lane((int)entry), claims, per_lane(a));
+        if (last >= 0 && a >= 0) ((int8_t*)unpark(9))[wb] = 1;
+        *tgt = last >= 0 ? (uint32_t)last : INF;          // (a fixed point always has a descent: INF cannot happen)
+      }
+      __syncthreads();
+      const uint32_t t = *tgt;
+      if (t == INF) break;
+      ++claims;
+      if (a >= 0) ++keeps;
+      if (--left == 0) break;                             // U is used up
+      if (slots >= (int)parked[41]) break;
+      take_disc((int)t);
+    }
+    // the followers: still in U
+    __syncthreads();
+    for (int64_t b = tid; b < B; b += FIELD_THREADS)
+      if (claim_round[b] < -1) claim_round[b] = -1;
+    if (tid == 0) { ((int32_t*)unpark(14))[0] = claims; ((int32_t*)unpark(15))[0] = keeps; }
+  } else if (tid == 0) {
+    n_claims[0] = 0; n_kept[0] = 0;
+  }
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_keep_utility_lds_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const int32_t* __restrict__ gain, const uint32_t* __restrict__ ufield, int w_gain, int g_cap,
+    int min_gain, const double* __restrict__ start, const int8_t* __restrict__ may_claim, const int32_t* __restrict__ prev_target,
+    int r_inflate, int r_claim, int r_keep, int keep_ratio16, int keep_slack, int max_claims, int max_seg, int S_max, double* sub_goals,
+    int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* target_gain, int32_t* claim_round,
+    int32_t* __restrict__ n_claims, int8_t* __restrict__ kept, int32_t* __restrict__ n_kept) {
+  extern __shared__ uint32_t field_lds[];
+  assign_keep_utility_body(field_lds + keepu_bitmap_words((int64_t)W * H), field_lds, B, W, H, ox, oy, dx, dy, frontier, field, gain,
+                           ufield, w_gain, g_cap, min_gain, start, may_claim, prev_target, r_inflate, r_claim, r_keep, keep_ratio16,
+                           keep_slack, max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, target_gain,
+                           claim_round, n_claims, kept, n_kept);
+}
+
+__global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_keep_utility_global_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, const uint8_t* __restrict__ frontier,
+    const uint32_t* __restrict__ field, const int32_t* __restrict__ gain, const uint32_t* __restrict__ ufield, int w_gain, int g_cap,
+    int min_gain, const double* __restrict__ start, const int8_t* __restrict__ may_claim, const int32_t* __restrict__ prev_target,
+    int r_inflate, int r_claim, int r_keep, int keep_ratio16, int keep_slack, int max_claims, int max_seg, int S_max, uint32_t* work,
+    double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* target_gain,
+    int32_t* claim_round, int32_t* __restrict__ n_claims, int8_t* __restrict__ kept, int32_t* __restrict__ n_kept) {
+  extern __shared__ uint32_t field_lds[];
+  assign_keep_utility_body(work, field_lds, B, W, H, ox, oy, dx, dy, frontier, field, gain, ufield, w_gain, g_cap, min_gain, start,
+                           may_claim, prev_target, r_inflate, r_claim, r_keep, keep_ratio16, keep_slack, max_claims, max_seg, S_max,
+                           sub_goals, n_sub, status, path_cost, target_cell, target_gain, claim_round, n_claims, kept, n_kept);
+}
+
 // E_ARG of a grid's placement
 bool bad_placement(const double* origin, const double* cell) {
   if (!origin || !cell) return true;
@@ -1729,6 +1987,43 @@ extern "C" int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, 
     hipLaunchKernelGGL(frontier_assign_utility_global_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
                        cell[1], frontier, field, gain, w_gain, g_cap, min_gain, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
                        S_max, work, sub_goals, n_sub, status, path_cost, target_cell, target_gain, claim_round, n_claims);
+  }
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int lipmpc_grid_frontier_assign_keep_utility_batch(
+    int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell, const uint8_t* frontier, const uint32_t* field,
+    const double* start, const int8_t* may_claim, const int32_t* prev_target, int32_t r_inflate, int32_t r_claim, int32_t r_keep,
+    int32_t keep_ratio16, int32_t keep_slack, int32_t max_claims, int32_t max_seg, int32_t S_max, uint32_t* work, double* sub_goals,
+    int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, int8_t* kept,
+    int32_t* n_kept, const int32_t* gain, const uint32_t* ufield, int32_t w_gain, int32_t g_cap, int32_t min_gain, int32_t* target_gain,
+    void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
+      keep_slack > KEEP_SLACK_MAX || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 ||
+      min_gain > G_CAP_MAX || !frontier || !field || !start || !prev_target || !work || !sub_goals || !n_sub || !status || !path_cost ||
+      !target_cell || !claim_round || !n_claims || !kept || !n_kept || !gain || !ufield || !target_gain)
+    return LIPMPC_E_ARG;
+  if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t ncells = (int64_t)W * H;
+  const bool in_lds = keepu_fits_lds(ncells);
+  const size_t lds = (size_t)keepu_lds_bytes(ncells, in_lds);
+  if (in_lds) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_keep_utility_lds_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return LIPMPC_E_HIP;
+    hipLaunchKernelGGL(frontier_assign_keep_utility_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1],
+                       cell[0], cell[1], frontier, field, gain, ufield, w_gain, g_cap, min_gain, start, may_claim, prev_target, r_inflate,
+                       r_claim, r_keep, keep_ratio16, keep_slack, max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost,
+                       target_cell, target_gain, claim_round, n_claims, kept, n_kept);
+  } else {
+    hipLaunchKernelGGL(frontier_assign_keep_utility_global_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1],
+                       cell[0], cell[1], frontier, field, gain, ufield, w_gain, g_cap, min_gain, start, may_claim, prev_target, r_inflate,
+                       r_claim, r_keep, keep_ratio16, keep_slack, max_claims, max_seg, S_max, work, sub_goals, n_sub, status, path_cost,
+                       target_cell, target_gain, claim_round, n_claims, kept, n_kept);
   }
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
@@ -2953,6 +3248,162 @@ __global__ void __launch_bounds__(FIELD_THREADS) utility_assign_take_kernel(
   }
 }
 
+// CLAIM HYSTERESIS FOR THE GAIN-SEEDED CLAIMS by tiles (lipmpc_grid_frontier_assign_keep_utility_tiled_batch): the tiled keep
+// call's kernel sequence with three kernels of its own -- the set-up (sources need gain >= min_gain; the call is stopped from the
+// start when either given field did not settle), the seed (a keep slot seeds the anchor alone at its seed, a greedy slot what is
+// left of the sources at theirs) and the take (the utility terminal rule, the keep test against `ufield`, path_cost, target_gain).
+// The robots, mode, pick and finish kernels and the rounds are the tiled keep call's own, launched as they are; the workspace is
+// that call's, KEEP_CTL control words.
+__global__ void __launch_bounds__(SETUP_THREADS) keep_utility_setup_kernel(int ncells, int64_t tiles, int max_claims,
+                                                                           const uint8_t* __restrict__ frontier,
+                                                                           const uint32_t* __restrict__ field,
+                                                                           const int32_t* __restrict__ gain, int min_gain,
+                                                                           const int32_t* __restrict__ settled,
+                                                                           const int32_t* __restrict__ usettled,
+                                                                           uint32_t* __restrict__ ctl, uint32_t* __restrict__ blk,
+                                                                           uint32_t* __restrict__ src, uint32_t* __restrict__ flags) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int words = (int)bitmap_words(ncells), padded = (words - 2) * 32;
+  const int c = blockIdx.x * SETUP_THREADS + tid, c0 = c - lane;
+  if (c0 < padded) {
+    const bool pass = c < ncells && field[c] != INF;
+    bool source = false;
+    if (pass && frontier[c] != 0) source = gain[c] >= min_gain;
+    const uint64_t mb = __ballot(c < ncells && !pass), ms = __ballot(source);
+    if (lane == 0) {
+      blk[c0 >> 5] = (uint32_t)mb; blk[(c0 >> 5) + 1] = (uint32_t)(mb >> 32);
+      src[c0 >> 5] = (uint32_t)ms; src[(c0 >> 5) + 1] = (uint32_t)(ms >> 32);
+    }
+  }
+  if (blockIdx.x == 0) {
+    if (tid < 2) { blk[words - 2 + tid] = 0; src[words - 2 + tid] = 0; }
+    if (tid == 2) {
+      const uint32_t unsettled = settled[0] == 0 || usettled[0] == 0;
+      ctl[0] = ctl[1] = ctl[CTL_TARGET] = INF;
+      ctl[CTL_STOPPED] = unsettled | (uint32_t)(max_claims == 0);
+      ctl[CTL_CLAIMS] = 0;
+      ctl[CTL_UNSETTLED] = unsettled;
+      ctl[CTL_ROUND_SETTLED] = 1;
+      ctl[CTL_ANY_SOURCE] = 0;
+    }
+  }
+  const int64_t total = 2 * tiles, step = (int64_t)gridDim.x * SETUP_THREADS;
+  for (int64_t k = (int64_t)blockIdx.x * SETUP_THREADS + tid; k < total; k += step) flags[k] = 0;
+}
+
+// claim_seed_body<KEEP>, a source starting at its seed (gain is read at source cells of the tile only): the anchor alone in a keep
+// slot, what is left of the sources in a greedy one
+__global__ void __launch_bounds__(TILE_THREADS) keep_utility_seed_kernel(
+    int W, int H, int tiles_j, uint32_t* __restrict__ ctl, const uint32_t* __restrict__ src, const int32_t* __restrict__ gain, int w_gain,
+    int g_cap, uint32_t* __restrict__ field_k, uint32_t* __restrict__ flags0, uint32_t* __restrict__ flags1) {
+  if (ld_agent(ctl + CTL_STOPPED)) return;              // (both flag arrays are clear: whoever stopped the call cleared them)
+  const bool keep = ld_agent(ctl + CTL_MODE) != 0;
+  const int anchor = (int)ld_agent(ctl + CTL_ANCHOR);
+  const int tile = blockIdx.x, tid = threadIdx.x;
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j, i0 = ti * TILE_W, j0 = tj * TILE_H;
+  int own = 0, near = 0;
+  for (int l = tid; l < HALO_CELLS; l += TILE_THREADS) {
+    const int li = l / HALO_H, lj = l - li * HALO_H, i = i0 + li - 1, j = j0 + lj - 1;
+    if ((unsigned)i >= (unsigned)W || (unsigned)j >= (unsigned)H) continue;
+    const bool s = keep ? i * H + j == anchor : bit_of(src, i * H + j);
+    const bool inner = li >= 1 && li <= TILE_W && lj >= 1 && lj <= TILE_H;
+    if (inner) field_k[i * H + j] = s ? gain_seed(gain[i * H + j], w_gain, g_cap) : INF;
+    own |= s & inner;
+    near |= s;
+  }
+  near = __syncthreads_or(near);
+  if (tid == 0) { flags0[tile] = near != 0; flags1[tile] = 0; }
+  if (own) st_agent(ctl + CTL_ANY_SOURCE, 1u);
+}
+
+// claim_take_body<KEEP> with utility_assign_take_kernel's walk: in a keep slot the walk ends at the anchor and the robot first has
+// to pass the test against the given `ufield`; in a greedy slot the utility terminal test on the source bitmap; path_cost is the
+// walk's length, target_gain the stored gain of the target
+__global__ void __launch_bounds__(FIELD_THREADS) keep_utility_take_kernel(
+    int64_t B, int W, int H, double ox, double oy, double dx, double dy, int r_inflate, int r_claim, int keep_ratio16, int keep_slack,
+    int max_seg, int S_max, int tiles, uint32_t* ctl, uint32_t* src, const uint32_t* field_k, const uint32_t* __restrict__ ufield,
+    const int32_t* __restrict__ gain, int w_gain, int g_cap, uint32_t* flags, double* sub_goals, int32_t* n_sub, int32_t* status,
+    double* path_cost, int32_t* target_cell, int32_t* target_gain, int32_t* claim_round, int8_t* kept) {
+  // what only the walking lane needs, parked in LDS as the one-workgroup kernels park it
+  __shared__ uint32_t parked[36];
+  auto park = [&](int slot, unsigned long long v) { parked[2 * slot] = (uint32_t)v; parked[2 * slot + 1] = (uint32_t)(v >> 32); };
+  auto unpark = [&](int slot) { return ((unsigned long long)parked[2 * slot + 1] << 32) | parked[2 * slot]; };
+  const int tid = threadIdx.x;
+  const bool stopped = ctl[CTL_STOPPED] != 0, no_source = ctl[CTL_ANY_SOURCE] == 0, unsettled = ctl[CTL_ROUND_SETTLED] == 0;
+  const bool keep = ctl[CTL_MODE] != 0;
+  const int k = (int)ctl[CTL_CLAIMS];
+  const unsigned long long win = *(const unsigned long long*)ctl;
+  if (tid == 0) {
+    park(0, __double_as_longlong(ox)); park(1, __double_as_longlong(oy)); park(2, __double_as_longlong(dx));
+    park(3, __double_as_longlong(dy));
+    park(4, (unsigned long long)sub_goals); park(5, (unsigned long long)n_sub); park(6, (unsigned long long)status);
+    park(7, (unsigned long long)path_cost); park(8, (unsigned long long)target_cell); park(9, (unsigned long long)target_gain);
+    park(10, (unsigned long long)gain); park(11, (unsigned long long)ufield); park(12, (unsigned long long)kept);
+    parked[26] = (uint32_t)w_gain; parked[27] = (uint32_t)g_cap; parked[28] = (uint32_t)max_seg; parked[29] = (uint32_t)S_max;
+    parked[30] = (uint32_t)keep_ratio16; parked[31] = (uint32_t)keep_slack; parked[32] = ctl[CTL_ANCHOR];
+  }
+  __syncthreads();                                      // (everybody has read the control words)
+  for (int t = tid; t < 2 * tiles; t += FIELD_THREADS) flags[t] = 0;
+  if (tid == 0) { ctl[0] = ctl[1] = INF; ctl[CTL_ANY_SOURCE] = 0; ctl[CTL_ROUND_SETTLED] = 1; ctl[CTL_TARGET] = INF; }
+  if (stopped) return;
+  if (no_source || unsettled || (win == ~0ull && !keep)) {      // no source left, a field that did not settle, no candidate
+    if (tid == 0) { ctl[CTL_STOPPED] = 1; if (!no_source && unsettled) ctl[CTL_UNSETTLED] = 1; }
+    return;
+  }
+  if (win == ~0ull) return;                             // a keep slot whose anchor is out of the robot's reach: spent, nothing else
+  const int64_t wb = (int64_t)(win & 0xFFFFFFFFull);
+  __syncthreads();                                      // (lane 0's reset of the target word comes before its new value)
+  if (tid == 0) {
+    // one lane walks the winner's path, twice: count, then -- if the sub-goals fit -- write (rows past n_sub stay untouched)
+    const int cell = -2 - claim_round[wb];
+    const int s = per_lane(claim_cell(field_k, W, H, cell, r_inflate));      // (in vector registers, as in the one-workgroup body)
+    bool ok = s >= 0;                                   // (the pick found the winner's entry in the same words)
+    if (keep) ok = keep_passes(field_k, (const uint32_t*)unpark(11), W, H, cell, s, r_inflate, parked[30], parked[31]);
+    const double wox = __longlong_as_double(unpark(0)), woy = __longlong_as_double(unpark(1));
+    const double wdx = __longlong_as_double(unpark(2)), wdy = __longlong_as_double(unpark(3));
+    const int32_t* wgain = (const int32_t*)unpark(10);
+    const int ww = (int)parked[26], wcap = (int)parked[27], wseg = (int)parked[28], wmax = (int)parked[29];
+    const int a = per_lane(keep ? (int)parked[32] : -1);
+    auto terminal = [&](int c) { return a >= 0 ? c == a : bit_of(src, c) && ld(field_k + c) == gain_seed(wgain[c], ww, wcap); };
+    double* sg = (double*)unpark(4) + wb * (int64_t)wmax * 2;
+    int last_cell = s, n = 0;
+    for (int pass = 0; ok && pass < 2 && n >= 0 && n <= wmax; ++pass)
+      n = walk_in_to(field_k, W, H, s, wseg, wox, woy, wdx, wdy, pass ? sg : nullptr, last_cell, terminal);
+    if (n > 0) {
+      if (n <= wmax) centre(last_cell, H, wox, woy, wdx, wdy, sg + 2 * (n - 1));
+      ((int32_t*)unpark(6))[wb] = n <= wmax ? LIPMPC_RRT_FOUND : LIPMPC_RRT_PATH_OVERFLOW;
+      ((int32_t*)unpark(5))[wb] = n <= wmax ? n : 0;
+      ((double*)unpark(7))[wb] = (double)(ld(field_k + s) - ld(field_k + last_cell)) / 5.0;
+      ((int32_t*)unpark(8))[wb] = last_cell;
+      ((int32_t*)unpark(9))[wb] = wgain[last_cell];
+      claim_round[wb] = k;
+      ctl[CTL_CLAIMS] = (uint32_t)(k + 1);
+      if (keep) { ((int8_t*)unpark(12))[wb] = 1; ctl[CTL_KEPT] += 1; }
+      ctl[CTL_TARGET] = (uint32_t)last_cell;
+    }
+  }
+  __syncthreads();
+  const uint32_t t = ctl[CTL_TARGET];
+  if (t == INF) {                                       // a keeper that failed the test stays in U; (a winner always has a descent:
+    if (tid == 0 && !keep) ctl[CTL_STOPPED] = 1;        // a greedy round without one stops the call, as "U is used up" does)
+    return;
+  }
+  int eligible = 0;
+  for (int64_t b = tid; b < B; b += FIELD_THREADS) eligible |= claim_round[b] <= -2;
+  const int more = __syncthreads_or(eligible);
+  if (!more) {                                          // U is used up
+    if (tid == 0) ctl[CTL_STOPPED] = 1;
+    return;
+  }
+  // S_{k+1}: the sources outside the winner's disc, clipped to the grid
+  const int ti = (int)t / H, tj = (int)t - ti * H, r2 = r_claim * r_claim;
+  const int i_lo = max(ti - r_claim, 0), i_hi = min(ti + r_claim, W - 1);
+  for (int c = i_lo * H + tid; c < (i_hi + 1) * H; c += FIELD_THREADS) {
+    const int i = c / H, j = c - i * H;
+    if (bit_of(src, c) && (i - ti) * (i - ti) + (j - tj) * (j - tj) <= r2) atomicAnd(src + (c >> 5), ~(1u << (c & 31)));
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t lipmpc_grid_frontier_gain_tiled_lds_bytes(int32_t r_view) {
@@ -3183,6 +3634,65 @@ extern "C" int lipmpc_grid_frontier_assign_utility_tiled_batch(int device, int64
                        target_gain, claim_round);
   }
   hipLaunchKernelGGL(claim_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, claims_settled);
+  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+}
+
+extern "C" int64_t lipmpc_grid_frontier_assign_keep_utility_tiled_workspace_bytes(int32_t W, int32_t H) {
+  if (W < 2 || H < 2) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  return claim_bytes(W, H, KEEP_CTL);
+}
+
+// claim_tiled's sequence with the keep forms: 3 launches round the slots, and per slot the mode, the seed, max_rounds rounds and
+// their settle, the pick and the take: max_claims * (max_rounds + 5) + 3
+extern "C" int lipmpc_grid_frontier_assign_keep_utility_tiled_batch(
+    int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell, const uint8_t* frontier, const uint32_t* field,
+    const int32_t* settled, const double* start, const int8_t* may_claim, const int32_t* prev_target, int32_t r_inflate, int32_t r_claim,
+    int32_t r_keep, int32_t keep_ratio16, int32_t keep_slack, int32_t max_claims, int32_t max_seg, int32_t S_max, void* work,
+    int64_t work_bytes, int32_t max_rounds, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+    int32_t* claim_round, int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled, const int32_t* gain,
+    const uint32_t* ufield, const int32_t* usettled, int32_t w_gain, int32_t g_cap, int32_t min_gain, int32_t* target_gain,
+    void* hip_stream) {
+  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
+      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
+      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS ||
+      (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
+    return LIPMPC_E_ARG;
+  if (r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
+      keep_slack > KEEP_SLACK_MAX || !prev_target || !kept || !n_kept)
+    return LIPMPC_E_ARG;
+  if (w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !gain || !ufield ||
+      !usettled || !target_gain)
+    return LIPMPC_E_ARG;
+  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  if (work_bytes < claim_bytes(W, H, KEEP_CTL)) return LIPMPC_E_ARG;
+  if (B == 0) return LIPMPC_OK;
+  if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const ClaimLayout c = claim_layout(W, H, KEEP_CTL);
+  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
+  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
+  const dim3 robots((unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS)), setup(SETUP_THREADS), one(1), group(FIELD_THREADS);
+  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
+  uint32_t* w = (uint32_t*)work;
+  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
+  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
+  hipLaunchKernelGGL(keep_utility_setup_kernel, dim3((unsigned)chunks), setup, 0, s, ncells, c.tiles, max_claims, frontier, field, gain,
+                     min_gain, settled, usettled, w, w + c.blocked, w + c.sources, w + c.flags0);
+  hipLaunchKernelGGL(keep_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round,
+                     kept, w);
+  for (int slot = 0; slot < max_claims; ++slot) {
+    hipLaunchKernelGGL(keep_mode_kernel, one, group, 0, s, B, W, H, r_keep, w, w + c.sources, claim_round, prev_target);
+    hipLaunchKernelGGL(keep_utility_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, gain,
+                       w_gain, g_cap, w + c.field, w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
+    hipLaunchKernelGGL(keep_pick_kernel, robots, setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+    hipLaunchKernelGGL(keep_utility_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, keep_ratio16, keep_slack,
+                       max_seg, S_max, tiles, w, w + c.sources, w + c.field, ufield, gain, w_gain, g_cap, w + c.flags0, sub_goals, n_sub,
+                       status, path_cost, target_cell, target_gain, claim_round, kept);
+  }
+  hipLaunchKernelGGL(keep_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, n_kept, claims_settled);
   return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
 }
 

@@ -247,6 +247,11 @@ def assign_utility_outputs(B, W, H, S_max):
     return dict(assign_outputs(B, W, H, S_max), **{k: table[k] for k in ("gain", "ufield", "n_sources", "target_gain")})
 
 
+def assign_keep_utility_outputs(B, W, H, S_max):
+    """Outputs of GainKeepFrontierPlanner.plan / replan: ``assign_utility_outputs`` plus who kept the last target and how many."""
+    return dict(assign_utility_outputs(B, W, H, S_max), kept=(torch.int8, (B,), True), n_kept=(torch.int32, (1,), True))
+
+
 def plan_outputs(B, S_max, max_cells, n_samples):
     """Outputs of a plan, in the order RrtStarPlanner.plan_batch returns them."""
     f64, i32 = torch.float64, torch.int32
@@ -746,8 +751,9 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     as the utility path's is; the discount stays the ``r_claim`` disc, no gain is recomputed after a claim.  The dict gains gain
     and ufield [1,W,H], n_sources [1] and target_gain [B]; followers keep their utility plan.  ``w_gain`` = 0 with ``min_gain`` =
     0 gives the plain claims, bit for bit.  ``paths`` = "wave" governs the utility path call only.  There is no hysteresis for
-    these claims: the gain keywords with ``r_keep`` / ``keep_ratio16`` / ``keep_slack``, and ``replan``, raise ValueError; so do
-    ``r_clear`` / ``w_clear`` / ``cost=``, as for every coordinated planner.  Without the keywords the very calls of before are made."""
+    these claims in this class: the gain keywords with ``r_keep`` / ``keep_ratio16`` / ``keep_slack``, and ``replan``, raise
+    ValueError -- the class with both is ``GainKeepFrontierPlanner``; so do ``r_clear`` / ``w_clear`` / ``cost=``, as for every
+    coordinated planner.  Without the keywords the very calls of before are made."""
 
     _TILED, _TILED_WHY, _TILED_CLASS = False, "the claim rounds keep", "TiledCoordinatedFrontierPlanner"
     _CLEARANCE = False
@@ -755,6 +761,8 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
     _table = staticmethod(assign_outputs)
     _keep_table = staticmethod(assign_keep_outputs)                 # the table of a planner with ``r_keep``
     _gain_table = staticmethod(assign_utility_outputs)              # the table of a planner with ``r_view``
+    _gain_keep_table = staticmethod(assign_keep_utility_outputs)    # the table of a planner with both (_GAIN_KEEP)
+    _GAIN_KEEP, _GAIN_KEEP_CLASS = False, "GainKeepFrontierPlanner"  # True: the subclass whose claims have both
     _informed = None                                                # the class whose gain, utility field and utility path calls run
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
@@ -779,9 +787,9 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         else:
             if any(v is None for v in gain[:3]):
                 raise ValueError("r_view, w_gain and g_cap go together: they have no defaults, nobody has measured one")
-            if keep != [None, None, None]:
-                raise ValueError("the gain keywords with r_keep / keep_ratio16 / keep_slack: there is no hysteresis for gain-seeded "
-                                 "claims")
+            if keep != [None, None, None] and not self._GAIN_KEEP:
+                raise ValueError(f"the gain keywords with r_keep / keep_ratio16 / keep_slack: there is no hysteresis for gain-seeded "
+                                 f"claims in {type(self).__name__}; the class with both is {self._GAIN_KEEP_CLASS}")
             self.r_view, self.w_gain, self.g_cap, self.min_gain = (int(v) for v in gain[:3] + [gain[3] or 0])
             if not 1 <= self.r_view <= 64 or not 0 <= self.w_gain <= 65535 or not 1 <= self.g_cap <= 16384 or \
                     not 0 <= self.min_gain <= 16384:
@@ -799,7 +807,7 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
             if not 0 <= self.r_keep <= 64 or not 16 <= self.keep_ratio16 <= 1024 or not 0 <= self.keep_slack <= 4096:
                 raise ValueError(f"invalid keep parameters (r_keep {keep[0]}: 0..64, keep_ratio16 {keep[1]}: 16..1024, "
                                  f"keep_slack {keep[2]}: 0..4096)")
-            self._table = self._keep_table
+            self._table = self._keep_table if self.r_view is None else self._gain_keep_table
         super().__init__(**frontier_planner_kwargs)
 
     @_cost_keyword
@@ -818,8 +826,9 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         ``target_cell`` of the last plan on this same grid, anything outside 0..W*H-1 (-1, say) = none; None = nobody has one.  A
         robot keeps what is left of that target by the keep rule ahead of the claim rounds.  Returns ``plan``'s dict plus kept [B]
         int8 (1 = the robot kept its target; its claim_round counts like a winner's) and n_kept [1]."""
-        if self.r_view is not None:
-            raise ValueError("replan on a planner with the gain keywords: there is no hysteresis for gain-seeded claims")
+        if self.r_view is not None and not self._GAIN_KEEP:
+            raise ValueError(f"replan on a planner with the gain keywords: there is no hysteresis for gain-seeded claims in "
+                             f"{type(self).__name__}; the class with both is {self._GAIN_KEEP_CLASS}")
         if self.r_keep is None:
             raise ValueError("replan needs a planner with r_keep, keep_ratio16 and keep_slack")
         return self._plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target)
@@ -866,7 +875,7 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         else:
             _check_table(table, out, self.device, "out")
         if self.r_view is not None:
-            return self._plan_gain(mapper_or_evidence, start, origin, cell, S_max, out, may_claim)
+            return self._plan_gain(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target)
         super().plan(mapper_or_evidence, start, origin, cell, S_max, out)      # (its table is part of this one)
         if B == 0:
             return out
@@ -879,8 +888,9 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         self.last = out
         return out
 
-    def _plan_gain(self, mapper_or_evidence, start, origin, cell, S_max, out, may_claim):
-        """The gain-seeded plan into ``out``: frontier field -> gain -> utility field -> utility path -> the claims."""
+    def _plan_gain(self, mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target=None):
+        """The gain-seeded plan into ``out``: frontier field -> gain -> utility field -> utility path -> the claims (with ``r_keep``:
+        the keep phase and the claims, ``prev_target`` as ``_plan`` made it)."""
         informed = self._informed or InformedFrontierPlanner
         ev, t_free, t_occ, origin, cell = self._map(mapper_or_evidence, origin, cell)
         origin, cell, org_c, cell_c = self._placement(origin, cell)
@@ -894,7 +904,10 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
         informed._gain(self, ev, t_free, t_occ, out)
         informed._ufield(self, ev, out)
         informed._path(self, ev, t_occ, start, org_c, cell_c, S_max, out)
-        self._gain_claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out)
+        if self.r_keep is None:
+            self._gain_claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out)
+        else:
+            self._gain_keep_claims(B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out)
         self._target(out, origin, cell, H)
         self.last = out
         return out
@@ -906,6 +919,16 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
                   work=out["work"], **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
                   gain=out["gain"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, target_gain=out["target_gain"],
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _gain_keep_claims(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out):
+        _lib.call("lipmpc_grid_frontier_assign_keep_utility_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
+                  cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], start=start, may_claim=may_claim,
+                  prev_target=prev_target, r_inflate=self.r_inflate, r_claim=self.r_claim, r_keep=self.r_keep,
+                  keep_ratio16=self.keep_ratio16, keep_slack=self.keep_slack, max_claims=self.max_claims, max_seg=self.max_seg,
+                  S_max=S_max, work=out["work"],
+                  **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims", "kept", "n_kept")),
+                  gain=out["gain"], ufield=out["ufield"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain,
+                  target_gain=out["target_gain"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
     _none = None                # [>= B] int32 of -1: the prev_target of a plan without one
 
@@ -924,6 +947,41 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
                   r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims, max_seg=self.max_seg, S_max=S_max,
                   work=out["work"], **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class GainKeepFrontierPlanner(CoordinatedFrontierPlanner):
+    """``CoordinatedFrontierPlanner`` with the gain keywords AND claim hysteresis (include/lipmpc.h,
+    lipmpc_grid_frontier_assign_keep_utility_batch): the far, high-gain targets that the gain-seeded claims hand out jump between
+    replans; here a robot keeps what is left of its last target -- the source of the current replan nearest to it within ``r_keep``
+    cells -- when, as a utility (the anchor's own seed plus the cost to it), it is at most ``keep_ratio16`` / 16 times the robot's
+    value in the shared utility field plus ``keep_slack`` cells.  A target whose gain has fallen pays for it through its seed; a
+    keeper takes its disc like a winner; keep attempts and rounds share the ``max_claims`` relaxations; the rounds that follow are
+    the gain-seeded ones.  ``plan()`` and ``replan(..., prev_target=)`` run frontier field -> gain -> utility field -> utility path
+    -> that call; the dict is the gain-seeded planner's plus kept [B] int8 and n_kept [1].
+    Every keyword is the parent's and none but ``min_gain`` has a default: nobody has measured one.  ``paths`` = "wave" governs the
+    utility path call only; ``r_clear`` / ``w_clear`` / ``cost=`` raise ValueError, as for every coordinated planner.  With no
+    previous targets the plan is the gain-seeded parent's, bit for bit; with ``w_gain`` = 0 and ``min_gain`` = 0 it is the parent's
+    with ``r_keep``.  The large-map class is ``TiledGainKeepFrontierPlanner``."""
+
+    _GAIN_KEEP = True
+    _TILED_CLASS = "TiledGainKeepFrontierPlanner"
+
+    def __init__(self, r_claim: int, max_claims: int = 64, *, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, r_keep: int,
+                 keep_ratio16: int, keep_slack: int, **frontier_planner_kwargs):
+        _gain_keep_init(super(), r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack,
+                        frontier_planner_kwargs)
+
+
+def _gain_keep_init(parent, r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack, kwargs):
+    """What the two gain-keep classes' ``__init__`` share: every parameter is required (a None is as good as none), then the parent's
+    checks and ranges."""
+    given = dict(r_view=r_view, w_gain=w_gain, g_cap=g_cap, min_gain=min_gain, r_keep=r_keep, keep_ratio16=keep_ratio16,
+                 keep_slack=keep_slack)
+    missing = sorted(k for k, v in given.items() if v is None and k != "min_gain")
+    if missing:
+        raise ValueError(f"{missing} None: r_view, w_gain, g_cap, r_keep, keep_ratio16 and keep_slack have no defaults, nobody has "
+                         f"measured one")
+    parent.__init__(r_claim, max_claims, **given, **kwargs)
 
 
 def tiled_assign_outputs(B, W, H, S_max):
@@ -945,6 +1003,11 @@ def tiled_assign_utility_outputs(B, W, H, S_max):
     table = assign_utility_outputs(B, W, H, S_max)
     del table["work"]
     return dict(table, claims_settled=(torch.int32, (1,), False))
+
+
+def tiled_assign_keep_utility_outputs(B, W, H, S_max):
+    """Outputs of TiledGainKeepFrontierPlanner.plan / replan: ``tiled_assign_utility_outputs`` plus kept and n_kept."""
+    return dict(tiled_assign_utility_outputs(B, W, H, S_max), kept=(torch.int8, (B,), True), n_kept=(torch.int32, (1,), True))
 
 
 CLAIM_MAX_LAUNCHES = 1 << 20    # max_claims * max_rounds of one lipmpc_grid_frontier_assign_tiled_batch
@@ -979,12 +1042,15 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
     GAIN-SEEDED CLAIMS: ``r_view``, ``w_gain``, ``g_cap`` and ``min_gain`` as the parent's, by ``TiledInformedFrontierPlanner``'s calls
     and ``lipmpc_grid_frontier_assign_utility_tiled_batch``: the dict gains gain, ufield, n_sources, target_gain and ``usettled``
     [1] (the utility field), ``rounds`` is the budget of the two fields and of every claim round, and a claim call costs
-    ``max_claims`` * (budget + 4) + 3 launches as without the keywords."""
+    ``max_claims`` * (budget + 4) + 3 launches as without the keywords.  The gain keywords together with the keep keywords raise
+    ValueError here: the class with both is ``TiledGainKeepFrontierPlanner``."""
 
     _FRESH = ("field", "frontier", "n_frontier")
     _table = staticmethod(tiled_assign_outputs)
     _keep_table = staticmethod(tiled_assign_keep_outputs)
     _gain_table = staticmethod(tiled_assign_utility_outputs)
+    _gain_keep_table = staticmethod(tiled_assign_keep_utility_outputs)
+    _GAIN_KEEP_CLASS = "TiledGainKeepFrontierPlanner"
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
         if self.rounds is not None and int(max_claims) * self.rounds > CLAIM_MAX_LAUNCHES:
@@ -1007,8 +1073,12 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
 
     def replan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None, may_claim=None, prev_target=None):
         """``CoordinatedFrontierPlanner.replan`` by the tiled calls: its dict without ``work``, plus ``settled`` and ``claims_settled`` [1]."""
+        if self.r_view is not None and out is not None:
+            self._settled(out, 1, "usettled")
         out = super().replan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target)
         self._settled(out, 1, "claims_settled")            # (B = 0: no call was made)
+        if self.r_view is not None:
+            self._settled(out, 1, "usettled")
         return out
 
     def _keep_claims(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out):
@@ -1016,6 +1086,9 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
 
     def _gain_claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
         self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out, gain=True)
+
+    def _gain_keep_claims(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out):
+        self._claims(B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target, gain=True)
 
     def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target=None, gain=False):
         capturing = torch.cuda.is_current_stream_capturing()
@@ -1026,9 +1099,11 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
             name = "lipmpc_grid_frontier_assign_utility_tiled_batch"
             keep = dict(gain=out["gain"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, target_gain=out["target_gain"])
         if prev_target is not None:
-            name = "lipmpc_grid_frontier_assign_keep_tiled_batch"
-            keep = dict(prev_target=prev_target, r_keep=self.r_keep, keep_ratio16=self.keep_ratio16, keep_slack=self.keep_slack,
+            name = "lipmpc_grid_frontier_assign_keep_utility_tiled_batch" if gain else "lipmpc_grid_frontier_assign_keep_tiled_batch"
+            keep = dict(keep, prev_target=prev_target, r_keep=self.r_keep, keep_ratio16=self.keep_ratio16, keep_slack=self.keep_slack,
                         kept=out["kept"], n_kept=out["n_kept"])
+            if gain:
+                keep.update(ufield=out["ufield"], usettled=out["usettled"])
         size = name.replace("_batch", "_workspace_bytes")
         work = self._workspace(self._claim_works, int(getattr(self.lib, size)(W, H)), size)
         done = self._settled(out, 1, "claims_settled")
@@ -1050,6 +1125,23 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
         while budget < cap and not bool(done[0]):
             budget = min(2 * budget, cap)
             call(budget)                                   # (the whole call again: it reproduces the rounds made so far and goes on)
+
+
+class TiledGainKeepFrontierPlanner(TiledCoordinatedFrontierPlanner):
+    """``GainKeepFrontierPlanner`` on maps of up to 2^24 cells, by ``TiledInformedFrontierPlanner``'s calls and
+    ``lipmpc_grid_frontier_assign_keep_utility_tiled_batch``: its dict without ``work``, plus ``settled`` [1] (the nearest-frontier
+    field), ``usettled`` [1] (the utility field) and ``claims_settled`` [1] -- 1 = every slot settled and every output is
+    ``GainKeepFrontierPlanner``'s, bit for bit; 0 = one of the two given fields or some slot's field did not settle within the
+    budget: then the keeps and claims made so far are the rule's first ``n_claims`` winners and everyone else keeps the utility plan.
+    ``rounds`` as ``TiledCoordinatedFrontierPlanner``'s: the budget of the two fields and of every SLOT (keep attempt or claim
+    round); a claim call costs ``max_claims`` * (budget + 5) + 3 launches.  No keyword but ``min_gain`` has a default."""
+
+    _GAIN_KEEP = True
+
+    def __init__(self, r_claim: int, max_claims: int = 64, *, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, r_keep: int,
+                 keep_ratio16: int, keep_slack: int, **frontier_planner_kwargs):
+        _gain_keep_init(super(), r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack,
+                        frontier_planner_kwargs)
 
 
 class InformedFrontierPlanner(FrontierPlanner):

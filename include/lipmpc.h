@@ -981,7 +981,8 @@ int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, int64_t F, in
  *  bit, whatever gain holds at or above 0 (a negative stored gain is no source at any min_gain); max_claims = 0 writes only claim_round = -1 and n_claims = 0; the round-0 winner's rows equal what
  *  the utility path call wrote for it; the targets of two winners are more than r_claim apart; the winning cost_b does not
  *  decrease from round to round (S only shrinks, so no ufield_k value falls); a min_gain that leaves no source gives
- *  n_claims = 0; two calls give identical bits.  There is no memory between calls and no hysteresis for these claims.
+ *  n_claims = 0; two calls give identical bits.  There is no memory between calls and no hysteresis for these claims
+ *  in this call: lipmpc_grid_frontier_assign_keep_utility_batch, below, is the keep phase on these sources and seeds.
  *  COST: the assign call's -- one relaxation of the whole map per claim, sequential.  ufield_k is kept in LDS when it fits
  *  beside two bitmaps (impassable, S_k) and 34 words (the assign kernels' 22, three more pointers -- gain, target_gain,
  *  n_claims -- and six scalars: w_gain, g_cap, max_seg, S_max, r_claim, max_claims):
@@ -1000,6 +1001,62 @@ int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, int32_t W, 
                                               int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
                                               int32_t* n_claims, const int32_t* gain, int32_t w_gain, int32_t g_cap, int32_t min_gain,
                                               int32_t* target_gain, void* hip_stream);
+
+/* lipmpc_grid_frontier_assign_keep_utility_batch (backward-compatible addition): CLAIM HYSTERESIS FOR THE GAIN-SEEDED CLAIMS.
+ * lipmpc_grid_frontier_assign_keep_batch's rule on lipmpc_grid_frontier_assign_utility_batch's sources, seeds and fields: the far,
+ * high-gain targets that the gain-seeded claims hand out jump between replans, and a robot that had one keeps what is left of
+ * it while it is still a source and, as a utility, not much worse than the best the robot could have.  One workgroup does the
+ * whole call.
+ * The arguments are lipmpc_grid_frontier_assign_keep_batch's in their order, and ahead of hip_stream:
+ *  gain [W,H] int32: lipmpc_grid_frontier_gain_batch's output (F = 1) -- or any int32 array; only read
+ *  ufield [W,H] uint32: lipmpc_grid_frontier_utility_field_batch's output (F = 1) for the same map and gain parameters; only read
+ *  w_gain 0..65535;  g_cap 1..16384;  min_gain 0..16384
+ *  target_gain [B] int32: read, and rewritten for the robots that keep or claim
+ *  sub_goals, n_sub, status, path_cost, target_cell, target_gain: the outputs of lipmpc_grid_frontier_utility_path_batch (F = 1)
+ *    for the same map, gain parameters and start, as for lipmpc_grid_frontier_assign_utility_batch
+ * THE RULE:
+ *  - passable(c), S_0 (frontier[c] != 0 && passable(c) && gain[c] >= min_gain, gain as stored), seed(c) and U_0 are exactly
+ *    lipmpc_grid_frontier_assign_utility_batch's.  Slots, k, claim_round, n_claims, kept and n_kept are exactly
+ *    lipmpc_grid_frontier_assign_keep_batch's.
+ *  - keep phase: the candidates and their order are the keep call's.
+ *      ANCHOR a_b = the cell of the current S within r_keep of the previous target with the least (d^2, cell index): the keep
+ *        call's key, unchanged, on this call's S.  None: b is skipped and no slot is spent.
+ *      one slot is spent.  keepfield[c] = seed(a_b) + the cost from c to a_b: a single source that starts at its seed.
+ *      ENTRY s_b as in a round (the start cell if keepfield is finite there, else the snap in keepfield).  None: b is not kept.
+ *      near_b = the given ufield at the robot's entry into the GIVEN ufield (its start cell if finite there, else the snap
+ *        there; none: b is not kept).  b keeps its target iff, in 64 bits,
+ *            16 * keepfield[s_b] <= keep_ratio16 * near_b + 80 * keep_slack
+ *        Both sides are utilities, so a target whose gain has fallen pays for it through its seed.
+ *      on success the rows are written by the utility winner's path rule on keepfield with terminal(c) <=> c == a_b;
+ *        path_cost = (keepfield[s_b] - keepfield[a_b]) / 5.0, target_cell = a_b, target_gain = gain[a_b] as stored,
+ *        claim_round[b] = k, kept[b] = 1; S loses the r_claim disc round a_b and U loses b.
+ *      a failed attempt spends its slot and changes nothing else.
+ *  - greedy phase: lipmpc_grid_frontier_assign_utility_batch's rounds on what is left of S, U and the slots.
+ *  Hence: with every prev_target "none" every output the calls share equals lipmpc_grid_frontier_assign_utility_batch's, bit for
+ *  bit (kept and n_kept are 0); with w_gain = 0, min_gain = 0 and stored gains >= 0 (then ufield == field) every output equals
+ *  lipmpc_grid_frontier_assign_keep_batch's, bit for bit, kept and n_kept included; the targets of two winners, kept or
+ *  claimed, are more than r_claim apart; two calls give identical bits.  No addition wraps: a seed is below 2^26 and a finite cost
+ *  below 7 * 2^24, and 16 (2^26 + 7 * 2^24) and 1024 (2^26 + 7 * 2^24) fit 64 bits with room to spare.
+ *  COST: the keep call's -- one relaxation per slot.  The slot's field is kept in LDS when it fits beside two bitmaps
+ *  (impassable, S) and 48 words (the keep kernels' 34 with ufield in the given field's place, four more pointers -- gain,
+ *  target_gain, n_claims, n_kept, a word pair each -- and six more scalars -- w_gain, g_cap, r_claim, r_keep, r_inflate,
+ *  max_claims):
+ *  4 (2 (2 ceil(W H / 64) + 2) + 48 + W H) + 256 <= 163840; a larger map is relaxed in `work`.
+ *  gain stays in global memory and is read at source cells only.
+ * Restated in numpy by tests/assign_keep_utility_oracle.py; the device's outputs equal it bit for bit.
+ * All pointers DEVICE pointers but origin / cell (HOST); asynchronous on hip_stream; no allocation and no host synchronisation,
+ * so the call can be captured in a graph; every refusal is decided on the host before anything is enqueued.
+ * LIPMPC_E_ARG: what lipmpc_grid_frontier_assign_keep_batch and lipmpc_grid_frontier_assign_utility_batch refuse as such, a
+ *  null gain, ufield or target_gain.  Then LIPMPC_E_UNSUPPORTED and B = 0 as there. */
+int lipmpc_grid_frontier_assign_keep_utility_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                                   const uint8_t* frontier, const uint32_t* field, const double* start,
+                                                   const int8_t* may_claim, const int32_t* prev_target, int32_t r_inflate,
+                                                   int32_t r_claim, int32_t r_keep, int32_t keep_ratio16, int32_t keep_slack,
+                                                   int32_t max_claims, int32_t max_seg, int32_t S_max, uint32_t* work, double* sub_goals,
+                                                   int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+                                                   int32_t* claim_round, int32_t* n_claims, int8_t* kept, int32_t* n_kept,
+                                                   const int32_t* gain, const uint32_t* ufield, int32_t w_gain, int32_t g_cap,
+                                                   int32_t min_gain, int32_t* target_gain, void* hip_stream);
 
 /* TILED FIELDS (backward-compatible addition): the two cost-to-go fields above on LARGE maps, relaxed by many workgroups.  The
  * four calls above keep their cap of 2^17 cells and their one workgroup per field; the calls here take any map with
@@ -1304,6 +1361,43 @@ int lipmpc_grid_frontier_assign_utility_tiled_batch(int device, int64_t B, int32
                                                     double* path_cost, int32_t* target_cell, int32_t* claim_round, int32_t* n_claims,
                                                     int32_t* claims_settled, const int32_t* gain, int32_t w_gain, int32_t g_cap,
                                                     int32_t min_gain, int32_t* target_gain, void* hip_stream);
+
+/* lipmpc_grid_frontier_assign_keep_utility_tiled_batch (backward-compatible addition): CLAIM HYSTERESIS FOR THE GAIN-SEEDED
+ * CLAIMS on large maps -- lipmpc_grid_frontier_assign_keep_utility_batch's rule, word for word, with every slot's field relaxed by
+ * tiled rounds.
+ *  The arguments of lipmpc_grid_frontier_assign_keep_tiled_batch in their order and, ahead of hip_stream, gain [W,H], ufield
+ *  [W,H], usettled [1] int32 (the `settled` word of the lipmpc_grid_frontier_utility_field_tiled_batch call that made ufield),
+ *  w_gain, g_cap, min_gain and target_gain [B] as lipmpc_grid_frontier_assign_keep_utility_batch takes them.  sub_goals ..
+ *  target_cell and target_gain: the outputs of lipmpc_grid_frontier_utility_path_tiled_batch (F = 1).  work: at least
+ *  lipmpc_grid_frontier_assign_keep_utility_tiled_workspace_bytes(W, H) bytes, 8-byte aligned: the tiled keep call's layout.
+ *  The host enqueues lipmpc_grid_frontier_assign_keep_tiled_batch's fixed sequence with three kernels of this call's own in it:
+ *  the set-up (a source needs gain >= min_gain), the seed (a keep slot seeds the anchor alone at seed(a), a greedy slot what is
+ *  left of S at its seeds) and the take (the utility terminal test -- c == a in a keep slot --, the keep test against ufield,
+ *  path_cost and target_gain).  The mode, the robots' set-up, the rounds, the settle kernel, the pick and the last kernel are
+ *  that call's, launched as they are.
+ *  THE COST, whatever the fleet needs: max_claims * (max_rounds + 5) + 3 launches; max_claims * max_rounds <= 2^20.
+ *  - claims_settled[0] == 1: every output equals lipmpc_grid_frontier_assign_keep_utility_batch's, bit for bit.
+ *  - settled[0] == 0 or usettled[0] == 0: n_claims = n_kept = 0 and claims_settled[0] = 0.
+ *  - a slot whose field does not settle within max_rounds stops the call with claims_settled[0] = 0: the keeps and claims made
+ *    so far are exactly the rule's first n_claims winners, and everyone else keeps the utility plan.  A repeat of the whole call
+ *    with a larger budget reproduces them and goes on (what lipmpc_grid_frontier_assign_tiled_batch says about rows applies).
+ *  LIPMPC_E_ARG: what lipmpc_grid_frontier_assign_keep_tiled_batch refuses as such, the three gain parameters out of range, a
+ *   null gain, ufield, usettled or target_gain.  Then LIPMPC_E_UNSUPPORTED (W * H > 2^24, W > 4096 or H > 4096), then
+ *   LIPMPC_E_ARG for a work_bytes below the size call's, then B = 0 returns 0, as there.
+ * lipmpc_grid_frontier_assign_keep_utility_tiled_workspace_bytes: as lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes. */
+int64_t lipmpc_grid_frontier_assign_keep_utility_tiled_workspace_bytes(int32_t W, int32_t H);
+int lipmpc_grid_frontier_assign_keep_utility_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin,
+                                                         const double* cell, const uint8_t* frontier, const uint32_t* field,
+                                                         const int32_t* settled, const double* start, const int8_t* may_claim,
+                                                         const int32_t* prev_target, int32_t r_inflate, int32_t r_claim,
+                                                         int32_t r_keep, int32_t keep_ratio16, int32_t keep_slack, int32_t max_claims,
+                                                         int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes,
+                                                         int32_t max_rounds, double* sub_goals, int32_t* n_sub, int32_t* status,
+                                                         double* path_cost, int32_t* target_cell, int32_t* claim_round,
+                                                         int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled,
+                                                         const int32_t* gain, const uint32_t* ufield, const int32_t* usettled,
+                                                         int32_t w_gain, int32_t g_cap, int32_t min_gain, int32_t* target_gain,
+                                                         void* hip_stream);
 
 /* WAVE-PER-ROBOT PATH CALLS (backward-compatible addition): the path calls above with one wavefront (64 lanes) walking each
  * robot's path where those walk it in one lane -- the sight tests 64 cells at a time, a descent step in one round of loads.  Every
