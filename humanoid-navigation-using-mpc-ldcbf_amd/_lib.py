@@ -164,6 +164,10 @@ SIGNATURES = {
     "lipmpc_grid_frontier_assign_keep_utility_tiled_workspace_bytes": _sig(C.c_int64, "W:i32 H:i32"),
     "lipmpc_grid_frontier_assign_keep_utility_tiled_batch": _sig(C.c_int, f"{_ASSIGN_KEEP_TILED} gain ufield usettled w_gain:i32 g_cap:i32 "
                                                                           "min_gain:i32 target_gain hip_stream"),
+    # claims from per-robot fields: the keep call's argument list with `resume` after max_rounds; prev_target, kept, n_kept nullable
+    "lipmpc_grid_frontier_assign_robot_fields_workspace_bytes": _sig(C.c_int64, "B:i64 W:i32 H:i32"),
+    "lipmpc_grid_frontier_assign_robot_fields_batch": _sig(C.c_int, _ASSIGN_KEEP_TILED.replace("max_rounds:i32", "max_rounds:i32 resume:i32")
+                                                           + " hip_stream"),
     # the wave-per-robot path calls: the weighted / tiled-utility calls' argument lists, cost and settled nullable
     "lipmpc_grid_path_wave_batch": _sig(C.c_int, "device:int B:i64 F:i64 W:i32 H:i32 origin cell occ grid_shared:i32 cost field "
                                                  "field_status settled goal start r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub "

@@ -3912,3 +3912,4 @@ extern "C" int lipmpc_grid_frontier_path_weighted_batch(int device, int64_t B, i
 // lipmpc_grid_frontier_utility_path_wave_batch): the path kernels above with a wavefront walking each robot's path; a section of its
 // own that shares this file's helpers and constants
 #include "lipmpc_field_wave.inc"
+#include "lipmpc_field_robots.inc"

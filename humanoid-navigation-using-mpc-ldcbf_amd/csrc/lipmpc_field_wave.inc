@@ -105,10 +105,12 @@ __device__ __forceinline__ bool wave_sight(const uint32_t* __restrict__ fld, con
 }
 
 // walk() (terminal: the word is 0), soft_walk() (the same, with a cost layer) and walk_to() (terminal: a source that holds its
-// own seed), rule for rule.  terminal(cell, its word) and emit(cell, row) are called with uniform arguments.
+// own seed), rule for rule.  terminal(cell, its word) and emit(cell, row) are called with uniform arguments.  `sight`: another
+// field whose INF words judge the line of sight (the claims from per-robot fields: passability); null: fld itself.
 template <typename Terminal, typename Emit>
 __device__ __forceinline__ int wave_walk(const uint32_t* __restrict__ fld, const uint8_t* __restrict__ kc, int W, int H, int s, int max_seg,
-                                         int lane, int& last_cell, Terminal terminal, Emit emit) {
+                                         int lane, int& last_cell, Terminal terminal, Emit emit, const uint32_t* sight = nullptr) {
+  const uint32_t* seen = sight ? sight : fld;
   int count = 0;
   last_cell = s;
   const uint32_t fs = uni(fld[s]);
@@ -120,8 +122,8 @@ __device__ __forceinline__ int wave_walk(const uint32_t* __restrict__ fld, const
       const bool last = terminal(cur, fcur);
       const uint32_t kcur = wave_k(kc, cur);
       uint32_t seg = 0;
-      const bool sight = wave_sight(fld, kc, H, a, cur, lane, seg);
-      if (!sight || seg - kcur > pen || (fa - fcur) - pen >= (uint32_t)max_seg) {
+      const bool clear = wave_sight(seen, kc, H, a, cur, lane, seg);
+      if (!clear || seg - kcur > pen || (fa - fcur) - pen >= (uint32_t)max_seg) {
         if (prev != a) { emit(prev, count); ++count; a = prev; fa = fprev; pen = kprev; continue; }   // cur is looked at again from the new anchor
         if (last) break;
         emit(cur, count); ++count; a = cur; fa = fcur; pen = 0;

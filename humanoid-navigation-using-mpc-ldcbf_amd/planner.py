@@ -1051,9 +1051,10 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
     _gain_table = staticmethod(tiled_assign_utility_outputs)
     _gain_keep_table = staticmethod(tiled_assign_keep_utility_outputs)
     _GAIN_KEEP_CLASS = "TiledGainKeepFrontierPlanner"
+    _LAUNCH_CAP = True              # False: a subclass whose claim call's launches do not grow with max_claims
 
     def __init__(self, r_claim: int, max_claims: int = 64, **frontier_planner_kwargs):
-        if self.rounds is not None and int(max_claims) * self.rounds > CLAIM_MAX_LAUNCHES:
+        if self._LAUNCH_CAP and self.rounds is not None and int(max_claims) * self.rounds > CLAIM_MAX_LAUNCHES:
             raise ValueError(f"max_claims {max_claims} * rounds {self.rounds}: at most 2^20, the launches of one claim call")
         super().__init__(r_claim, max_claims, **frontier_planner_kwargs)
         self._claim_works = []      # the claim call's own workspace: grown only, every buffer kept alive
@@ -1142,6 +1143,95 @@ class TiledGainKeepFrontierPlanner(TiledCoordinatedFrontierPlanner):
                  keep_ratio16: int, keep_slack: int, **frontier_planner_kwargs):
         _gain_keep_init(super(), r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack,
                         frontier_planner_kwargs)
+
+
+ROBOT_FIELDS_MAX_THREADS = 1 << 31    # B * (W * H + 64): the threads of one round launch of the per-robot fields
+
+
+class _RobotFieldsKeywords(_TiledKeywords):
+    """``_TiledKeywords`` for the class that has no untiled form: an explicit ``tiled=False`` is refused, not overruled."""
+
+    def __call__(cls, *args, **kwargs):
+        if "tiled" in kwargs and not kwargs["tiled"]:
+            raise ValueError(f"{cls.__name__}: tiled=False is not supported (the per-robot fields are relaxed by the tiled rounds only; "
+                             f"the one-workgroup class is CoordinatedFrontierPlanner)")
+        return super().__call__(*args, **kwargs)
+
+
+class RobotFieldsFrontierPlanner(TiledCoordinatedFrontierPlanner, metaclass=_RobotFieldsKeywords):
+    """``TiledCoordinatedFrontierPlanner`` whose claims come from ONE single-source field per robot, all B of them relaxed in the same
+    rounds (include/lipmpc.h, CLAIMS FROM PER-ROBOT FIELDS, ``lipmpc_grid_frontier_assign_robot_fields_batch``): the tiled
+    nearest-frontier plan, then a claim call of ``budget`` + 8 launches whatever ``max_claims`` is -- every claim round and the whole
+    keep phase are reductions over the fields in memory, and the winners' paths are walked a wavefront each, all at once.  Claiming
+    for every robot (``max_claims`` = B) is no longer something to ration.
+    The rule is the parent's greedy over (robot, frontier cell) pairs with these differences: a robot enters the map ONCE, at its
+    start cell or the snap in the nearest-frontier field (the parent snaps again in every round's field: the two differ only for a
+    robot that stands on an impassable cell); ``max_claims`` caps the winners, and a failed keep attempt costs nothing.
+    ``plan`` / ``replan`` return the parent's dict (``tiled_assign_outputs``; with the keep keywords ``tiled_assign_keep_outputs``);
+    ``claims_settled`` [1] = 1: the nearest-frontier field and every robot's field settled and the claims are the rule's; 0: nobody
+    claimed, every row is the nearest-frontier plan's.
+    Keyword-only ``r_keep`` / ``keep_ratio16`` / ``keep_slack``: all three or none, no defaults (nobody has measured one), the
+    parent's ranges.  Keyword-only ``rounds``: an int = the budget of the frontier field and of the per-robot fields, one call each,
+    no synchronisation, capturable; None = a cold call with the parent's starting budget, then resumed calls with a doubled budget
+    until ``claims_settled`` -- one word read on the host per call, so this raises under stream capture.  ``paths`` governs the
+    nearest-frontier plan.  The workspace is the planner's own: grown only, every buffer kept alive, never grown under capture.
+    The limits: the workspace holds the B fields, 4 B W H bytes (33.5 MB for 64 robots on 362 x 362), and a fleet with
+    B * (W * H + 64) > 2^31 is refused; there are no gain seeds (``r_view`` / ``w_gain`` / ``g_cap`` / ``min_gain``) and no clearance
+    (``r_clear`` / ``w_clear`` / ``cost=``): ValueError, as is ``tiled=False``; the device still cannot end the rounds early."""
+
+    _LAUNCH_CAP = False             # (max_claims * rounds <= 2^20 is the parent's claim call's: this one's launches are rounds + 8)
+
+    def __init__(self, r_claim: int, max_claims: int = 64, *, r_keep: int | None = None, keep_ratio16: int | None = None,
+                 keep_slack: int | None = None, **frontier_planner_kwargs):
+        gain = sorted(k for k in ("r_view", "w_gain", "g_cap", "min_gain") if k in frontier_planner_kwargs)
+        if gain:
+            raise ValueError(f"{type(self).__name__}: {gain} not supported (the per-robot fields have no gain seeds; the gain-seeded "
+                             f"claims are TiledCoordinatedFrontierPlanner's)")
+        keep = dict(r_keep=r_keep, keep_ratio16=keep_ratio16, keep_slack=keep_slack)
+        if any(v is not None for v in keep.values()) and any(v is None for v in keep.values()):
+            raise ValueError("r_keep, keep_ratio16 and keep_slack go together: they have no defaults, nobody has measured one")
+        super().__init__(r_claim, max_claims, **{k: v for k, v in keep.items() if v is not None}, **frontier_planner_kwargs)
+
+    def _plan(self, mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target):
+        ev = self._map(mapper_or_evidence, origin, cell)[0]
+        B, (_, W, H) = len(start), ev.shape
+        if B * (W * H + 64) > ROBOT_FIELDS_MAX_THREADS:
+            raise ValueError(f"{B} robots on {W} x {H} cells: the per-robot fields need B * (W * H + 64) <= 2^31 (the threads of one "
+                             f"round launch, and {4 * B * W * H / 2 ** 30:.1f} GiB of fields); claim with fewer robots per call or use "
+                             f"TiledCoordinatedFrontierPlanner")
+        return super()._plan(mapper_or_evidence, start, origin, cell, S_max, out, may_claim, prev_target)
+
+    def _claim_call(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out, budget, resume):
+        """ONE lipmpc_grid_frontier_assign_robot_fields_batch on the current stream: ``budget`` rounds, cold (``resume`` 0) or on the
+        fields the call before left in the workspace (1)."""
+        size = "lipmpc_grid_frontier_assign_robot_fields_workspace_bytes"
+        work = self._workspace(self._claim_works, int(getattr(self.lib, size)(B, W, H)), size)
+        keep = self.r_keep is not None
+        _lib.call("lipmpc_grid_frontier_assign_robot_fields_batch", device=self.device_index, B=B, W=W, H=H,
+                  origin=C.addressof(org_c), cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"],
+                  settled=out["settled"], start=start, may_claim=may_claim, prev_target=prev_target, r_inflate=self.r_inflate,
+                  r_claim=self.r_claim, r_keep=self.r_keep if keep else 0, keep_ratio16=self.keep_ratio16 if keep else 16,
+                  keep_slack=self.keep_slack if keep else 0, max_claims=self.max_claims, max_seg=self.max_seg, S_max=S_max,
+                  work=work, work_bytes=work.numel(), max_rounds=int(budget), resume=int(resume),
+                  **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
+                  kept=out["kept"] if keep else None, n_kept=out["n_kept"] if keep else None,
+                  claims_settled=self._settled(out, 1, "claims_settled"), hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out, prev_target=None, gain=False):
+        if self.rounds is None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("rounds=None reads `claims_settled` on the host: give the planner a fixed `rounds` to capture its calls")
+        call = functools.partial(self._claim_call, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out)
+        if self.rounds is not None:
+            return call(self.rounds, 0)
+        tw, th, _ = tiled_info()
+        budget = max(8, -(-W // tw) - (-H // th) + 1)
+        call(budget, 0)
+        done = out["claims_settled"]
+        # (ends: every round but the last lowers a word, and words are bounded below; an unsettled nearest-frontier field cannot
+        # happen here -- with rounds=None the field call before this one ran until it settled)
+        while not bool(done[0]):
+            budget = min(2 * budget, 65536)
+            call(budget, 1)
 
 
 class InformedFrontierPlanner(FrontierPlanner):

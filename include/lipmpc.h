@@ -1439,6 +1439,87 @@ int lipmpc_grid_frontier_utility_path_wave_batch(int device, int64_t B, int64_t 
                                                  double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                                  int32_t* target_cell, int32_t* target_gain, void* hip_stream);
 
+/* CLAIMS FROM PER-ROBOT FIELDS (backward-compatible addition): lipmpc_grid_frontier_assign_robot_fields_batch.  The claim calls
+ * above relax the whole map once per claim.  The claims are a greedy over (robot, frontier cell) pairs whose costs come from ONE
+ * single-source field per robot; those B fields are independent, so this call relaxes them together in max_rounds rounds of THE
+ * TILED FIELD, after which every claim round and the whole keep phase are reductions over words already in memory.
+ *  The arguments of lipmpc_grid_frontier_assign_keep_tiled_batch in their order, with `resume` (0 / 1) after max_rounds:
+ *  frontier, field, settled: the tiled nearest-frontier field call's outputs on ONE shared map; start, may_claim, r_inflate,
+ *  r_claim, max_claims, max_seg, S_max, r_keep, keep_ratio16, keep_slack as there, in the same ranges (the three keep parameters
+ *  are range-checked even where they are not used).  prev_target [B] int32 or NULL: NULL = no keep phase; then kept and n_kept
+ *  may be NULL too (given, they are written: 0).  work: at least lipmpc_grid_frontier_assign_robot_fields_workspace_bytes(B, W, H)
+ *  bytes, 8-byte aligned; it holds the B fields, 4 B W H bytes, and stays below twice that from 16 x 16 cells on.  All pointers
+ *  are DEVICE pointers except origin / cell; asynchronous on hip_stream, no allocation, no host synchronisation, capturable.
+ *  On entry sub_goals, n_sub, status, path_cost and target_cell hold the nearest-frontier path call's outputs for the same starts.
+ * THE RULE.  passable(c) <=> the given field[c] != LIPMPC_FIELD_INF; moves, the costs 5 / 7 and the no-corner-cut rule are
+ *  lipmpc_grid_field_batch's.
+ *  U_0 = the robots with may_claim != 0 (NULL: everybody) whose status is FOUND or PATH_OVERFLOW.
+ *  ENTRY e_b of a robot of U_0: its start cell (the floor rule) if passable, else the SNAP in the GIVEN field: window
+ *   r_inflate + 1, key (d^2, field, index).  It exists: the path call found it.  (lipmpc_grid_frontier_assign_batch snaps again
+ *   in every round's field; this rule enters the map once.  The two differ only for a robot whose start cell is impassable.)
+ *  D_b(c) = the least cost from e_b to c, LIPMPC_FIELD_INF if there is none; the move rules are symmetric, so this is also the
+ *   cost from c to e_b.
+ *  S_0 = the passable cells with frontier != 0.  k counts the WINNERS, kept ones included, and max_claims caps them: there are
+ *   no relaxation slots to spend here, so -- unlike lipmpc_grid_frontier_assign_keep_batch -- a failed keep attempt costs nothing.
+ *  KEEP PHASE (prev_target not NULL): the robots of U_0 whose prev_target is a cell of the grid, in ascending index while
+ *   k < max_claims.  The ANCHOR a_b = the cell of the current S within r_keep of the previous target with the least (d^2, cell);
+ *   none: the robot is passed over.  The robot is KEPT iff D_b(a_b) is finite and, in 64 bits,
+ *       16 * D_b(a_b) <= keep_ratio16 * field[e_b] + 80 * keep_slack.
+ *   A keeper gets the target a_b, claim_round = k, kept = 1; S loses the r_claim disc round a_b, U loses b, k grows by one.
+ *  GREEDY ROUNDS, while k < max_claims and U and S are not empty: cost_b = min over c in S of D_b(c); a robot without a finite
+ *   cost is no candidate; no candidate: the rounds end.  The winner is the candidate with the least (cost_b, b); its TARGET t is
+ *   the cell of S with the least (D_b(c), c).  S loses the disc round t, U loses the winner, claim_round = k, k grows by one.
+ *  ROWS of a winner or keeper b with target t.  The chain: c_0 = t; from c the next cell is the first neighbour n in the
+ *   descent's order with D_b(n) + step == D_b(c), a diagonal only past two passable side cells; the chain ends at c_L = e_b.  The
+ *   MARKED cells are the string pulling of lipmpc_grid_path_batch along that chain, word for word: the line of sight is judged
+ *   on passability, the cost since the anchor a is D_b(a) - D_b(c_k), and the last chain cell -- the robot's own -- is never
+ *   marked.  The sub-goals are the centres of the marked cells IN REVERSE ORDER (nearest the robot first), then the centre of t;
+ *   a centre is ox + (i + 0.5) * dx as written, no contraction.  n_sub = marks + 1; more than S_max: status PATH_OVERFLOW,
+ *   n_sub = 0 and nothing written to sub_goals -- the robot still claims.  Else status FOUND.  path_cost = D_b(t) / 5.0,
+ *   target_cell = t; rows from n_sub on are untouched.  (The chain exists whenever claims_settled is 1: D_b(t) is finite.  Were a
+ *   descent ever to break off, the robot would still claim and be reported as PATH_OVERFLOW with nothing written.)
+ *  Everybody else keeps every output of the path call and gets claim_round = -1 and kept = 0 (a FOLLOWER).  n_claims[0] = k,
+ *   n_kept[0] = the keepers among them.
+ *  claims_settled[0] == 1 <=> settled[0] == 1 and every robot's field is settled after this call's rounds.  Otherwise NO row
+ *   of any robot is rewritten: claim_round = -1 and kept = 0 for everybody, n_claims = n_kept = 0.  resume = 1 (same arguments,
+ *   same buffers, stream-ordered after the call before) enqueues max_rounds more rounds on the fields in `work` and runs the
+ *   claims again; a cold call (resume = 0) initialises everything it reads in `work`.
+ *  HENCE: two winners' targets are more than r_claim apart; the greedy winners' costs do not decrease; a winner's target is a
+ *   nearest live source of that winner; the round-0 greedy winner and its cost are lipmpc_grid_frontier_assign_batch's when every
+ *   start cell of U_0 is passable (min over b of min over c of D_b(c) = min over b of field_0 at b's cell); the winners are
+ *   those of the plain greedy over all (robot, cell) pairs by (cost, robot, cell) in which a pair leaves with its robot or with
+ *   a cell in a winner's disc; with prev_target NULL or all "none" the outputs other than kept / n_kept are equal; every
+ *   comparison is on integers with a total order, so two calls give identical bits.  Reproduced in numpy by
+ *   tests/robot_fields_oracle.py.
+ * THE COST.  The host enqueues a fixed sequence of max_rounds + 8 launches, whatever max_claims is: the set-up over cells, the
+ *  robots' entries, the fill of the B fields, max_rounds rounds with F = B and one blocked bitmap, their settle kernel, the
+ *  all-settled word, the claim kernel (ONE workgroup: the keep phase and every greedy round in a loop), the walks (a wavefront
+ *  per winner, all winners at once) and the finish.  A resumed call leaves out the first three: max_rounds + 5.  A robot outside
+ *  U_0 seeds nothing: its tiles stay idle at one word read per workgroup and round.
+ * THE LIMITS.  Memory and the threads of a round launch grow with B: B * (W * H + 64) <= 2^31.  There are no gain seeds and no
+ *  clearance layer.  The device still cannot end the rounds early: max_rounds launches are enqueued whatever the map needs.  The
+ *  claim kernel is ONE workgroup that takes the robots of U one after another (a barrier pair and a scan of the source bitmap per
+ *  robot at the start, and again per round for every robot whose best source was just claimed): its time grows with the robots
+ *  that claim times the map's bitmap, and with thousands of claiming robots it is the sequential part that remains -- the caps
+ *  (B up to 2^31 / (W H + 64), max_claims up to 4096) bound memory and threads, not that time.
+ * LIPMPC_E_ARG: B outside 0..2^31-1, W or H < 2, a bad placement, r_inflate, r_claim, max_claims, max_seg, S_max, r_keep,
+ *  keep_ratio16 or keep_slack out of their ranges, max_rounds outside 1..65536, resume not 0 / 1, a null pointer other than
+ *  may_claim, prev_target and -- with prev_target NULL -- kept and n_kept, a `work` that is not 8-byte aligned.  Then
+ *  LIPMPC_E_UNSUPPORTED: W or H > 4096, W * H > 2^24, B * (W * H + 64) > 2^31.  Then LIPMPC_E_ARG: work_bytes too small.  Then
+ *  B = 0: nothing is enqueued.  Every refusal is decided on the host before anything is enqueued.
+ * lipmpc_grid_frontier_assign_robot_fields_workspace_bytes: the bytes of `work`, monotone in B, W and H; LIPMPC_E_ARG or
+ *  LIPMPC_E_UNSUPPORTED (negative) as above. */
+int64_t lipmpc_grid_frontier_assign_robot_fields_workspace_bytes(int64_t B, int32_t W, int32_t H);
+int lipmpc_grid_frontier_assign_robot_fields_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
+                                                   const uint8_t* frontier, const uint32_t* field, const int32_t* settled,
+                                                   const double* start, const int8_t* may_claim, const int32_t* prev_target,
+                                                   int32_t r_inflate, int32_t r_claim, int32_t r_keep, int32_t keep_ratio16,
+                                                   int32_t keep_slack, int32_t max_claims, int32_t max_seg, int32_t S_max, void* work,
+                                                   int64_t work_bytes, int32_t max_rounds, int32_t resume, double* sub_goals,
+                                                   int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell,
+                                                   int32_t* claim_round, int32_t* n_claims, int8_t* kept, int32_t* n_kept,
+                                                   int32_t* claims_settled, void* hip_stream);
+
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
  * c_eta, in the form lipmpc_plan_step_batch_c_eta solves against -- after the rows of a scan (first_slot = the scan's
