@@ -8,4 +8,4 @@ from .lidar import GridMap, LidarSensor, HumanoidMPCUnknownEnvironment, UnknownE
 from .neighbours import NeighbourRows  # noqa: F401
 from .mapping import OccupancyMapper  # noqa: F401
 from .planner import (RrtStarPlanner, GridFieldPlanner, FrontierPlanner, CoordinatedFrontierPlanner, InformedFrontierPlanner, TiledCoordinatedFrontierPlanner, TiledInformedFrontierPlanner, GainKeepFrontierPlanner, TiledGainKeepFrontierPlanner, RobotFieldsFrontierPlanner, FIELD_INF, RRT_FOUND, RRT_NO_PATH, RRT_START_OCCUPIED, RRT_GOAL_OCCUPIED,  # noqa: F401
-                      RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID, RRT_FIELD_UNSETTLED, RRT_STATUS_NAMES, tiled_info)
+                      RRT_GRID_TOO_LARGE, RRT_NO_OBSTACLE_GRID, RRT_PATH_OVERFLOW, RRT_OUTSIDE_GRID, RRT_FIELD_UNSETTLED, RRT_STATUS_NAMES, tiled_info, frontier_regions, regions_outputs)

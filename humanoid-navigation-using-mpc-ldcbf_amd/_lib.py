@@ -179,6 +179,10 @@ SIGNATURES = {
                                                                   "gain ufield n_sources settled w_gain:i32 g_cap:i32 min_gain:i32 start "
                                                                   "r_inflate:i32 max_seg:i32 S_max:i32 sub_goals n_sub status path_cost "
                                                                   "target_cell target_gain hip_stream"),
+    # frontier regions: connected frontier cells, their sizes and a table of the kept ones (rep and, with R_max == 0, table nullable)
+    "lipmpc_grid_frontier_regions_workspace_bytes": _sig(C.c_int64, "F:i64 W:i32 H:i32 R_max:i32"),
+    "lipmpc_grid_frontier_regions_batch": _sig(C.c_int, "device:int F:i64 W:i32 H:i32 frontier min_size:i32 R_max:i32 work work_bytes:i64 "
+                                                        "label size rep table n_regions hip_stream"),
     "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
                                              "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),

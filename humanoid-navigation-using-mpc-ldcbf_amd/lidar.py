@@ -607,6 +607,8 @@ class UnknownEnvFleet:
         -1, and -1 for everybody at the first replan; they are kept in a buffer of the fleet's own, on the device.  The result
         then gains n_kept [n_replans] (the keepers of every replan) and n_jumps [n_replans]: the robots whose target is FOUND at
         this replan and was at the previous one, and lies more than ``r_keep`` cells (Euclidean) from it.
+        With an explorer whose plan dict carries ``n_regions`` (``gain_from="region"``) the result gains n_regions [n_replans,F,3]:
+        per replan all regions, the kept ones and the kept ones beyond the table, of every map.  With any other explorer nothing new.
         The model's limits: with a plain ``FrontierPlanner`` every robot goes to ITS nearest frontier (no task assignment:
         ``CoordinatedFrontierPlanner`` adds it), and the walker cannot turn on the spot while walking -- a working goal that
         jumps behind a robot can make its solve INFEASIBLE.  That ends the robot's run only in a fleet without ``recover``: with
@@ -642,6 +644,7 @@ class UnknownEnvFleet:
             prev = torch.full((B,), -1, dtype=torch.int32, device=dev)
             n_kept, n_jumps = (torch.zeros((rows,), dtype=torch.int32, device=dev) for _ in range(2))
         info = dict(n_replans=0)
+        counts = {}                                          # n_regions [n_replans,F,3], with an explorer whose dict carries it
 
         def replan(k, pl, closing=False):
             if not closing and k % replan_every:
@@ -669,6 +672,10 @@ class UnknownEnvFleet:
                 known_free[info["n_replans"]].copy_((ev <= -t_free).sum((1, 2)))
                 if coordinated:
                     n_claims[info["n_replans"]].copy_(plan["n_claims"][0])
+                if "n_regions" in plan:
+                    if "n_regions" not in counts:
+                        counts["n_regions"] = torch.zeros((rows, F, 3), dtype=torch.int32, device=dev)
+                    counts["n_regions"][info["n_replans"]].copy_(plan["n_regions"])
                 if keeping:
                     tc, H = plan["target_cell"], ev.shape[2]
                     di = torch.div(tc, H, rounding_mode="floor") - torch.div(prev, H, rounding_mode="floor")
@@ -687,6 +694,7 @@ class UnknownEnvFleet:
         solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
         res.update(info, working_goal=self._plan["goal"], walking=fl["walking"], n_frontier=n_frontier, known_free=known_free,
                    done=(fl["walking"] == 0) & solved & (info["explore_status"] == RRT_NO_PATH))
+        res.update(counts)
         if coordinated:
             res["n_claims"] = n_claims
         if keeping:

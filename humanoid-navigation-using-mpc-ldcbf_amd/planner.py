@@ -57,16 +57,17 @@ COST_MAX, R_CLEAR_MAX = 248, 31     # LIPMPC_COST_MAX; the largest r_clear (a di
 
 
 class _TiledKeywords(type):
-    """The keyword-only ``tiled`` / ``rounds`` / ``r_clear`` / ``w_clear`` / ``paths`` of the two field planners, taken off before
+    """The keyword-only ``tiled`` / ``rounds`` / ``r_clear`` / ``w_clear`` / ``paths`` / ``gain_from`` / ``target`` of the two field planners, taken off before
     ``__init__`` runs: the classes' ``__init__`` signatures -- which callers hand on positionally and through ``**kwargs`` -- stay what
     they were."""
 
     def __call__(cls, *args, tiled: bool = False, rounds: int | None = None, r_clear: int | None = None, w_clear: int | None = None,
-                 paths: str = "lane", **kwargs):
+                 paths: str = "lane", gain_from: str | None = None, target: str | None = None, **kwargs):
         self = cls.__new__(cls)
         self._init_paths(paths)
         self._init_tiled(tiled, rounds)
         self._init_clearance(r_clear, w_clear)
+        self._init_regions(gain_from, target, kwargs)
         self.__init__(*args, **kwargs)
         return self
 
@@ -137,6 +138,61 @@ class _TiledRounds(metaclass=_TiledKeywords):
         if not 1 <= self.r_clear <= R_CLEAR_MAX or not 0 <= self.w_clear <= COST_MAX:
             raise ValueError(f"invalid clearance parameters (r_clear {r_clear}: 1..{R_CLEAR_MAX}, w_clear {w_clear}: 0..{COST_MAX})")
 
+    region_rows = 1024          # R_max of the regions call a planner with gain_from="region" makes inside its plans
+
+    _REGIONS = True             # False: a subclass that refuses gain_from / target whatever its keywords
+    _GAIN_CALL = False          # True: a subclass that issues the gain call whatever its keywords
+
+    def _init_regions(self, gain_from, target, keywords=()):
+        """FRONTIER REGIONS (include/lipmpc.h): ``gain_from`` = "view" (the ray-marched visibility gain) / "region" (the size of the
+        frontier cell's region, by ``lipmpc_grid_frontier_regions_batch`` with min_size = max(min_gain, 1): ``r_view`` must be None)
+        and ``target`` = "cell" / "representative" (with "region" only: ``rep`` -- one cell per tabled region, the one nearest its
+        centroid -- stands where the utility field, the utility path and the claim call take ``frontier``; the nearest-frontier field
+        still comes from the real frontier).  Not given: "view" and "cell", no call and no bit changes.  The planners that issue
+        the gain call take them; every other planner, and one with ``r_clear`` / ``w_clear``, refuses them."""
+        if gain_from not in (None, "view", "region"):
+            raise ValueError(f"gain_from {gain_from!r}: 'view' (the visibility gain, the default) or 'region' (the region's size)")
+        if target not in (None, "cell", "representative"):
+            raise ValueError(f"target {target!r}: 'cell' (the default) or 'representative' (one cell per region)")
+        if target == "representative" and gain_from != "region":
+            raise ValueError("target='representative' needs gain_from='region': the representatives are the regions call's")
+        self.gain_from, self.target = gain_from or "view", target or "cell"
+        self._region_works = []     # the regions call's workspace: grown only, every buffer kept alive
+        if gain_from is None and target is None:
+            return
+        if self.r_clear is not None:
+            raise ValueError(f"{type(self).__name__}: gain_from / target with r_clear / w_clear are not supported (regions with soft "
+                             f"clearance are out of scope)")
+        gain_call = self._GAIN_CALL or any(dict(keywords).get(k) is not None for k in ("w_gain", "g_cap"))
+        if not gain_call or not self._REGIONS:
+            raise ValueError(f"{type(self).__name__}: gain_from / target are not supported (they replace the gain call, which this "
+                             f"planner does not issue: the informed planners and the coordinated ones with the gain keywords do)")
+
+    def _region_table(self, F, W, H):
+        """What a plan dict gains with gain_from="region": label, rep [F,W,H], table [F,region_rows,5], n_regions [F,3]."""
+        if self.gain_from != "region":
+            return {}
+        table = regions_outputs(F, W, H, self.region_rows)
+        return {k: table[k] for k in ("label", "rep", "table", "n_regions")}
+
+    def _regions_call(self, F, W, H, min_size, R_max, out, size):
+        """ONE lipmpc_grid_frontier_regions_batch on the current stream from out["frontier"] into out's label / rep / table /
+        n_regions and ``size``, in the planner's own workspace."""
+        name = "lipmpc_grid_frontier_regions_workspace_bytes"
+        work = self._workspace(self._region_works, int(getattr(self.lib, name)(F, W, H, R_max)), name)
+        _lib.call("lipmpc_grid_frontier_regions_batch", device=self.device_index, F=F, W=W, H=H, frontier=out["frontier"],
+                  min_size=min_size, R_max=R_max, work=work, work_bytes=work.numel(), label=out["label"], size=size, rep=out["rep"],
+                  table=out["table"], n_regions=out["n_regions"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _region_gain(self, ev, out):
+        """gain := size: the regions call in the gain call's place (min_gain acts as the minimum size)."""
+        F, W, H = ev.shape
+        self._regions_call(F, W, H, max(self.min_gain, 1), self.region_rows, out, out["gain"])
+
+    def _sources(self, out):
+        """What stands where the utility field, the utility path and the claim call take ``frontier``."""
+        return out["rep"] if self.target == "representative" else out["frontier"]
+
     def _clearance(self, M, W, H, occ=None, evidence=None, t_occ=0):
         """The clearance layer [M,W,H] uint8 of M maps given as occ bytes or as evidence, in the planner's own buffer."""
         if self.r_clear is None:
@@ -202,6 +258,55 @@ class _TiledRounds(metaclass=_TiledKeywords):
         while F and not bool(settled.all()):           # (ends: every round but the last lowers a word, and words are bounded below)
             budget = min(2 * budget, 65536)
             call(budget, 1)
+
+
+MIN_SIZE_MAX, R_MAX_MAX = 1 << 24, 1 << 20     # the regions call's ranges
+
+
+def regions_outputs(F, W, H, R_max):
+    """Outputs of lipmpc_grid_frontier_regions_batch (``frontier_regions``, ``FrontierPlanner.regions``)."""
+    i32 = torch.int32
+    return {"label": (i32, (F, W, H), True), "size": (i32, (F, W, H), True), "rep": (torch.uint8, (F, W, H), True),
+            "table": (i32, (F, R_max, 5), True), "n_regions": (i32, (F, 3), True)}
+
+
+def _region_args(min_size, R_max):
+    min_size, R_max = int(min_size), int(R_max)
+    if not 1 <= min_size <= MIN_SIZE_MAX or not 0 <= R_max <= R_MAX_MAX:
+        raise ValueError(f"invalid region parameters (min_size {min_size}: 1..2^24, R_max {R_max}: 0..2^20)")
+    return min_size, R_max
+
+
+def frontier_regions(frontier, min_size: int = 1, R_max: int = 1024, out=None):
+    """The frontier REGIONS of a given mask (include/lipmpc.h, lipmpc_grid_frontier_regions_batch): ``frontier`` a contiguous uint8
+    tensor [W,H] or [F,W,H] on a HIP device, any non-zero byte a frontier cell.  A region is a maximal 8-connected set of frontier
+    cells.  Returns dict(label [F,W,H] int32: -1 off the frontier, else the region's least flat index; size [F,W,H] int32: the
+    region's cell count, 0 off the frontier -- the layout and dtype of the gain call's ``gain``; rep [F,W,H] uint8: 1 on the
+    representative of every tabled region; table [F,R_max,5] int32: per kept region (size >= ``min_size``) in ascending root order
+    (root, size, centroid_cell, rep_cell, 0), rows past min(kept, R_max) untouched (0 in a fresh dict); n_regions [F,3]: all, kept,
+    kept beyond R_max; work: the call's workspace, which lives with the outputs so that calls on two streams use two of them).
+    ``out``: that dict, to write into (a captured graph replays into the same buffers; nothing is allocated then).  Asynchronous on
+    the current stream; nine launches whatever the mask holds."""
+    if not isinstance(frontier, torch.Tensor) or frontier.dtype != torch.uint8 or not frontier.is_cuda or not frontier.is_contiguous() or \
+            frontier.dim() not in (2, 3):
+        raise ValueError("frontier: a contiguous uint8 tensor [W,H] or [F,W,H] on a HIP device")
+    min_size, R_max = _region_args(min_size, R_max)
+    fr = frontier if frontier.dim() == 3 else frontier[None]
+    F, W, H = fr.shape
+    lib = _lib.load()
+    need = int(lib.lipmpc_grid_frontier_regions_workspace_bytes(F, W, H, R_max))
+    if need < 0:
+        _lib.check(need, "lipmpc_grid_frontier_regions_workspace_bytes")
+    table = dict(regions_outputs(F, W, H, R_max), work=(torch.uint8, (need,), True))
+    if out is None:
+        out = _alloc(table, ("label", "size", "rep", "n_regions", "work"), fr.device)
+        out["table"] = torch.zeros(table["table"][1], dtype=torch.int32, device=fr.device)
+    else:
+        _check_table(table, out, fr.device, "out")
+    _lib.call("lipmpc_grid_frontier_regions_batch", device=fr.device.index, F=F, W=W, H=H, frontier=fr, min_size=min_size, R_max=R_max,
+              work=out["work"], work_bytes=need, **_named(out, ("label", "size", "rep", "table", "n_regions")),
+              hip_stream=torch.cuda.current_stream(fr.device).cuda_stream)
+    return out
 
 
 def field_plan_outputs(B, F, W, H, S_max):
@@ -654,6 +759,27 @@ class FrontierPlanner(_TiledRounds):
         self._field(ev, t_free, t_occ, out)
         return {k: out[k] for k in names + (("settled",) if self.tiled else ()) + (("cost",) if "cost" in out else ())}
 
+    def regions(self, mapper_or_evidence, min_size: int = 1, R_max: int = 1024, out=None):
+        """The frontier REGIONS of a mapper or an evidence tensor (include/lipmpc.h, lipmpc_grid_frontier_regions_batch): the
+        frontier field (tiled when the planner is), then the regions call on its ``frontier``, both on the current stream.  Returns
+        ``frontier_regions``' label, size, rep, table and n_regions plus ``field()``'s dict.  ``out``: that dict, to write into.  The
+        call's workspace is the planner's own: grown only, never under capture -- run the call once before capturing it."""
+        ev, t_free, t_occ, _, _ = self._map(mapper_or_evidence)
+        min_size, R_max = _region_args(min_size, R_max)
+        F, W, H = ev.shape
+        field = frontier_outputs(0, F, W, H, 1)
+        table = dict({k: field[k] for k in ("field", "frontier", "n_frontier")}, **regions_outputs(F, W, H, R_max))
+        if out is None:
+            out = _alloc(table, tuple(k for k in table if k != "table"), self.device)
+            out["table"] = torch.zeros(table["table"][1], dtype=torch.int32, device=self.device)
+        else:
+            _check_table(table, out, self.device, "out")
+        out.pop("cost", None)
+        self._field(ev, t_free, t_occ, out)
+        self._regions_call(F, W, H, min_size, R_max, out, out["size"])
+        names = ("frontier", "label", "size", "rep", "table", "n_regions", "field", "n_frontier")
+        return {k: out[k] for k in names + (("settled",) if self.tiled else ()) + (("cost",) if "cost" in out else ())}
+
     @_cost_keyword
     def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None):
         """Plan B robots from ``start`` [B,2] to their nearest frontier: on a shared map (a mapper without ``per_robot``, an
@@ -776,6 +902,13 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
             raise TypeError(f"unexpected keyword {misspelt}: the keep parameters are r_keep, keep_ratio16 and keep_slack")
         # the gain parameters, likewise
         gain = [frontier_planner_kwargs.pop(k, None) for k in ("r_view", "w_gain", "g_cap", "min_gain")]
+        region = self.gain_from == "region"
+        if region:
+            if gain[0] is not None:
+                raise ValueError(f"gain_from='region' with r_view {gain[0]}: r_view must be None (the gain is the region's size, no ray "
+                                 f"is marched)")
+            if gain[1] is not None or gain[2] is not None:
+                gain[0] = 0                                # (r_view 0 marks a planner whose gain is the region's size)
         misspelt = sorted(k for k in frontier_planner_kwargs if any(w in k for w in ("gain", "view", "cap")) or
                           (gain != [None] * 4 and k not in inspect.signature(FrontierPlanner.__init__).parameters))
         if misspelt:
@@ -791,7 +924,7 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
                 raise ValueError(f"the gain keywords with r_keep / keep_ratio16 / keep_slack: there is no hysteresis for gain-seeded "
                                  f"claims in {type(self).__name__}; the class with both is {self._GAIN_KEEP_CLASS}")
             self.r_view, self.w_gain, self.g_cap, self.min_gain = (int(v) for v in gain[:3] + [gain[3] or 0])
-            if not 1 <= self.r_view <= 64 or not 0 <= self.w_gain <= 65535 or not 1 <= self.g_cap <= 16384 or \
+            if not (region or 1 <= self.r_view <= 64) or not 0 <= self.w_gain <= 65535 or not 1 <= self.g_cap <= 16384 or \
                     not 0 <= self.min_gain <= 16384:
                 raise ValueError(f"invalid gain parameters (r_view {gain[0]}: 1..64, w_gain {gain[1]}: 0..65535, g_cap {gain[2]}: "
                                  f"1..16384, min_gain {gain[3]}: 0..16384)")
@@ -861,10 +994,12 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
                 if prev_target.dtype != torch.int32:                            # whatever is no cell of an int32 grid is "none"
                     prev_target = torch.where((prev_target >= 0) & (prev_target < W * H), prev_target, -1).to(torch.int32)
                 prev_target = prev_target.contiguous()
-        table = self._table(B, W, H, S_max)
+        regions = self._region_table(1, W, H)
+        table = dict(self._table(B, W, H, S_max), **regions)
         if out is None:
             out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost", "target", "target_cell"), self.device, torch.zeros)
             out.update(_alloc(table, self._FRESH, self.device))
+            out.update(_alloc(regions, tuple(regions), self.device, torch.zeros))
             out.update(claim_round=torch.full((B,), -1, dtype=torch.int32, device=self.device),
                        n_claims=torch.zeros((1,), dtype=torch.int32, device=self.device))
             if self.r_keep is not None:
@@ -914,7 +1049,7 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
 
     def _gain_claims(self, B, W, H, start, may_claim, org_c, cell_c, S_max, out):
         _lib.call("lipmpc_grid_frontier_assign_utility_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
-                  cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], start=start, may_claim=may_claim,
+                  cell=C.addressof(cell_c), frontier=self._sources(out), field=out["field"], start=start, may_claim=may_claim,
                   r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims, max_seg=self.max_seg, S_max=S_max,
                   work=out["work"], **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
                   gain=out["gain"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, target_gain=out["target_gain"],
@@ -922,7 +1057,7 @@ class CoordinatedFrontierPlanner(FrontierPlanner):
 
     def _gain_keep_claims(self, B, W, H, start, may_claim, prev_target, org_c, cell_c, S_max, out):
         _lib.call("lipmpc_grid_frontier_assign_keep_utility_batch", device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
-                  cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], start=start, may_claim=may_claim,
+                  cell=C.addressof(cell_c), frontier=self._sources(out), field=out["field"], start=start, may_claim=may_claim,
                   prev_target=prev_target, r_inflate=self.r_inflate, r_claim=self.r_claim, r_keep=self.r_keep,
                   keep_ratio16=self.keep_ratio16, keep_slack=self.keep_slack, max_claims=self.max_claims, max_seg=self.max_seg,
                   S_max=S_max, work=out["work"],
@@ -969,15 +1104,15 @@ class GainKeepFrontierPlanner(CoordinatedFrontierPlanner):
     def __init__(self, r_claim: int, max_claims: int = 64, *, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, r_keep: int,
                  keep_ratio16: int, keep_slack: int, **frontier_planner_kwargs):
         _gain_keep_init(super(), r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack,
-                        frontier_planner_kwargs)
+                        frontier_planner_kwargs, self.gain_from == "region")
 
 
-def _gain_keep_init(parent, r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack, kwargs):
+def _gain_keep_init(parent, r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack, kwargs, region=False):
     """What the two gain-keep classes' ``__init__`` share: every parameter is required (a None is as good as none), then the parent's
     checks and ranges."""
     given = dict(r_view=r_view, w_gain=w_gain, g_cap=g_cap, min_gain=min_gain, r_keep=r_keep, keep_ratio16=keep_ratio16,
                  keep_slack=keep_slack)
-    missing = sorted(k for k, v in given.items() if v is None and k != "min_gain")
+    missing = sorted(k for k, v in given.items() if v is None and k != "min_gain" and not (region and k == "r_view"))
     if missing:
         raise ValueError(f"{missing} None: r_view, w_gain, g_cap, r_keep, keep_ratio16 and keep_slack have no defaults, nobody has "
                          f"measured one")
@@ -1112,7 +1247,8 @@ class TiledCoordinatedFrontierPlanner(_AlwaysTiled, CoordinatedFrontierPlanner):
 
         def call(budget):
             _lib.call(name, device=self.device_index, B=B, W=W, H=H, origin=C.addressof(org_c),
-                      cell=C.addressof(cell_c), frontier=out["frontier"], field=out["field"], settled=out["settled"], start=start,
+                      cell=C.addressof(cell_c), frontier=self._sources(out) if gain else out["frontier"], field=out["field"],
+                      settled=out["settled"], start=start,
                       may_claim=may_claim, r_inflate=self.r_inflate, r_claim=self.r_claim, max_claims=self.max_claims,
                       max_seg=self.max_seg, S_max=S_max, work=work, work_bytes=work.numel(), max_rounds=budget, **keep,
                       **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "claim_round", "n_claims")),
@@ -1142,7 +1278,7 @@ class TiledGainKeepFrontierPlanner(TiledCoordinatedFrontierPlanner):
     def __init__(self, r_claim: int, max_claims: int = 64, *, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, r_keep: int,
                  keep_ratio16: int, keep_slack: int, **frontier_planner_kwargs):
         _gain_keep_init(super(), r_claim, max_claims, r_view, w_gain, g_cap, min_gain, r_keep, keep_ratio16, keep_slack,
-                        frontier_planner_kwargs)
+                        frontier_planner_kwargs, self.gain_from == "region")
 
 
 ROBOT_FIELDS_MAX_THREADS = 1 << 31    # B * (W * H + 64): the threads of one round launch of the per-robot fields
@@ -1180,6 +1316,7 @@ class RobotFieldsFrontierPlanner(TiledCoordinatedFrontierPlanner, metaclass=_Rob
     (``r_clear`` / ``w_clear`` / ``cost=``): ValueError, as is ``tiled=False``; the device still cannot end the rounds early."""
 
     _LAUNCH_CAP = False             # (max_claims * rounds <= 2^20 is the parent's claim call's: this one's launches are rounds + 8)
+    _REGIONS = False                # (no gain seeds here, so nothing for gain_from / target to replace)
 
     def __init__(self, r_claim: int, max_claims: int = 64, *, r_keep: int | None = None, keep_ratio16: int | None = None,
                  keep_slack: int | None = None, **frontier_planner_kwargs):
@@ -1246,36 +1383,54 @@ class InformedFrontierPlanner(FrontierPlanner):
     with ``min_gain`` = 0 is ``FrontierPlanner``, bit for bit.  None of the three gain parameters has a default: nobody has measured
     one.  The other arguments are ``FrontierPlanner``'s.
     The model's limits: unknown cells do not occlude; there is no memory between plans (no hysteresis), so a replan may hand a robot
-    another target; a shared field sends robots that stand together to the same cell, as the parent does."""
+    another target; a shared field sends robots that stand together to the same cell, as the parent does.
+    Keyword-only ``gain_from`` = "view" (default) / "region" and ``target`` = "cell" (default) / "representative" (include/lipmpc.h,
+    FRONTIER REGIONS): with "region" ``r_view`` must be None, the gain call is replaced by ``lipmpc_grid_frontier_regions_batch`` with
+    min_size = max(``min_gain``, 1), the gain of a frontier cell is the SIZE of its region, and the plan dict gains label, rep
+    [F,W,H], table [F,1024,5] and n_regions [F,3]; with "representative" one cell per tabled region -- the region's own cell
+    nearest its centroid -- stands where the utility field and the utility path take ``frontier``.  ``w_gain``, ``g_cap`` and
+    ``min_gain`` keep their meaning and ranges.  The coordinated classes with the gain keywords take both options likewise."""
 
     _TILED, _TILED_WHY, _TILED_CLASS = False, "the gain call and the utility field keep", "TiledInformedFrontierPlanner"
     _CLEARANCE = False
+    _GAIN_CALL = True
     _SETTLED = ()               # what the large-map subclass adds to the dicts of gain() and field()
 
     def __init__(self, r_view: int, w_gain: int, g_cap: int, min_gain: int = 0, **frontier_planner_kwargs):
-        self.r_view, self.w_gain, self.g_cap, self.min_gain = int(r_view), int(w_gain), int(g_cap), int(min_gain)
-        if not 1 <= self.r_view <= 64 or not 0 <= self.w_gain <= 65535 or not 1 <= self.g_cap <= 16384 or not 0 <= self.min_gain <= 16384:
+        region = self.gain_from == "region"
+        if region and r_view is not None:
+            raise ValueError(f"gain_from='region' with r_view {r_view}: r_view must be None (the gain is the region's size, no ray is "
+                             f"marched)")
+        # (r_view 0 marks a planner whose gain is the region's size)
+        self.r_view, self.w_gain, self.g_cap, self.min_gain = 0 if region else int(r_view), int(w_gain), int(g_cap), int(min_gain)
+        if not (region or 1 <= self.r_view <= 64) or not 0 <= self.w_gain <= 65535 or not 1 <= self.g_cap <= 16384 or \
+                not 0 <= self.min_gain <= 16384:
             raise ValueError(f"invalid gain parameters (r_view {r_view}: 1..64, w_gain {w_gain}: 0..65535, g_cap {g_cap}: 1..16384, "
                              f"min_gain {min_gain}: 0..16384)")
         super().__init__(**frontier_planner_kwargs)
 
     def _gain(self, ev, t_free, t_occ, out):
+        if self.gain_from == "region":
+            return self._region_gain(ev, out)
         F, W, H = ev.shape
         _lib.call("lipmpc_grid_frontier_gain_batch", device=self.device_index, F=F, W=W, H=H, evidence=ev, t_free=t_free, t_occ=t_occ,
                   frontier=out["frontier"], r_view=self.r_view, gain=out["gain"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
     def _ufield(self, ev, out):
         F, W, H = ev.shape
-        _lib.call("lipmpc_grid_frontier_utility_field_batch", device=self.device_index, F=F, W=W, H=H, frontier=out["frontier"],
+        _lib.call("lipmpc_grid_frontier_utility_field_batch", device=self.device_index, F=F, W=W, H=H, frontier=self._sources(out),
                   field=out["field"], gain=out["gain"], w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, ufield=out["ufield"],
                   n_sources=out["n_sources"], hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
 
     def _fields(self, mapper_or_evidence, out, names):
         ev, t_free, t_occ, _, _ = self._map(mapper_or_evidence)
-        table = informed_outputs(0, *ev.shape, 1)
+        regions = self._region_table(*ev.shape)
+        table = dict(informed_outputs(0, *ev.shape, 1), **regions)
         if out is None:
             out = _alloc(table, names, self.device)
-        else:
+            out.update(_alloc(regions, tuple(regions), self.device, torch.zeros))      # (table rows past the kept regions stay 0)
+        names = names + tuple(regions)
+        if out is not None:
             _check_table({k: table[k] for k in names}, out, self.device, "out")
         self._field(ev, t_free, t_occ, out)
         self._gain(ev, t_free, t_occ, out)
@@ -1307,10 +1462,12 @@ class InformedFrontierPlanner(FrontierPlanner):
         B, (F, W, H), S_max = start.shape[0], ev.shape, int(S_max)
         if F != B and F != 1:
             raise ValueError(f"{F} maps for {B} robots: one shared map, or one per robot")
-        table = informed_outputs(B, F, W, H, S_max)
+        regions = self._region_table(F, W, H)
+        table = dict(informed_outputs(B, F, W, H, S_max), **regions)
         if out is None:
             out = _alloc(table, ("sub_goals", "n_sub", "status", "path_cost", "target", "target_cell"), self.device, torch.zeros)
             out.update(_alloc(table, ("field", "frontier", "n_frontier", "gain", "ufield", "n_sources"), self.device))     # written whole
+            out.update(_alloc(regions, tuple(regions), self.device, torch.zeros))
             out["target_gain"] = torch.full((B,), -1, dtype=torch.int32, device=self.device)
         else:
             _check_table(table, out, self.device, "out")
@@ -1331,7 +1488,7 @@ class InformedFrontierPlanner(FrontierPlanner):
             name, more = "lipmpc_grid_frontier_utility_path_wave_batch", dict(settled=None)
         _lib.call(name, device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
                   origin=C.addressof(org_c), cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ,
-                  **_named(out, ("frontier", "gain", "ufield", "n_sources")), **more, w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain,
+                  frontier=self._sources(out), **_named(out, ("gain", "ufield", "n_sources")), **more, w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain,
                   start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "target_gain")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)
@@ -1360,6 +1517,8 @@ class TiledInformedFrontierPlanner(_AlwaysTiled, InformedFrontierPlanner):
         return super()._field(ev, t_free, t_occ, out)
 
     def _gain(self, ev, t_free, t_occ, out):
+        if self.gain_from == "region":
+            return self._region_gain(ev, out)
         F, W, H = ev.shape
         _lib.call("lipmpc_grid_frontier_gain_tiled_batch", device=self.device_index, F=F, W=W, H=H, evidence=ev, t_free=t_free,
                   t_occ=t_occ, frontier=out["frontier"], r_view=self.r_view, gain=out["gain"],
@@ -1369,7 +1528,7 @@ class TiledInformedFrontierPlanner(_AlwaysTiled, InformedFrontierPlanner):
         F, W, H = ev.shape
         t_free, t_occ = self._classes
         self._run_tiled("lipmpc_grid_frontier_utility_field_tiled_batch", F, W, H, out, works=self._uworks, key="usettled", evidence=ev,
-                        t_free=t_free, t_occ=t_occ, r_inflate=self.r_inflate, frontier=out["frontier"], gain=out["gain"],
+                        t_free=t_free, t_occ=t_occ, r_inflate=self.r_inflate, frontier=self._sources(out), gain=out["gain"],
                         w_gain=self.w_gain, g_cap=self.g_cap, min_gain=self.min_gain, ufield=out["ufield"], n_sources=out["n_sources"])
 
     def plan(self, mapper_or_evidence, start, origin=None, cell=None, S_max: int = 64, out=None):
@@ -1388,7 +1547,7 @@ class TiledInformedFrontierPlanner(_AlwaysTiled, InformedFrontierPlanner):
         name = "lipmpc_grid_frontier_utility_path_wave_batch" if self.paths == "wave" else "lipmpc_grid_frontier_utility_path_tiled_batch"
         _lib.call(name, device=self.device_index, B=start.shape[0], F=F, W=W, H=H,
                   origin=C.addressof(org_c), cell=C.addressof(cell_c), evidence=ev, t_occ=t_occ,
-                  **_named(out, ("frontier", "gain", "ufield", "n_sources")), settled=out["usettled"], w_gain=self.w_gain, g_cap=self.g_cap,
+                  frontier=self._sources(out), **_named(out, ("gain", "ufield", "n_sources")), settled=out["usettled"], w_gain=self.w_gain, g_cap=self.g_cap,
                   min_gain=self.min_gain, start=start, r_inflate=self.r_inflate, max_seg=self.max_seg, S_max=S_max,
                   **_named(out, ("sub_goals", "n_sub", "status", "path_cost", "target_cell", "target_gain")),
                   hip_stream=torch.cuda.current_stream(self.device).cuda_stream)

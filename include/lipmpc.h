@@ -1520,6 +1520,47 @@ int lipmpc_grid_frontier_assign_robot_fields_batch(int device, int64_t B, int32_
                                                    int32_t* claim_round, int32_t* n_claims, int8_t* kept, int32_t* n_kept,
                                                    int32_t* claims_settled, void* hip_stream);
 
+/* FRONTIER REGIONS (backward-compatible addition): lipmpc_grid_frontier_regions_batch.  The frontier calls above mark frontier
+ * CELLS; Yamauchi's frontiers are REGIONS, connected groups of frontier cells with a size and a centre.  This call labels the
+ * regions of a given mask, sizes them and tables the ones that are large enough.  `size` has the layout and dtype of the gain
+ * call's `gain` on purpose: every call that takes `gain` takes it, with min_gain acting as the minimum size, and `rep` can stand
+ * where those calls take `frontier`.
+ *  frontier [F,W,H] uint8, layout i * H + j: any non-zero byte is a frontier cell.  min_size 1..2^24.  R_max 0..2^20: the rows of
+ *  the table per map.  work: at least lipmpc_grid_frontier_regions_workspace_bytes(F, W, H, R_max) bytes, 8-byte aligned, contents
+ *  arbitrary on entry; calls that share one must be stream-ordered.  All pointers are DEVICE pointers; asynchronous on hip_stream,
+ *  no allocation, no host synchronisation, capturable.
+ * THE RULE, per map f.
+ *  A REGION is a maximal 8-connected set of frontier cells; plain 8-connectivity: a diagonal pair is connected whatever lies
+ *   beside it.
+ *  label [F,W,H] int32: -1 off the frontier, else the least flat index of the cell's region (the region's ROOT).
+ *  size  [F,W,H] int32: 0 off the frontier, else the number of cells of the cell's region.  Neither depends on min_size or R_max.
+ *  A region is KEPT iff its size >= min_size.  The kept regions are RANKED by root, ascending.
+ *  n_regions [F,3] int32: (all regions, kept regions, kept regions beyond R_max = max(kept - R_max, 0)).
+ *  table [F,R_max,5] int32 or NULL if R_max == 0: row r < min(kept, R_max) is (root, size, centroid_cell, rep_cell, 0); the rows
+ *   from there on are untouched.  centroid_cell = ci * H + cj with ci = (2 * sum of i + n) / (2 n), cj likewise with j: integer
+ *   division of non-negative 64-bit values (the sum of i over a region reaches 2^36), n = size.  rep_cell, the REPRESENTATIVE, is
+ *   the region's own cell with the least key ((i - ci)^2 + (j - cj)^2, flat index): a frontier cell even where the centroid is
+ *   none, as for a ring.
+ *  rep [F,W,H] uint8 or NULL: 1 on the rep_cell of every tabled region, 0 elsewhere; written whole.
+ *  Everything is an integer and every reduction is an integer add or a min over totally ordered keys: two calls give identical
+ *  bits.  Reproduced in numpy by tests/regions_oracle.py.
+ * THE COST.  The host enqueues a fixed sequence of 9 launches, whatever the mask holds and whatever its size (R_max == 0, no
+ *  table: the first 6 of them): the tiles' components in LDS (a lock-free union-find on the 32 x 64 tiles of the tiled field, the
+ *  parent words in `label`), the unions across tile borders, the flatten with the roots' cell counts, the kept roots per 2048
+ *  consecutive cells, their scan, the ranks with the first two table columns and every cell's size, the sums, the keys, the table.
+ *  No kernel spins, waits for another thread's store or uses a grid-wide barrier; every loop is bounded by a size.
+ * THE WORKSPACE is 4 bytes per cell (the root's rank), 32 bytes per table row and 8 bytes per 2048 cells, + 64: at most
+ *  8 * F * W * H + 64 * F * R_max + 65536 bytes, monotone in every argument.  Statistics are kept per table row, not per cell.
+ * LIPMPC_E_ARG: F < 0, W or H < 2, min_size outside 1..2^24, R_max outside 0..2^20, a null frontier, work, label, size or
+ *  n_regions, a null table with R_max > 0, a `work` that is not 8-byte aligned or -- for a supported shape: the size of `work` is
+ *  not defined for any other -- is too small.  Then LIPMPC_E_UNSUPPORTED: W or H > 4096, F * W * H > 2^31, whatever work_bytes
+ *  is.  Then F = 0: nothing is enqueued.  Every refusal is decided on the host before anything is enqueued.
+ * lipmpc_grid_frontier_regions_workspace_bytes: the bytes of `work`; LIPMPC_E_ARG or LIPMPC_E_UNSUPPORTED (negative) as above. */
+int64_t lipmpc_grid_frontier_regions_workspace_bytes(int64_t F, int32_t W, int32_t H, int32_t R_max);
+int lipmpc_grid_frontier_regions_batch(int device, int64_t F, int32_t W, int32_t H, const uint8_t* frontier, int32_t min_size,
+                                       int32_t R_max, void* work, int64_t work_bytes, int32_t* label, int32_t* size, uint8_t* rep,
+                                       int32_t* table, int32_t* n_regions, void* hip_stream);
+
 /* NEIGHBOUR LDCBF ROWS (backward-compatible addition): the robots of one launch as each other's obstacles.  For every robot
  * the call finds its nearest neighbours among the B robots and appends one half-space row per neighbour to the robot's
  * c_eta, in the form lipmpc_plan_step_batch_c_eta solves against -- after the rows of a scan (first_slot = the scan's
