@@ -185,6 +185,9 @@ SIGNATURES = {
                                                         "label size rep table n_regions hip_stream"),
     "lipmpc_map_update_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
                                              "w_hit:i32 w_miss:i32 state hits ray_table mask evidence hip_stream"),
+    "lipmpc_scan_match_batch": _sig(C.c_int, "device:int B:i64 resolution:i32 W:i32 H:i32 grid_shared:i32 origin cell lidar_range:f64 depth:f64 "
+                                             "n_x:i32 n_y:i32 n_yaw:i32 rot_table clamp:i32 min_score:i32 min_gain:i32 state hits mask evidence "
+                                             "offset_cells yaw_index offset score n_used matched hip_stream"),
     "lipmpc_neighbour_workspace_bytes": _sig(C.c_int64, "B:i64"),
     "lipmpc_neighbour_c_eta_batch": _sig(C.c_int, "device:int B:i64 n_obs_max:i32 k_rows:i32 sense_range:f64 share:f64 state radius group "
                                                   "first_slot workspace c_eta n_rows n_near neighbours hip_stream"),

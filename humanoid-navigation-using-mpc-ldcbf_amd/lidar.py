@@ -362,11 +362,16 @@ class UnknownEnvFleet:
     samples in a row and only if the capture point respects every half-space the sample's solve was given, neighbour rows
     included (lipmpc_fleet_recover_update_batch; DESIGN.md has the argument).  A recovering robot is walking.  6 is a sensible
     value: on the recorded scenes a robot that recovery keeps needs one in a row (tests/golden/EXPLORATION_RECOVER.md).  0 (the default): every
-    call and every bit as before."""
+    call and every bit as before.
+    ``drift_sigma`` = s: the robots' odometry drifts -- what they believe about their position parts from the truth by a random walk
+    of N(0, s^2) per sample and axis, and it is the believed pose that maps and plans (``run`` has the model).  ``matcher=
+    ScanMatcher(...)`` (needs ``mapper``; shifts only, n_yaw = 0: the sensor is world-aligned): every sample the scan is matched
+    against the map before it is added to it (lipmpc_scan_match_batch) and the pose corrected by the accepted offset.
+    ``drift_sigma`` without a matcher shows the smear.  Both None (the default): every call and every bit as before."""
 
     def __init__(self, env_rings=None, N_horizon=3, lidar_range=3.0, resolution=360, n_obs_max=12, v_max=32,
                  exact=False, interior_tol=1e-6, device=None, warm_start=False, grid=None, avoid=None, mapper=None, split_rays=0,
-                 recover=0):
+                 drift_sigma=None, matcher=None, recover=0):
         from .solver import BatchedLipMpc, LipMpcParams, FLAG_INTERIOR, FLAG_WARM_START
         if (env_rings is None) == (grid is None):
             raise ValueError("the true map: env_rings or grid")
@@ -390,11 +395,22 @@ class UnknownEnvFleet:
                                    or mapper.lidar_range != self.sensor.lidar_range):
             raise ValueError("mapper: an OccupancyMapper on the fleet's device, for the fleet's resolution and lidar_range")
         self.mapper = mapper
+        if matcher is not None and mapper is None:
+            raise ValueError("matcher: a ScanMatcher matches against the fleet's map: UnknownEnvFleet(..., mapper=OccupancyMapper(...))")
+        if matcher is not None and matcher.n_yaw:
+            raise ValueError("matcher: the fleet's sensor is world-aligned, its matcher searches shifts only (n_yaw = 0)")
+        if drift_sigma is not None and not 0.0 <= float(drift_sigma) < math.inf:
+            raise ValueError("drift_sigma: None or a standard deviation >= 0")
+        self.matcher = matcher
+        self.drift_sigma = None if drift_sigma is None else float(drift_sigma)
+        # what ``run_exploring`` hands to its run as ``drift`` / ``drift_seed`` (its own parameter list is as it always was)
+        self.exploring_drift, self.exploring_drift_seed = "seeded", 0
 
-    def _plan_for(self, B, k_max, noise_mode, have_delta, stop_obj, use_graph):
+    def _plan_for(self, B, k_max, noise_mode, have_delta, stop_obj, use_graph, drift_mode=None):
         """Buffers (and, once captured, the HIP graph of one sample) of a run shape; kept across ``run`` calls, so a
-        second run of the same shape replays the graph it already has."""
-        key = (B, k_max, noise_mode, have_delta, float(stop_obj), bool(use_graph))
+        second run of the same shape replays the graph it already has.  ``drift_mode``: None (no drift model: the buffers and the
+        sample of a fleet without one), "none", "seeded" or "given"."""
+        key = (B, k_max, noise_mode, have_delta, float(stop_obj), bool(use_graph)) + (() if drift_mode is None else (drift_mode,))
         pl = getattr(self, "_plan", None)
         if pl is not None and pl["key"] == key:
             return pl
@@ -425,11 +441,41 @@ class UnknownEnvFleet:
             pl["rec"] = _alloc(table, table, dev, torch.zeros)
             pl["last_margin"] = torch.zeros((B,), **f64)
             pl["not_evaluated"] = torch.zeros((B,), dtype=torch.bool, device=dev)
+        if drift_mode is not None:
+            # the odometry model: drift = believed - true position, this sample's draw, what the robots believe (state, goal, and
+            # with a map the readings as placed at the believed pose), and the record of the run
+            pl.update(drift=torch.zeros((B, 2), **f64), dbuf=torch.zeros((B, 2), **f64), dstep=torch.zeros((B, 2), **f64),
+                      walkf=torch.zeros((B,), **f64), bstate=torch.zeros((B, 5), **f64), bgoal=torch.zeros((B, 2), **f64),
+                      perr=torch.zeros((B,), **f64), pose_error=torch.zeros((k_max, B), **f64),
+                      n_matched=torch.zeros((B,), dtype=torch.int32, device=dev),
+                      dgen=torch.Generator(device=dev) if drift_mode == "seeded" else None)
+            if self.mapper is not None:
+                pl["bhits"] = torch.zeros((B, sn.resolution, 2), **f64)
+            if self.matcher is not None:
+                pl["mout"] = self.matcher.alloc_outputs(B, dev)
         self._plan = pl
         return pl
 
+    def _drift_mode(self, drift):
+        """How a run's ``drift`` argument is taken: None = the fleet has no drift model (no ``drift_sigma``, no ``matcher``, no
+        given draws) and its sample is the one it always was; "given" = a tensor of draws; "seeded" = draws of N(0,
+        drift_sigma^2) from the run's generator; "none" = no draws (a matcher alone, or ``drift=None``)."""
+        if isinstance(drift, torch.Tensor):
+            return "given"
+        if drift is not None and drift != "seeded":
+            raise ValueError('drift: "seeded", None or a tensor [k_max,B,2]')
+        if self.drift_sigma is None and self.matcher is None:
+            return None
+        return "none" if drift is None or self.drift_sigma is None else "seeded"
+
+    @staticmethod
+    def _believed_positions(pl):
+        """[B,2]: where the robots believe they are (true + drift); the true positions in a fleet without a drift model."""
+        pos = pl["fl"]["state"][:, (0, 2)].contiguous()
+        return pos if "drift" not in pl else pos + pl["drift"]
+
     def run(self, state0, goal, first_foot, k_max, noise="seeded", noise_seed=0, delta=None, stop_obj=0.05,
-            use_graph=True):
+            use_graph=True, drift="seeded", drift_seed=0):
         """state0 [B,5], goal [B,2], first_foot [B] int8.  noise: "seeded" (N(0, 0.01) per reading from a generator
         seeded with noise_seed), None (noiseless) or a tensor [k_max,B,resolution,2].  Returns dict(X_pred
         [B,k_max+1,5], U_pred [B,k_max,3], n_steps [B] solved samples, last_status [B] (STATUS_SENSOR_OVERFLOW = 5: the
@@ -440,16 +486,32 @@ class UnknownEnvFleet:
         neighbour in range of the robot got no row (n_near > n_rows: more neighbours than k_rows or than free slots).
         One sample = noise draw (seeded mode), scan + constraint assembly, step solve, fleet update; with ``use_graph``
         it is captured once per run shape in a HIP graph (kept by the object) and replayed k_max times back to back.
-        The returned tensors are the object's buffers: the next ``run`` of the same shape overwrites them."""
-        return self._run(state0, goal, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph)
+        The returned tensors are the object's buffers: the next ``run`` of the same shape overwrites them.
+        THE DRIFT MODEL (a fleet with ``drift_sigma`` or a ``matcher``, or a run given ``drift`` as a tensor; any other run takes
+        the code path it always took, bit for bit).  ``state`` stays the TRUE state: it scans the world and is solved for.  A
+        buffer ``drift`` [B,2] holds believed minus true position, zero at the start of a run.  Per sample: the walking robots'
+        drift grows by the sample's draw -- ``drift="seeded"``: N(0, drift_sigma^2) per axis from a generator seeded with
+        ``drift_seed``; a tensor [k_max,B,2]: the draws themselves; None: no draws --; after the scan the believed state and
+        the readings as placed at the believed pose are true + drift; with a ``matcher`` they are matched against the evidence
+        as it stands before this sample's update (walking robots only) and the offset is added to drift, believed state and
+        readings; the map is updated with the believed state and readings; the solve (and the recovery) gets goal - drift,
+        because goals live in the map's frame.  The result gains drift [B,2], pose_error [k_max,B] (|drift| after each sample)
+        and n_matched [B] int32 (accepted non-zero offsets).  The model's limits: position drift only (no yaw), whole-cell
+        corrections, and nothing already written into the map is ever corrected."""
+        return self._run(state0, goal, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, drift=drift, drift_seed=drift_seed)
 
-    def _run(self, state0, goal, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=None):
+    def _run(self, state0, goal, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=None, drift=None,
+             drift_seed=0):
         """``run``; ``before_sample(k, pl)``: called on the host before sample k is enqueued (run_replanning's hook)."""
-        dev, sv, sn, avoid, mapper = self.device, self.solver, self.sensor, self.avoid, self.mapper
+        dev, sv, sn, avoid, mapper, matcher = self.device, self.solver, self.sensor, self.avoid, self.mapper, self.matcher
         B = state0.shape[0]
         mode = "none" if noise is None else ("seeded" if isinstance(noise, str) else "given")
-        pl = self._plan_for(B, int(k_max), mode, delta is not None, stop_obj, use_graph)
+        dmode = self._drift_mode(drift)
+        if dmode == "given":
+            _check(drift, (int(k_max), B, 2), torch.float64, dev, "drift")
+        pl = self._plan_for(B, int(k_max), mode, delta is not None, stop_obj, use_graph, dmode)
         fl, sen, out, nbuf, gen, rec = pl["fl"], pl["sen"], pl["out"], pl["nbuf"], pl["gen"], pl.get("rec")
+        dgen = pl.get("dgen")
         pl["goal"].copy_(goal)
         if delta is not None:
             pl["delta"].copy_(delta)
@@ -468,8 +530,57 @@ class UnknownEnvFleet:
             sv.reset_warm_start()                            # every run starts cold (no-op without a record)
             if gen is not None:
                 gen.manual_seed(int(noise_seed))
+            if dmode is not None:
+                pl["drift"].zero_(); pl["n_matched"].zero_(); pl["pose_error"].zero_()
+            if dgen is not None:
+                dgen.manual_seed(int(drift_seed))
+
+        def drifting_sample():
+            # the sample of a fleet whose odometry drifts: `state` is the truth, the map and the goals are in the believed frame
+            drift_, bstate = pl["drift"], pl["bstate"]
+            if gen is not None:
+                nbuf.normal_(0.0, NOISE_STD, generator=gen)
+            if dgen is not None:
+                pl["dbuf"].normal_(0.0, self.drift_sigma, generator=dgen)
+            if dmode != "none":
+                pl["walkf"].copy_(fl["walking"])
+                torch.mul(pl["dbuf"], pl["walkf"][:, None], out=pl["dstep"])
+                drift_.add_(pl["dstep"])
+            sn.sense(fl["state"], nbuf, out=sen, c_eta=True, rings=False, schedule=pl["sched"])
+            if avoid is not None:
+                nbr = avoid.append(fl["state"], sen["c_eta"], first_slot=sen["n_inferred"], out=pl["nbr"])
+                torch.gt(nbr["n_near"], nbr["n_rows"], out=pl["crowded"])
+                pl["n_crowded"].add_(pl["crowded"])
+            bstate.copy_(fl["state"])
+            torch.add(fl["state"][:, 0], drift_[:, 0], out=bstate[:, 0])
+            torch.add(fl["state"][:, 2], drift_[:, 1], out=bstate[:, 2])
+            if mapper is not None:
+                bhits = pl["bhits"]
+                torch.add(sen["hits"], drift_[:, None, :], out=bhits)
+                pl["mask"].copy_(fl["walking"])
+                if matcher is not None:
+                    # against the evidence as it stands before this sample's update (the stream orders the two calls)
+                    m = matcher.match(mapper, bstate, bhits, mask=pl["mask"], out=pl["mout"])
+                    drift_.add_(m["offset"])
+                    bstate[:, 0].add_(m["offset"][:, 0]); bstate[:, 2].add_(m["offset"][:, 1])
+                    bhits.add_(m["offset"][:, None, :])
+                    pl["n_matched"].add_(m["matched"])
+                mapper.update(bstate, bhits, mask=pl["mask"])
+            torch.sub(pl["goal"], drift_, out=pl["bgoal"])      # the goal lives in the map's frame, the solve in the true one
+            sv.plan_step_batch_c_eta(fl["state"], pl["bgoal"], fl["first_foot"], sen["c_eta"], pl["delta"], out=out,
+                                     overflow=sen["overflow"])
+            torch.mul(drift_, drift_, out=pl["dstep"])
+            torch.sum(pl["dstep"], dim=1, out=pl["perr"])
+            pl["perr"].sqrt_()
 
         def sample():
+            if dmode is not None:
+                drifting_sample()
+                return finish(pl["bgoal"])
+            plain_sample()
+            finish(pl["goal"])
+
+        def plain_sample():
             # HumanoidMpc.py:387/:417 sense + solve; :392 stop rule, :419-429 failed solve ends the run, :432-447 advance
             # and the trajectory row: one bookkeeping launch (lipmpc_fleet_update_batch)
             if gen is not None:
@@ -488,12 +599,15 @@ class UnknownEnvFleet:
                     mapper.update(fl["state"], sen["hits"], mask=pl["mask"])
                 sv.plan_step_batch_c_eta(fl["state"], pl["goal"], fl["first_foot"], sen["c_eta"], pl["delta"], out=out,
                                          overflow=sen["overflow"])
+
+        def finish(working):
+            # ``working``: the goals the solve was given
             if rec is None:
                 sv.fleet_update(fl, out, overflow=sen["overflow"], stop_obj=stop_obj)
             else:
                 # the rows the solve was given (the scan's, then the neighbours') vouch for the capture step
                 sv.fleet_update(fl, out, overflow=sen["overflow"], stop_obj=stop_obj,
-                                recover=dict(rec, goal=pl["goal"], c_eta=sen["c_eta"], delta=pl["delta"], max_recover=self.recover))
+                                recover=dict(rec, goal=working, c_eta=sen["c_eta"], delta=pl["delta"], max_recover=self.recover))
                 # NaN = not evaluated in this sample (an evaluated margin is never NaN): keep the robot's last evaluated one
                 torch.ne(rec["recover_margin"], rec["recover_margin"], out=pl["not_evaluated"])
                 torch.where(pl["not_evaluated"], pl["last_margin"], rec["recover_margin"], out=pl["last_margin"])
@@ -502,6 +616,8 @@ class UnknownEnvFleet:
             reset()
             if mode == "given":
                 nbuf.copy_(noise[0])
+            if dmode == "given":
+                pl["dbuf"].copy_(drift[0])
             side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
@@ -513,6 +629,8 @@ class UnknownEnvFleet:
             graph = torch.cuda.CUDAGraph()
             if gen is not None:
                 graph.register_generator_state(gen)          # the draw is part of the graph: every replay advances the stream
+            if dgen is not None:
+                graph.register_generator_state(dgen)
             with torch.cuda.graph(graph):
                 sample()
             pl["graph"] = graph
@@ -522,20 +640,26 @@ class UnknownEnvFleet:
                 before_sample(k, pl)
             if mode == "given":
                 nbuf.copy_(noise[k])
+            if dmode == "given":
+                pl["dbuf"].copy_(drift[k])
             if use_graph:
                 pl["graph"].replay()
             else:
                 sample()
+            if dmode is not None:
+                pl["pose_error"][k].copy_(pl["perr"])
         res = dict(X_pred=fl["X_pred"], U_pred=fl["U_pred"], n_steps=fl["n_steps"], last_status=fl["last_status"],
                    overflow=fl["n_overflow"])
         if rec is not None:
             res.update(n_recover=rec["n_recover"], recover_run=rec["recover_run"], recover_margin=pl["last_margin"])
         if avoid is not None:
             res["n_crowded"] = pl["n_crowded"]
+        if dmode is not None:
+            res.update(drift=pl["drift"], pose_error=pl["pose_error"], n_matched=pl["n_matched"])
         return res
 
     def run_replanning(self, state0, goal, first_foot, k_max, planner, replan_every, lookahead, noise="seeded", noise_seed=0,
-                       delta=None, stop_obj=0.05, use_graph=True, seeds=None, S_max=None, min_evidence=None):
+                       delta=None, stop_obj=0.05, use_graph=True, seeds=None, S_max=None, min_evidence=None, drift="seeded", drift_seed=0):
         """``run`` with a global planner on the map the fleet builds (``mapper`` is required): a robot that the reactive loop
         leaves in a dead end re-plans on what it has seen and walks out.  The loop is driven from the host, all per-robot work
         runs on the device, nothing is copied device -> host per sample.  Every ``replan_every`` samples (sample 0 included):
@@ -549,7 +673,8 @@ class UnknownEnvFleet:
             whose budget of rounds did not settle the field -- the next replan tries again).
         Returns what ``run`` returns, plus n_replans (int), rrt_status [B] of the last plan, working_goal [B,2] and walking [B]
         (int8) as the last sample left them: a robot ARRIVED if it is not walking, its last_status is SOLVED or UNCERTIFIED
-        (the stop rule stopped it, not a failed solve) and its working goal is its final goal."""
+        (the stop rule stopped it, not a failed solve) and its working goal is its final goal.
+        ``drift`` / ``drift_seed``: as ``run``'s; in a fleet with a drift model every plan starts from the BELIEVED positions."""
         from .planner import RRT_FOUND
         from .solver import STATUS_SOLVED, STATUS_UNCERTIFIED
         if self.mapper is None:
@@ -566,7 +691,7 @@ class UnknownEnvFleet:
             if k % replan_every:
                 return
             fl, working = pl["fl"], pl["goal"]
-            pos = fl["state"][:, (0, 2)].contiguous()
+            pos = self._believed_positions(pl)
             plan = planner.plan_grid_batch(final, self.mapper.grid_map(min_evidence), pos, seeds=seeds, S_max=S_max)
             # stopped by the stop rule (not by a failed solve: that leaves its status), at a goal that was not the final one
             solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
@@ -577,7 +702,8 @@ class UnknownEnvFleet:
             info["n_replans"] += 1
             info["rrt_status"] = plan["status"]
 
-        res = self._run(state0, final, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=replan)
+        res = self._run(state0, final, first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=replan, drift=drift,
+                        drift_seed=drift_seed)
         res.update(info, working_goal=self._plan["goal"], walking=self._plan["fl"]["walking"])
         return res
 
@@ -617,7 +743,10 @@ class UnknownEnvFleet:
         walking [B] (int8), n_frontier and known_free [n_replans,F] (device tensors: per replan the frontier cells, and the cells
         with evidence <= -t_free, of every map), and done [B] (bool): not walking, not stopped by a failed solve, and the closing
         plan said RRT_NO_PATH -- for the robot nothing is left to explore.  The tensors are the object's or fresh ones; the
-        next run of the same shape overwrites the former."""
+        next run of the same shape overwrites the former.
+        In a fleet with a drift model (``run``) every plan, and the first look round, start from the BELIEVED positions; the run's
+        ``drift`` and ``drift_seed`` are the fleet's ``exploring_drift`` ("seeded"; None or a tensor [k_max,B,2] as ``run`` takes
+        them) and ``exploring_drift_seed`` (0), attributes to set before the call: this method's parameter list stays as it is."""
         from .planner import RRT_FOUND, RRT_NO_PATH, CoordinatedFrontierPlanner
         from .solver import STATUS_SOLVED, STATUS_UNCERTIFIED
         mapper = self.mapper
@@ -653,8 +782,14 @@ class UnknownEnvFleet:
             if k == 0 and not closing:
                 # the first look round, noise-free: the run's own scans start with sample 0
                 self.sensor.sense(fl["state"], None, out=pl["sen"], c_eta=True, rings=False, schedule=pl["sched"])
-                mapper.update(fl["state"], pl["sen"]["hits"])
-            pos = fl["state"][:, (0, 2)].contiguous()
+                if "drift" in pl:
+                    # (the drift is zero before sample 0: the same numbers, from the buffers the samples use)
+                    believed = fl["state"].clone()
+                    believed[:, (0, 2)] += pl["drift"]
+                    mapper.update(believed, pl["sen"]["hits"] + pl["drift"][:, None, :])
+                else:
+                    mapper.update(fl["state"], pl["sen"]["hits"])
+            pos = self._believed_positions(pl)
             solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)
             claim = dict(may_claim=solved.to(torch.int8)) if coordinated else {}
             if keeping:
@@ -688,7 +823,8 @@ class UnknownEnvFleet:
             fl["walking"].masked_fill_(~found, 0)
             info["explore_status"] = plan["status"]
 
-        res = self._run(state0, state0[:, (0, 2)], first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=replan)
+        res = self._run(state0, state0[:, (0, 2)], first_foot, k_max, noise, noise_seed, delta, stop_obj, use_graph, before_sample=replan,
+                        drift=self.exploring_drift, drift_seed=self.exploring_drift_seed)
         fl = self._plan["fl"]
         replan(k_max, self._plan, closing=True)
         solved = (fl["last_status"] == STATUS_SOLVED) | (fl["last_status"] == STATUS_UNCERTIFIED)

@@ -1,17 +1,20 @@
 """Occupancy mapping: LiDAR scans integrated into an evidence grid on the device -- host wrapper of lipmpc_map_update_batch
 (include/lipmpc.h).  ``OccupancyMapper.update`` adds one scan per robot (+w_hit on the cells the readings lie in, -w_miss on the
 cells the rays passed through); ``grid_map`` thresholds the evidence into the ``GridMap`` that ``RrtStarPlanner.plan_grid_batch``
-plans on and a grid sensor scans.  ``UnknownEnvFleet(..., mapper=OccupancyMapper(...))`` does the update every sample."""
+plans on and a grid sensor scans.  ``UnknownEnvFleet(..., mapper=OccupancyMapper(...))`` does the update every sample.
+``ScanMatcher.match`` (lipmpc_scan_match_batch) finds where a scan fits the evidence best: the pose correction of a fleet whose
+odometry drifts (``UnknownEnvFleet(..., mapper=, drift_sigma=, matcher=ScanMatcher(...))``)."""
 from __future__ import annotations
 
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
 from .lidar import GridMap, ray_table
-from .solver import _check
+from .solver import _alloc, _check, _check_table, _named
 
 WEIGHT_MAX = 32767
 
@@ -85,3 +88,75 @@ class OccupancyMapper:
         """The cells KNOWN to be free as a ``GridMap`` (nonzero = free): evidence <= max_evidence (default -w_miss)."""
         thr = -self.w_miss if max_evidence is None else int(max_evidence)
         return GridMap(self.evidence <= thr, self.origin, self.cell)
+
+
+def match_outputs(B):
+    """The outputs of lipmpc_scan_match_batch: name -> (dtype, shape, required)."""
+    return {"offset_cells": (torch.int32, (B, 2), True), "yaw_index": (torch.int32, (B,), True), "offset": (torch.float64, (B, 2), True),
+            "score": (torch.int32, (B, 2), True), "n_used": (torch.int32, (B,), True), "matched": (torch.int8, (B,), True)}
+
+
+class ScanMatcher:
+    """A correlative scan matcher on a mapper's evidence (lipmpc_scan_match_batch): where is a robot on the map it builds?  Every
+    whole-cell shift (a, b) with |a| <= ``n_x``, |b| <= ``n_y`` of the believed position -- and, with ``n_yaw`` > 0, every yaw
+    (k - n_yaw) * ``yaw_step`` of the scan about it -- is scored by the evidence, clamped to +-``clamp`` (1..127), under the
+    scan's hit cells; the best candidate is accepted if its score is at least ``min_score`` and beats the unshifted scan's by at
+    least ``min_gain`` (>= 0).  The three scoring parameters have no defaults: nobody has measured one.  n_x, n_y, n_yaw: 0..16.
+    The rule: include/lipmpc.h."""
+
+    N_MAX, CLAMP_MAX = 16, 127
+
+    def __init__(self, n_x, n_y, *, clamp, min_score, min_gain, n_yaw=0, yaw_step=None):
+        self.n_x, self.n_y, self.n_yaw = int(n_x), int(n_y), int(n_yaw)
+        self.clamp, self.min_score, self.min_gain = int(clamp), int(min_score), int(min_gain)
+        if not all(0 <= n <= self.N_MAX for n in (self.n_x, self.n_y, self.n_yaw)):
+            raise ValueError(f"n_x, n_y and n_yaw must be 0..{self.N_MAX}")
+        if not 1 <= self.clamp <= self.CLAMP_MAX or self.min_gain < 0 or not -2 ** 31 <= self.min_score < 2 ** 31:
+            raise ValueError(f"clamp must be 1..{self.CLAMP_MAX}, min_gain >= 0, min_score an int32")
+        if self.n_yaw and (yaw_step is None or not math.isfinite(float(yaw_step))):
+            raise ValueError("n_yaw > 0 needs a finite yaw_step")
+        self.yaw_step = None if yaw_step is None else float(yaw_step)
+        # (cos, sin) of (k - n_yaw) * yaw_step, evaluated once on the host: the kernel takes the table, it calls no cos or sin
+        self.rot = None
+        if self.n_yaw:
+            ang = (np.arange(2 * self.n_yaw + 1) - self.n_yaw).astype(np.float64) * np.float64(self.yaw_step)
+            self.rot = np.stack([np.cos(ang), np.sin(ang)], axis=1)
+        self._tables = {}                                    # device -> the table there
+
+    def alloc_outputs(self, B, device):
+        table = match_outputs(B)
+        return _alloc(table, table, device)
+
+    def _rot_on(self, device):
+        if self.rot is None:
+            return None
+        if device not in self._tables:
+            self._tables[device] = torch.as_tensor(self.rot, device=device)
+        return self._tables[device]
+
+    def match(self, mapper, state, hits, mask=None, out=None):
+        """Match one scan per robot against ``mapper.evidence``: state [B,5] the BELIEVED pose (only p_x, p_y are read), hits
+        [B,resolution,2] the readings as placed at that pose (NaN = no reading), mask [B] int32 or None (0 = the robot gets
+        zeros).  Geometry, lidar_range, depth and resolution are the mapper's.  Returns dict(offset_cells [B,2] int32, yaw_index
+        [B] int32, offset [B,2] float64 = the shift in map units, score [B,2] int32 (best before the acceptance test, unshifted),
+        n_used [B] int32, matched [B] int8) -- ``out`` when given (``alloc_outputs``): then the call makes no allocation and can
+        be captured in a graph (with n_yaw > 0 after one call outside the capture: the first puts the yaw table on the device).
+        Asynchronous on the current stream; the evidence is only read."""
+        dev = mapper.device
+        B = state.shape[0]
+        _check(state, (B, 5), torch.float64, dev, "state", required=True)
+        _check(hits, (B, mapper.resolution, 2), torch.float64, dev, "hits", required=True)
+        _check(mask, (B,), torch.int32, dev, "mask")
+        if mapper.per_robot is not None and B != mapper.per_robot:
+            raise ValueError(f"a mapper of {mapper.per_robot} per-robot maps takes batches of that size, not {B}")
+        if out is None:
+            out = self.alloc_outputs(B, dev)
+        else:
+            _check_table(match_outputs(B), out, dev, "out")
+        _lib.call("lipmpc_scan_match_batch", device=mapper.device_index, B=B, resolution=mapper.resolution, W=mapper.W, H=mapper.H,
+                  grid_shared=int(mapper.shared), origin=C.addressof(mapper._origin_c), cell=C.addressof(mapper._cell_c),
+                  lidar_range=mapper.lidar_range, depth=mapper.depth, n_x=self.n_x, n_y=self.n_y, n_yaw=self.n_yaw,
+                  rot_table=self._rot_on(dev), clamp=self.clamp, min_score=self.min_score, min_gain=self.min_gain, state=state,
+                  hits=hits, mask=mask, evidence=mapper.evidence, **_named(out, match_outputs(B)),
+                  hip_stream=torch.cuda.current_stream(dev).cuda_stream)
+        return out

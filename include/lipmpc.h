@@ -49,7 +49,8 @@ extern "C" {
                                 *      lipmpc_grid_frontier_field_weighted_batch / lipmpc_grid_path_weighted_batch /
                                 *      lipmpc_grid_frontier_path_weighted_batch, LIPMPC_COST_MAX;
                                 *    + lipmpc_grid_path_wave_batch / lipmpc_grid_frontier_path_wave_batch /
-                                *      lipmpc_grid_frontier_utility_path_wave_batch */
+                                *      lipmpc_grid_frontier_utility_path_wave_batch;
+                                *    + lipmpc_scan_match_batch */
 /* An instrumented development build (tools/build_variant.sh: phase counters in `diag`, other buffer contracts) reports
  * LIPMPC_ABI_VERSION + LIPMPC_VARIANT_BASE from lipmpc_version(), so that a loader which checks the version refuses it. */
 #define LIPMPC_VARIANT_BASE 1000
@@ -538,6 +539,51 @@ int lipmpc_map_update_batch(int device, int64_t B, int32_t resolution, int32_t W
                             const double* origin, const double* cell, double lidar_range, double depth, int32_t w_hit,
                             int32_t w_miss, const double* state, const double* hits, const double* ray_table,
                             const int32_t* mask, int32_t* evidence, void* hip_stream);
+
+/* CORRELATIVE SCAN MATCHING (backward-compatible addition): lipmpc_scan_match_batch -- where a robot is ON THE MAP IT BUILDS.  Per
+ * robot a window of candidate poses (whole-cell shifts (a, b) of the believed position and a table of yaws) is scored by the
+ * evidence under the scan's hit cells, and the best candidate is returned (Olson 2009, over whole cells).  The evidence is only
+ * read.  Asynchronous on hip_stream; no allocation and no host synchronisation, so the call can be captured in a graph.
+ *  resolution, W, H, grid_shared, origin, cell, lidar_range, depth: as lipmpc_map_update_batch takes them
+ *  n_x, n_y   0..16: the search half-widths in cells;  n_yaw 0..16: the yaw half-width, T = 2 n_yaw + 1 yaws
+ *  rot_table  [T,2] doubles on the device: (cos, sin) of (k - n_yaw) * yaw_step as the caller evaluated them (numpy); may be NULL
+ *             only when n_yaw == 0; entry n_yaw is never read (it stands for (1, 0))
+ *  clamp      1..127;  min_score any int32;  min_gain >= 0
+ *  state      [B,5]  the BELIEVED pose; only (p_x, p_y) = p0 are read
+ *  hits       [B,resolution,2] the readings as placed at that pose, a NaN coordinate = no reading
+ *  mask       [B] int32 or NULL: a robot with mask == 0 gets zeros in every output and nothing else of it is read
+ *  evidence   int32, [W,H] if grid_shared else [B,W,H], READ ONLY (plain reads: order the call before an update by the stream)
+ * THE RULE, in IEEE double, no contraction, division and square root correctly rounded, every expression evaluated as written:
+ *  - robot cell c0 = (ci, cj), the window half-widths (mx, my) and, for reading r, the END POINT e_r with its validity tests:
+ *    exactly lipmpc_map_update_batch's (mx, my are its nx, ny).  A robot without a cell gets zeros in every output.
+ *  - yaw index k = n_yaw: the rotated end point is e_r itself, NO ARITHMETIC -- the zero candidate scores exactly the cells the
+ *    update would raise.  Any other k, with (c, s) = rot_table[k] and (rx, ry) = (e_x - x0, e_y - y0):
+ *    x = x0 + (c * rx - s * ry), y = y0 + (s * rx + c * ry).
+ *  - its cell (i, j): fi' = floor((x - ox) / dx), fj' = floor((y - oy) / dy).  The pair (r, k) is USED if r has a valid end point
+ *    and |fi' - ci| <= mx and |fj' - cj| <= my, the differences taken in double as the update takes them (so an index too large
+ *    for an int, an infinity or a NaN is simply not used); then i = ci + (fi' - ci), j likewise.
+ *  - V(i, j) = min(max(evidence(i, j), -clamp), clamp) inside the map, 0 outside.
+ *  - score(k, a, b) = sum over the used (r, k) of V(i + a, j + b), |a| <= n_x, |b| <= n_y: every reading counts, also two in a cell.
+ *  - THE BEST candidate minimises (-score, a * a + b * b, |k - n_yaw|, k, (a + n_x) * (2 n_y + 1) + (b + n_y)) lexicographically:
+ *    integers and a total order, so the result does not depend on thread order; an empty map returns the zero candidate.
+ *  - it is ACCEPTED if score_best >= min_score and score_best - score_zero >= min_gain (score_zero: k = n_yaw, a = b = 0);
+ *    otherwise the zero candidate is returned.
+ * OUTPUTS, all written for every robot:
+ *  offset_cells [B,2] int32 (a, b);  yaw_index [B] int32 k - n_yaw;  offset [B,2] double (a * dx, b * dy), one product each
+ *  score      [B,2] int32: the best candidate's BEFORE the acceptance test, and the zero candidate's
+ *  n_used     [B] int32: the used pairs at k = n_yaw;  matched [B] int8: accepted and not the zero candidate
+ * Reproduced bit for bit in numpy by tests/scan_match_oracle.py.
+ * The update's window grown by (n_x, n_y), (2 (mx + n_x) + 1) x (2 (my + n_y) + 1) cells, is kept as one signed byte per cell in
+ * the kernel's LDS: more than 49152 cells are refused with LIPMPC_E_UNSUPPORTED before anything is enqueued.  Other refusals
+ * (LIPMPC_E_ARG): what lipmpc_map_update_batch refuses of the shared arguments, n_x, n_y or n_yaw outside 0..16, clamp outside
+ * 1..127, min_gain < 0, n_yaw > 0 with a null rot_table, a null state / hits / evidence / output / origin / cell.  B == 0
+ * enqueues nothing. */
+int lipmpc_scan_match_batch(int device, int64_t B, int32_t resolution, int32_t W, int32_t H, int32_t grid_shared,
+                            const double* origin, const double* cell, double lidar_range, double depth, int32_t n_x, int32_t n_y,
+                            int32_t n_yaw, const double* rot_table, int32_t clamp, int32_t min_score, int32_t min_gain,
+                            const double* state, const double* hits, const int32_t* mask, const int32_t* evidence,
+                            int32_t* offset_cells, int32_t* yaw_index, double* offset, int32_t* score, int32_t* n_used,
+                            int8_t* matched, void* hip_stream);
 
 /* RRT* SUB-GOAL PLANNER (backward-compatible addition): the global planner of HumanoidMPCWithRRT
  * (HumanoidMPCVariants/HumanoidMPCWithRRT.py:21-135) for B independent problems, one workgroup per problem.  Per problem b:
