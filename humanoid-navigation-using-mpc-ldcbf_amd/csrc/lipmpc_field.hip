@@ -1726,18 +1726,93 @@ __global__ void __launch_bounds__(FIELD_THREADS) frontier_assign_keep_utility_gl
                            sub_goals, n_sub, status, path_cost, target_cell, target_gain, claim_round, n_claims, kept, n_kept);
 }
 
-// E_ARG of a grid's placement
+// =====================================================================================================================
+// WHAT A CALL REFUSES, for every entry point of this translation unit.  A call decides in this order: LIPMPC_E_ARG, LIPMPC_E_UNSUPPORTED
+// (a shape beyond the caps), a zero count returns LIPMPC_OK, then the device is selected -- the first HIP call: nothing is enqueued
+// before.  Each family of arguments states its legal range ONCE, as a bad_*() predicate that is true for E_ARG; an entry point is a
+// short list of families, a cap and its launches.  All E_ARG share one code, so their order cannot be seen; what CAN be seen, and
+// differs from call to call, is whether the pointers are tested EARLY or only behind the caps and the zero count (LATE): each call
+// says which where it does it, and tests/test_field_refusals_build.py pins all of it.
+constexpr int64_t TILED_MAX_CELLS = 1 << 24;          // of the tiled calls: a finite value stays below 7 * 2^24, the additions cannot wrap
+constexpr int64_t TILED_MAX_THREADS = (int64_t)1 << 31;                   // of one launch: F * (W * H + 64) stays within it
+constexpr int MAX_ROUNDS = 65536;
+constexpr int64_t CLAIM_MAX_LAUNCHES = 1 << 20;       // max_claims * max_rounds of one tiled claim call
+
+template <typename... P> inline bool any_null(const P*... p) { return (... || !p); }
+
+inline bool bad_count(int64_t n) { return n < 0 || n > 0x7fffffff; }
+inline bool bad_shape(int32_t W, int32_t H) { return W < 2 || H < 2; }
+inline bool bad_grid(int32_t W, int32_t H, int32_t r_inflate) { return bad_shape(W, H) || r_inflate < 0 || r_inflate > R_INFLATE_MAX; }
+// a grid's placement, read on the host
 bool bad_placement(const double* origin, const double* cell) {
   if (!origin || !cell) return true;
   const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
   return !(dx > 0.0) || !(dy > 0.0) || !(dx < INFINITY) || !(dy < INFINITY) || !(fabs(ox) < INFINITY) || !(fabs(oy) < INFINITY);
 }
+inline bool bad_placed_grid(int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate) {
+  return bad_grid(W, H, r_inflate) || bad_placement(origin, cell);
+}
+inline bool bad_threshold(int32_t t) { return t < 1 || t > THRESHOLD_MAX; }            // t_free, t_occ
+inline bool bad_min_unknown(int32_t min_unknown) { return min_unknown < 1 || min_unknown > 8; }
+inline bool bad_view(int32_t r_view) { return r_view < 1 || r_view > R_VIEW_MAX; }
+inline bool bad_walk(int32_t max_seg, int32_t S_max) { return max_seg < 5 || S_max < 1; }
+// a path call: B robots down one shared field or down a field each
+inline bool bad_path(int64_t B, int64_t F, int32_t max_seg, int32_t S_max) {
+  return bad_count(B) || (F != 1 && F != B) || bad_walk(max_seg, S_max);
+}
+// a claim call, one-workgroup or tiled: its scalars and the pointers that the form needs (never `may_claim`), EARLY in every form
+template <typename... P> bool bad_claim(int64_t B, int32_t r_claim, int32_t max_claims, int32_t max_seg, int32_t S_max, const P*... needed) {
+  return bad_count(B) || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || bad_walk(max_seg, S_max) ||
+         any_null(needed...);
+}
+inline bool bad_keep(int32_t r_keep, int32_t keep_ratio16, int32_t keep_slack) {
+  return r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
+         keep_slack > KEEP_SLACK_MAX;
+}
+inline bool bad_gain(int32_t w_gain, int32_t g_cap, int32_t min_gain) {
+  return w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX;
+}
+// the rounds of a tiled call: max_rounds, and `resume` where the call has it
+inline bool bad_rounds(int32_t rounds, int32_t resume = 0) { return rounds < 1 || rounds > MAX_ROUNDS || (resume != 0 && resume != 1); }
+// what a claim call on a large map adds: a workspace that starts on 8 bytes (its 64-bit keys) and the rounds ...
+bool bad_claim_rounds(const void* work, int32_t rounds, int32_t resume = 0) { return ((uintptr_t)work & 7) != 0 || bad_rounds(rounds, resume); }
+// ... and, where every claim relaxes a field of its own, max_claims * max_rounds launches
+inline bool too_many_launches(int32_t max_claims, int32_t max_rounds) { return (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES; }
 
-// what both entry points refuse about the grid: E_ARG, then the caps
-int grid_refusal(int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate) {
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+// the caps, behind every E_ARG: of the one-workgroup calls ...
+int group_cap_refusal(int32_t W, int32_t H) {
+  return W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS ? LIPMPC_E_UNSUPPORTED : LIPMPC_OK;
+}
+// ... and of the tiled calls, for F fields of the shape
+int tiled_cap_refusal(int64_t F, int32_t W, int32_t H) {
+  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > TILED_MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (F > 0 && F * ((int64_t)W * H + 64) > TILED_MAX_THREADS) return LIPMPC_E_UNSUPPORTED;
   return LIPMPC_OK;
+}
+// what the one-workgroup calls with a placed grid refuse about it: E_ARG, then the caps
+int grid_refusal(int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate) {
+  return bad_placed_grid(W, H, origin, cell, r_inflate) ? LIPMPC_E_ARG : group_cap_refusal(W, H);
+}
+// what the path calls on large maps (tiled, weighted, wave) refuse about their shape: E_ARG, then the tiled caps for F fields -- a
+// path call needs no LDS sized to the map
+int tiled_path_refusal(int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate,
+                       int32_t max_seg, int32_t S_max) {
+  if (bad_path(B, F, max_seg, S_max) || bad_placed_grid(W, H, origin, cell, r_inflate)) return LIPMPC_E_ARG;
+  return tiled_cap_refusal(F, W, H);
+}
+
+// LAUNCH SET-UP.  A kernel's dynamic LDS above 64 KiB needs leave; false where the runtime refuses it (LIPMPC_E_HIP)
+template <typename Kernel> bool lds_allowed(Kernel kernel, size_t lds) {
+  return lds <= 64 * 1024 || hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+}
+inline int launched() { return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP; }
+inline dim3 path_grid(int64_t B) { return dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)); }
+// one of a pair of FIELD_THREADS kernels with the same arguments: the field in LDS (`lds` bytes, sized to the map) or in global memory
+template <typename Kernel, typename... Args>
+int launch_field(bool in_lds, Kernel lds_kernel, Kernel global_kernel, int64_t F, size_t lds, void* hip_stream, Args... args) {
+  if (in_lds && !lds_allowed(lds_kernel, lds)) return LIPMPC_E_HIP;
+  hipLaunchKernelGGL(in_lds ? lds_kernel : global_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, (hipStream_t)hip_stream, args...);
+  return launched();
 }
 
 }  // namespace
@@ -1745,68 +1820,47 @@ int grid_refusal(int32_t W, int32_t H, const double* origin, const double* cell,
 extern "C" int lipmpc_grid_field_batch(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin,
                                        const double* cell, const uint8_t* occ, const double* goal, int32_t r_inflate,
                                        uint32_t* field, int32_t* field_status, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff) return LIPMPC_E_ARG;
+  if (bad_count(F)) return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (F == 0) return LIPMPC_OK;
-  if (!occ || !goal || !field || !field_status) return LIPMPC_E_ARG;
+  if (any_null(occ, goal, field, field_status)) return LIPMPC_E_ARG;          // LATE: F == 0 passes with any of them null
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
   const int64_t ncells = (int64_t)W * H, stride = grid_shared ? 0 : ncells;
   const bool in_lds = field_fits_lds(ncells);
-  const size_t lds = (size_t)field_lds_bytes(ncells, in_lds);
-  if (in_lds) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)grid_field_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-      return LIPMPC_E_HIP;
-    hipLaunchKernelGGL(grid_field_lds_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, stride, origin[0], origin[1],
-                       cell[0], cell[1], occ, goal, r_inflate, field, field_status);
-  } else {
-    hipLaunchKernelGGL(grid_field_global_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, stride, origin[0], origin[1],
-                       cell[0], cell[1], occ, goal, r_inflate, field, field_status);
-  }
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launch_field(in_lds, grid_field_lds_kernel, grid_field_global_kernel, F, (size_t)field_lds_bytes(ncells, in_lds), hip_stream, W, H,
+                      stride, origin[0], origin[1], cell[0], cell[1], occ, goal, r_inflate, field, field_status);
 }
 
 extern "C" int lipmpc_grid_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell,
                                       const uint8_t* occ, int32_t grid_shared, const uint32_t* field, const int32_t* field_status,
                                       const double* goal, const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
                                       double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
+  if (bad_path(B, F, max_seg, S_max)) return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!occ || !field || !field_status || !goal || !start || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
+  // LATE: B == 0 passes with any of them null
+  if (any_null(occ, field, field_status, goal, start, sub_goals, n_sub, status, path_cost)) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(grid_path_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1],
-                     cell[0], cell[1], occ, field, field_status, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
-                     path_cost);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(grid_path_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
+                     grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1], cell[0], cell[1], occ, field, field_status, goal, start,
+                     r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_field_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
                                                 int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier,
                                                 uint32_t* field, int32_t* n_frontier, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
-      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || !field || !n_frontier)
+  // (the pointers EARLY, unlike lipmpc_grid_field_batch: a null one is E_ARG whatever the shape and F; `frontier` may be null)
+  if (bad_count(F) || bad_grid(W, H, r_inflate) || bad_threshold(t_free) || bad_threshold(t_occ) || bad_min_unknown(min_unknown) ||
+      any_null(evidence, field, n_frontier))
     return LIPMPC_E_ARG;
-  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (const int rc = group_cap_refusal(W, H)) return rc;
   if (F == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
   const int64_t ncells = (int64_t)W * H;
   const bool in_lds = frontier_fits_lds(ncells);
-  const size_t lds = (size_t)frontier_lds_bytes(ncells, in_lds);
-  if (in_lds) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_field_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-      return LIPMPC_E_HIP;
-    hipLaunchKernelGGL(frontier_field_lds_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, evidence, t_free, t_occ,
-                       r_inflate, min_unknown, frontier, field, n_frontier);
-  } else {
-    hipLaunchKernelGGL(frontier_field_global_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, evidence, t_free, t_occ,
-                       r_inflate, min_unknown, frontier, field, n_frontier);
-  }
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launch_field(in_lds, frontier_field_lds_kernel, frontier_field_global_kernel, F, (size_t)frontier_lds_bytes(ncells, in_lds),
+                      hip_stream, W, H, evidence, t_free, t_occ, r_inflate, min_unknown, frontier, field, n_frontier);
 }
 
 extern "C" int lipmpc_grid_frontier_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -1814,15 +1868,16 @@ extern "C" int lipmpc_grid_frontier_path_batch(int device, int64_t B, int64_t F,
                                                const int32_t* n_frontier, const double* start, int32_t r_inflate, int32_t max_seg,
                                                int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                                int32_t* target_cell, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
+  if (bad_path(B, F, max_seg, S_max) || bad_threshold(t_occ)) return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!evidence || !field || !n_frontier || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell) return LIPMPC_E_ARG;
+  // LATE: B == 0 passes with any of them null
+  if (any_null(evidence, field, n_frontier, start, sub_goals, n_sub, status, path_cost, target_cell)) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(frontier_path_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, field,
-                     n_frontier, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(frontier_path_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0],
+                     origin[1], cell[0], cell[1], evidence, t_occ, field, n_frontier, start, r_inflate, max_seg, S_max, sub_goals, n_sub,
+                     status, path_cost, target_cell);
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
@@ -1831,8 +1886,9 @@ extern "C" int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t 
                                                  int32_t max_seg, int32_t S_max, uint32_t* work, double* sub_goals, int32_t* n_sub,
                                                  int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
                                                  int32_t* n_claims, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      !frontier || !field || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round || !n_claims)
+  // (the pointers EARLY in every claim call, `work` included even where the field will fit LDS)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, start, work, sub_goals, n_sub, status, path_cost, target_cell,
+                claim_round, n_claims))
     return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (B == 0) return LIPMPC_OK;
@@ -1841,10 +1897,8 @@ extern "C" int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t 
   const int64_t ncells = (int64_t)W * H;
   const bool in_lds = assign_fits_lds(ncells);
   const size_t lds = (size_t)assign_lds_bytes(ncells, in_lds);
-  if (in_lds) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-      return LIPMPC_E_HIP;
+  if (in_lds) {                                         // (the pair differs by `work`: two launches)
+    if (!lds_allowed(frontier_assign_lds_kernel, lds)) return LIPMPC_E_HIP;
     hipLaunchKernelGGL(frontier_assign_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0], cell[1],
                        frontier, field, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max, sub_goals, n_sub, status,
                        path_cost, target_cell, claim_round, n_claims);
@@ -1853,7 +1907,7 @@ extern "C" int lipmpc_grid_frontier_assign_batch(int device, int64_t B, int32_t 
                        cell[1], frontier, field, start, may_claim, r_inflate, r_claim, max_claims, max_seg, S_max, work, sub_goals,
                        n_sub, status, path_cost, target_cell, claim_round, n_claims);
   }
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_assign_keep_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
@@ -1864,10 +1918,9 @@ extern "C" int lipmpc_grid_frontier_assign_keep_batch(int device, int64_t B, int
                                                       double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                                       int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, int8_t* kept,
                                                       int32_t* n_kept, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
-      keep_slack > KEEP_SLACK_MAX || !frontier || !field || !start || !prev_target || !work || !sub_goals || !n_sub || !status ||
-      !path_cost || !target_cell || !claim_round || !n_claims || !kept || !n_kept)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, start, prev_target, work, sub_goals, n_sub, status, path_cost,
+                target_cell, claim_round, n_claims, kept, n_kept) ||
+      bad_keep(r_keep, keep_ratio16, keep_slack))
     return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (B == 0) return LIPMPC_OK;
@@ -1877,9 +1930,7 @@ extern "C" int lipmpc_grid_frontier_assign_keep_batch(int device, int64_t B, int
   const bool in_lds = keep_fits_lds(ncells);
   const size_t lds = (size_t)keep_lds_bytes(ncells, in_lds);
   if (in_lds) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_keep_lds_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return LIPMPC_E_HIP;
+    if (!lds_allowed(frontier_assign_keep_lds_kernel, lds)) return LIPMPC_E_HIP;
     hipLaunchKernelGGL(frontier_assign_keep_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
                        cell[1], frontier, field, start, may_claim, prev_target, r_inflate, r_claim, r_keep, keep_ratio16, keep_slack,
                        max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims, kept, n_kept);
@@ -1889,51 +1940,37 @@ extern "C" int lipmpc_grid_frontier_assign_keep_batch(int device, int64_t B, int
                        max_claims, max_seg, S_max, work, sub_goals, n_sub, status, path_cost, target_cell, claim_round, n_claims, kept,
                        n_kept);
   }
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_gain_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
                                                int32_t t_occ, const uint8_t* frontier, int32_t r_view, int32_t* gain, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
-      r_view < 1 || r_view > R_VIEW_MAX || !evidence || !frontier || !gain)
+  if (bad_count(F) || bad_shape(W, H) || bad_threshold(t_free) || bad_threshold(t_occ) || bad_view(r_view) ||
+      any_null(evidence, frontier, gain))                 // (the pointers EARLY)
     return LIPMPC_E_ARG;
-  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (const int rc = group_cap_refusal(W, H)) return rc;
   if (F == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   const int64_t ncells = (int64_t)W * H;
   const size_t lds = (size_t)gain_lds_bytes(ncells, r_view);
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)frontier_gain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return LIPMPC_E_HIP;
+  if (!lds_allowed(frontier_gain_kernel, lds)) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(frontier_gain_kernel, dim3((unsigned)F, (unsigned)((ncells + GAIN_CHUNK - 1) / GAIN_CHUNK)), dim3(GAIN_THREADS), lds,
                      (hipStream_t)hip_stream, W, H, evidence, t_free, t_occ, frontier, r_view, gain);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_utility_field_batch(int device, int64_t F, int32_t W, int32_t H, const uint8_t* frontier,
                                                         const uint32_t* field, const int32_t* gain, int32_t w_gain, int32_t g_cap,
                                                         int32_t min_gain, uint32_t* ufield, int32_t* n_sources, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 ||
-      min_gain > G_CAP_MAX || !frontier || !field || !gain || !ufield || !n_sources)
-    return LIPMPC_E_ARG;
-  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
+  if (bad_count(F) || bad_shape(W, H) || bad_gain(w_gain, g_cap, min_gain) || any_null(frontier, field, gain, ufield, n_sources))
+    return LIPMPC_E_ARG;                                  // (the pointers EARLY)
+  if (const int rc = group_cap_refusal(W, H)) return rc;
   if (F == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipStream_t s = (hipStream_t)hip_stream;
   const int64_t ncells = (int64_t)W * H;
   const bool in_lds = utility_fits_lds(ncells);
-  const size_t lds = (size_t)utility_lds_bytes(ncells, in_lds);
-  if (in_lds) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_utility_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-      return LIPMPC_E_HIP;
-    hipLaunchKernelGGL(frontier_utility_lds_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, frontier, field, gain, w_gain,
-                       g_cap, min_gain, ufield, n_sources);
-  } else {
-    hipLaunchKernelGGL(frontier_utility_global_kernel, dim3((unsigned)F), dim3(FIELD_THREADS), lds, s, W, H, frontier, field, gain, w_gain,
-                       g_cap, min_gain, ufield, n_sources);
-  }
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launch_field(in_lds, frontier_utility_lds_kernel, frontier_utility_global_kernel, F, (size_t)utility_lds_bytes(ncells, in_lds),
+                      hip_stream, W, H, frontier, field, gain, w_gain, g_cap, min_gain, ufield, n_sources);
 }
 
 extern "C" int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -1943,18 +1980,17 @@ extern "C" int lipmpc_grid_frontier_utility_path_batch(int device, int64_t B, in
                                                        int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                                        int32_t* status, double* path_cost, int32_t* target_cell, int32_t* target_gain,
                                                        void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX || w_gain < 0 ||
-      w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !evidence || !frontier || !gain ||
-      !ufield || !n_sources || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !target_gain)
+  // (the pointers EARLY, unlike the two path calls above: B == 0 with a null one is E_ARG)
+  if (bad_path(B, F, max_seg, S_max) || bad_threshold(t_occ) || bad_gain(w_gain, g_cap, min_gain) ||
+      any_null(evidence, frontier, gain, ufield, n_sources, start, sub_goals, n_sub, status, path_cost, target_cell, target_gain))
     return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(frontier_utility_path_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier,
-                     gain, ufield, n_sources, w_gain, g_cap, min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
-                     path_cost, target_cell, target_gain);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(frontier_utility_path_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
+                     origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier, gain, ufield, n_sources, w_gain, g_cap, min_gain,
+                     start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, target_gain);
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin,
@@ -1965,9 +2001,9 @@ extern "C" int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, 
                                                          double* path_cost, int32_t* target_cell, int32_t* claim_round,
                                                          int32_t* n_claims, const int32_t* gain, int32_t w_gain, int32_t g_cap,
                                                          int32_t min_gain, int32_t* target_gain, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !frontier || !field ||
-      !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round || !n_claims || !gain || !target_gain)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, start, work, sub_goals, n_sub, status, path_cost, target_cell,
+                claim_round, n_claims, gain, target_gain) ||
+      bad_gain(w_gain, g_cap, min_gain))
     return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (B == 0) return LIPMPC_OK;
@@ -1977,9 +2013,7 @@ extern "C" int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, 
   const bool in_lds = uclaim_fits_lds(ncells);
   const size_t lds = (size_t)uclaim_lds_bytes(ncells, in_lds);
   if (in_lds) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_utility_lds_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return LIPMPC_E_HIP;
+    if (!lds_allowed(frontier_assign_utility_lds_kernel, lds)) return LIPMPC_E_HIP;
     hipLaunchKernelGGL(frontier_assign_utility_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1], cell[0],
                        cell[1], frontier, field, gain, w_gain, g_cap, min_gain, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
                        S_max, sub_goals, n_sub, status, path_cost, target_cell, target_gain, claim_round, n_claims);
@@ -1988,7 +2022,7 @@ extern "C" int lipmpc_grid_frontier_assign_utility_batch(int device, int64_t B, 
                        cell[1], frontier, field, gain, w_gain, g_cap, min_gain, start, may_claim, r_inflate, r_claim, max_claims, max_seg,
                        S_max, work, sub_goals, n_sub, status, path_cost, target_cell, target_gain, claim_round, n_claims);
   }
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_assign_keep_utility_batch(
@@ -1998,11 +2032,9 @@ extern "C" int lipmpc_grid_frontier_assign_keep_utility_batch(
     int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, int8_t* kept,
     int32_t* n_kept, const int32_t* gain, const uint32_t* ufield, int32_t w_gain, int32_t g_cap, int32_t min_gain, int32_t* target_gain,
     void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
-      keep_slack > KEEP_SLACK_MAX || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 ||
-      min_gain > G_CAP_MAX || !frontier || !field || !start || !prev_target || !work || !sub_goals || !n_sub || !status || !path_cost ||
-      !target_cell || !claim_round || !n_claims || !kept || !n_kept || !gain || !ufield || !target_gain)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, start, prev_target, work, sub_goals, n_sub, status, path_cost,
+                target_cell, claim_round, n_claims, kept, n_kept, gain, ufield, target_gain) ||
+      bad_keep(r_keep, keep_ratio16, keep_slack) || bad_gain(w_gain, g_cap, min_gain))
     return LIPMPC_E_ARG;
   if (const int rc = grid_refusal(W, H, origin, cell, r_inflate)) return rc;
   if (B == 0) return LIPMPC_OK;
@@ -2012,9 +2044,7 @@ extern "C" int lipmpc_grid_frontier_assign_keep_utility_batch(
   const bool in_lds = keepu_fits_lds(ncells);
   const size_t lds = (size_t)keepu_lds_bytes(ncells, in_lds);
   if (in_lds) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)frontier_assign_keep_utility_lds_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return LIPMPC_E_HIP;
+    if (!lds_allowed(frontier_assign_keep_utility_lds_kernel, lds)) return LIPMPC_E_HIP;
     hipLaunchKernelGGL(frontier_assign_keep_utility_lds_kernel, dim3(1), dim3(FIELD_THREADS), lds, s, B, W, H, origin[0], origin[1],
                        cell[0], cell[1], frontier, field, gain, ufield, w_gain, g_cap, min_gain, start, may_claim, prev_target, r_inflate,
                        r_claim, r_keep, keep_ratio16, keep_slack, max_claims, max_seg, S_max, sub_goals, n_sub, status, path_cost,
@@ -2025,7 +2055,7 @@ extern "C" int lipmpc_grid_frontier_assign_keep_utility_batch(
                        r_claim, r_keep, keep_ratio16, keep_slack, max_claims, max_seg, S_max, work, sub_goals, n_sub, status, path_cost,
                        target_cell, target_gain, claim_round, n_claims, kept, n_kept);
   }
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 // =====================================================================================================================
@@ -2068,9 +2098,6 @@ constexpr int TILE_OWN = TILE_W / TILE_ROWS;
 constexpr int HALO_H = TILE_H + 2, HALO_CELLS = (TILE_W + 2) * HALO_H;    // 34 x 66 = 2244 words, 9 KiB: many workgroups per CU
 constexpr int HALO_PADDED = ((HALO_CELLS + 63) / 64) * 64;
 constexpr int SETUP_THREADS = 256;
-constexpr int64_t TILED_MAX_CELLS = 1 << 24;          // a finite value stays below 7 * 2^24: the additions cannot wrap
-constexpr int64_t TILED_MAX_THREADS = (int64_t)1 << 31;                   // of one launch: F * (W * H + 64) stays within it
-constexpr int MAX_ROUNDS = 65536;
 static_assert(TILE_H == 64 && TILE_OWN * TILE_ROWS == TILE_W && TILE_OWN == 8, "the ownership rule and the 8-bit move masks");
 
 // relaxed accesses of agent scope: the global field and the tile flags, read by one workgroup while another writes
@@ -2081,6 +2108,13 @@ __host__ __device__ inline int tiles_along(int n, int side) { return (n + side -
 
 // The workspace: per field three bitmaps (solid, unknown, blocked; the goal field uses the first and the last, of map 0 alone on
 // a shared grid), then the two flag arrays [F, tiles] each.
+// what the rounds read of a workspace, whatever its layout: the tiles of a field, the blocked bitmap, the two flag arrays
+struct RoundBuffers {
+  int64_t tiles;
+  uint32_t *blocked, *flags0, *flags1;
+};
+template <typename Layout> RoundBuffers round_buffers(const Layout& l, uint32_t* w) { return {l.tiles, w + l.blocked, w + l.flags0, w + l.flags1}; }
+
 struct TiledLayout {
   int64_t bm_words, tiles, solid, unknown, blocked, flags0, flags1, words;
 };
@@ -2404,38 +2438,31 @@ __global__ void __launch_bounds__(PATH_THREADS) soft_frontier_descent_kernel(
                            S_max, sub_goals, n_sub, status, path_cost, target_cell);
 }
 
-// the tiled calls' caps, after every E_ARG
-int tiled_cap_refusal(int64_t F, int32_t W, int32_t H) {
-  if (W > MAX_SIDE || H > MAX_SIDE || (int64_t)W * H > TILED_MAX_CELLS) return LIPMPC_E_UNSUPPORTED;
-  if (F > 0 && F * ((int64_t)W * H + 64) > TILED_MAX_THREADS) return LIPMPC_E_UNSUPPORTED;
-  return LIPMPC_OK;
-}
-
 // what the two tiled field calls add to their refusals: E_ARG, then the caps; a `work` too small for a shape within the caps is
 // E_ARG (beyond them no size is defined)
 int tiled_refusal(int64_t F, int32_t W, int32_t H, const void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume,
                   const int32_t* settled) {
-  if (!work || !settled || max_rounds < 1 || max_rounds > MAX_ROUNDS || (resume != 0 && resume != 1)) return LIPMPC_E_ARG;
+  if (any_null(work, settled) || bad_rounds(max_rounds, resume)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
   return work_bytes < tiled_bytes(F, W, H) ? LIPMPC_E_ARG : LIPMPC_OK;
 }
 
 // the rounds and the settle kernel; with a cost layer (`cost` not null, `cost_stride` bytes from field to field) the weighted rounds
-int tiled_rounds(hipStream_t s, int64_t F, int W, int H, int64_t blk_stride, const TiledLayout& l, uint32_t* work, uint32_t* field,
-                 int max_rounds, int32_t* settled, const uint8_t* cost = nullptr, int64_t cost_stride = 0) {
-  const int tiles = (int)l.tiles, tiles_j = tiles_along(H, TILE_H);
+int tiled_rounds(hipStream_t s, int64_t F, int W, int H, int64_t blk_stride, const RoundBuffers& b, uint32_t* field, int max_rounds,
+                 int32_t* settled, const uint8_t* cost = nullptr, int64_t cost_stride = 0) {
+  const int tiles = (int)b.tiles, tiles_j = tiles_along(H, TILE_H);
   const dim3 grid((unsigned)(F * tiles)), block(TILE_THREADS);
-  uint32_t* flags[2] = {work + l.flags0, work + l.flags1};
+  uint32_t* flags[2] = {b.flags0, b.flags1};
   for (int r = 0; r < max_rounds; ++r) {
     if (cost)
-      hipLaunchKernelGGL(soft_round_kernel, grid, block, 0, s, W, H, tiles_j, tiles, blk_stride, work + l.blocked, cost_stride, cost, field,
+      hipLaunchKernelGGL(soft_round_kernel, grid, block, 0, s, W, H, tiles_j, tiles, blk_stride, b.blocked, cost_stride, cost, field,
                          flags[r & 1], flags[(r + 1) & 1]);
     else
-      hipLaunchKernelGGL(tiled_round_kernel, grid, block, 0, s, W, H, tiles_j, tiles, blk_stride, work + l.blocked, field, flags[r & 1],
+      hipLaunchKernelGGL(tiled_round_kernel, grid, block, 0, s, W, H, tiles_j, tiles, blk_stride, b.blocked, field, flags[r & 1],
                          flags[(r + 1) & 1]);
   }
   hipLaunchKernelGGL(tiled_settle_kernel, dim3((unsigned)F), dim3(SETUP_THREADS), 0, s, tiles, max_rounds & 1, flags[0], flags[1], settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 // what a tiled field call derives from its shape: the workspace's layout, the set-up launches' blocks per map (a wave per 64 cells
@@ -2447,14 +2474,8 @@ struct TiledCall {
   uint32_t* w;
 };
 TiledCall tiled_call(int64_t F, int W, int H, bool shared, void* work) {
-  TiledCall t;
-  t.l = tiled_layout(F, W, H);
-  t.ncells = W * H;
-  t.chunks = ((int)(t.l.bm_words - 2) * 32 + SETUP_THREADS - 1) / SETUP_THREADS;
-  t.maps = shared ? 1 : F;
-  t.blk_stride = shared ? 0 : t.l.bm_words;
-  t.w = (uint32_t*)work;
-  return t;
+  const TiledLayout l = tiled_layout(F, W, H);
+  return {l, W * H, ((int)(l.bm_words - 2) * 32 + SETUP_THREADS - 1) / SETUP_THREADS, shared ? 1 : F, shared ? 0 : l.bm_words, (uint32_t*)work};
 }
 
 // the first two set-up launches of the frontier kind (the frontier and the utility field): the bitmaps of the evidence, `counter`
@@ -2473,9 +2494,9 @@ int goal_field(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared,
                const uint8_t* occ, bool weighted, const uint8_t* cost, const double* goal, int32_t r_inflate, uint32_t* field,
                int32_t* field_status, void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume, int32_t* settled,
                void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell))
+  // (the pointers EARLY, unlike lipmpc_grid_field_batch)
+  if (bad_count(F) || bad_placed_grid(W, H, origin, cell, r_inflate) || any_null(occ, goal, field, field_status) || (weighted && !cost))
     return LIPMPC_E_ARG;
-  if (!occ || (weighted && !cost) || !goal || !field || !field_status) return LIPMPC_E_ARG;
   if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
   if (F == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
@@ -2491,7 +2512,7 @@ int goal_field(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared,
     hipLaunchKernelGGL(tiled_goal_seed_kernel, dim3((unsigned)(F * t.chunks)), block, 0, s, W, H, t.chunks, t.blk_stride, origin[0],
                        origin[1], cell[0], cell[1], goal, t.w + l.blocked, field, field_status, t.w + l.flags0, l.tiles);
   }
-  return tiled_rounds(s, F, W, H, t.blk_stride, l, t.w, field, max_rounds, settled, weighted ? cost : nullptr,
+  return tiled_rounds(s, F, W, H, t.blk_stride, round_buffers(l, t.w), field, max_rounds, settled, weighted ? cost : nullptr,
                       grid_shared ? (int64_t)0 : (int64_t)t.ncells);
 }
 
@@ -2499,9 +2520,8 @@ int goal_field(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared,
 int frontier_field(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, bool weighted, const uint8_t* cost, int32_t t_free,
                    int32_t t_occ, int32_t r_inflate, int32_t min_unknown, uint8_t* frontier, uint32_t* field, int32_t* n_frontier,
                    void* work, int64_t work_bytes, int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
-      r_inflate < 0 || r_inflate > R_INFLATE_MAX || min_unknown < 1 || min_unknown > 8 || !evidence || (weighted && !cost) || !field ||
-      !n_frontier)
+  if (bad_count(F) || bad_grid(W, H, r_inflate) || bad_threshold(t_free) || bad_threshold(t_occ) || bad_min_unknown(min_unknown) ||
+      any_null(evidence, field, n_frontier) || (weighted && !cost))       // (`frontier` may be null)
     return LIPMPC_E_ARG;
   if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
   if (F == 0) return LIPMPC_OK;
@@ -2514,7 +2534,7 @@ int frontier_field(int device, int64_t F, int32_t W, int32_t H, const int32_t* e
     hipLaunchKernelGGL(tiled_frontier_seed_kernel, dim3((unsigned)(F * t.chunks)), dim3(SETUP_THREADS), 0, s, W, H, t.chunks, min_unknown,
                        t.w + l.unknown, t.w + l.blocked, frontier, field, n_frontier, t.w + l.flags0, l.tiles);
   }
-  return tiled_rounds(s, F, W, H, t.blk_stride, l, t.w, field, max_rounds, settled, weighted ? cost : nullptr, t.ncells);
+  return tiled_rounds(s, F, W, H, t.blk_stride, round_buffers(l, t.w), field, max_rounds, settled, weighted ? cost : nullptr, t.ncells);
 }
 
 }  // namespace
@@ -2528,7 +2548,7 @@ extern "C" int lipmpc_grid_tiled_info(int32_t* tile_w, int32_t* tile_h, int64_t*
 }
 
 extern "C" int64_t lipmpc_grid_tiled_workspace_bytes(int64_t F, int32_t W, int32_t H) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2) return LIPMPC_E_ARG;
+  if (bad_count(F) || bad_shape(W, H)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
   return tiled_bytes(F, W, H);
 }
@@ -2554,17 +2574,15 @@ extern "C" int lipmpc_grid_path_tiled_batch(int device, int64_t B, int64_t F, in
                                             const int32_t* settled, const double* goal, const double* start, int32_t r_inflate,
                                             int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub, int32_t* status,
                                             double* path_cost, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!occ || !field || !field_status || !settled || !goal || !start || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
+  // LATE: B == 0 passes with any of them null
+  if (any_null(occ, field, field_status, settled, goal, start, sub_goals, n_sub, status, path_cost)) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(tiled_goal_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1],
-                     cell[0], cell[1], occ, field, field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
-                     path_cost);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(tiled_goal_descent_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
+                     grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1], cell[0], cell[1], occ, field, field_status, settled,
+                     goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -2572,17 +2590,16 @@ extern "C" int lipmpc_grid_frontier_path_tiled_batch(int device, int64_t B, int6
                                                      const int32_t* n_frontier, const int32_t* settled, const double* start,
                                                      int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                                      int32_t* status, double* path_cost, int32_t* target_cell, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (bad_threshold(t_occ)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!evidence || !field || !n_frontier || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell)
-    return LIPMPC_E_ARG;
+  // LATE: B == 0 passes with any of them null
+  if (any_null(evidence, field, n_frontier, settled, start, sub_goals, n_sub, status, path_cost, target_cell)) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(tiled_frontier_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, field,
-                     n_frontier, settled, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(tiled_frontier_descent_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
+                     origin[0], origin[1], cell[0], cell[1], evidence, t_occ, field, n_frontier, settled, start, r_inflate, max_seg, S_max,
+                     sub_goals, n_sub, status, path_cost, target_cell);
+  return launched();
 }
 
 // =====================================================================================================================
@@ -2779,7 +2796,6 @@ constexpr int CLAIM_CTL = 8;                          // words 0, 1: the key (64
 constexpr int CTL_TARGET = 2, CTL_STOPPED = 3, CTL_CLAIMS = 4, CTL_UNSETTLED = 5, CTL_ROUND_SETTLED = 6, CTL_ANY_SOURCE = 7;
 constexpr int KEEP_CTL = 16;
 constexpr int CTL_MODE = 8, CTL_ROBOT = 9, CTL_ANCHOR = 10, CTL_CURSOR = 11, CTL_KEPT = 12;      // MODE: 1 = a keep slot, 0 = a greedy round
-constexpr int64_t CLAIM_MAX_LAUNCHES = 1 << 20;       // max_claims * max_rounds of one call
 
 struct ClaimLayout {
   int64_t bm_words, tiles, blocked, sources, flags0, flags1, field, words;
@@ -3407,15 +3423,15 @@ __global__ void __launch_bounds__(FIELD_THREADS) keep_utility_take_kernel(
 }  // namespace
 
 extern "C" int64_t lipmpc_grid_frontier_gain_tiled_lds_bytes(int32_t r_view) {
-  if (r_view < 1 || r_view > R_VIEW_MAX) return LIPMPC_E_ARG;
+  if (bad_view(r_view)) return LIPMPC_E_ARG;
   return tile_gain_lds_bytes(r_view);
 }
 
 extern "C" int lipmpc_grid_frontier_gain_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence, int32_t t_free,
                                                      int32_t t_occ, const uint8_t* frontier, int32_t r_view, int32_t* gain,
                                                      void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
-      r_view < 1 || r_view > R_VIEW_MAX || !evidence || !frontier || !gain)
+  if (bad_count(F) || bad_shape(W, H) || bad_threshold(t_free) || bad_threshold(t_occ) || bad_view(r_view) ||
+      any_null(evidence, frontier, gain))
     return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
   if (F == 0) return LIPMPC_OK;
@@ -3423,7 +3439,7 @@ extern "C" int lipmpc_grid_frontier_gain_tiled_batch(int device, int64_t F, int3
   const int tiles_j = tiles_along(H, TILE_H), tiles = tiles_along(W, TILE_W) * tiles_j;
   hipLaunchKernelGGL(tile_gain_kernel, dim3((unsigned)(F * tiles)), dim3(GAIN_THREADS), (size_t)tile_gain_lds_bytes(r_view),
                      (hipStream_t)hip_stream, W, H, tiles_j, tiles, evidence, t_free, t_occ, frontier, r_view, gain);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_utility_field_tiled_batch(int device, int64_t F, int32_t W, int32_t H, const int32_t* evidence,
@@ -3431,9 +3447,8 @@ extern "C" int lipmpc_grid_frontier_utility_field_tiled_batch(int device, int64_
                                                               const int32_t* gain, int32_t w_gain, int32_t g_cap, int32_t min_gain,
                                                               uint32_t* ufield, int32_t* n_sources, void* work, int64_t work_bytes,
                                                               int32_t max_rounds, int32_t resume, int32_t* settled, void* hip_stream) {
-  if (F < 0 || F > 0x7fffffff || W < 2 || H < 2 || t_free < 1 || t_free > THRESHOLD_MAX || t_occ < 1 || t_occ > THRESHOLD_MAX ||
-      r_inflate < 0 || r_inflate > R_INFLATE_MAX || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 ||
-      min_gain > G_CAP_MAX || !evidence || !frontier || !gain || !ufield || !n_sources)
+  if (bad_count(F) || bad_grid(W, H, r_inflate) || bad_threshold(t_free) || bad_threshold(t_occ) || bad_gain(w_gain, g_cap, min_gain) ||
+      any_null(evidence, frontier, gain, ufield, n_sources))
     return LIPMPC_E_ARG;
   if (const int rc = tiled_refusal(F, W, H, work, work_bytes, max_rounds, resume, settled)) return rc;
   if (F == 0) return LIPMPC_OK;
@@ -3446,7 +3461,7 @@ extern "C" int lipmpc_grid_frontier_utility_field_tiled_batch(int device, int64_
     hipLaunchKernelGGL(tile_utility_seed_kernel, dim3((unsigned)(F * t.chunks)), dim3(SETUP_THREADS), 0, s, W, H, t.chunks, t.w + l.blocked,
                        frontier, gain, w_gain, g_cap, min_gain, ufield, n_sources, t.w + l.flags0, l.tiles);
   }
-  return tiled_rounds(s, F, W, H, t.blk_stride, l, t.w, ufield, max_rounds, settled);
+  return tiled_rounds(s, F, W, H, t.blk_stride, round_buffers(l, t.w), ufield, max_rounds, settled);
 }
 
 extern "C" int lipmpc_grid_frontier_utility_path_tiled_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -3457,21 +3472,22 @@ extern "C" int lipmpc_grid_frontier_utility_path_tiled_batch(int device, int64_t
                                                              int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                                              int32_t* status, double* path_cost, int32_t* target_cell,
                                                              int32_t* target_gain, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX || w_gain < 0 ||
-      w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !evidence || !frontier || !gain ||
-      !ufield || !n_sources || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !target_gain)
+  // (the pointers EARLY, unlike the other tiled path calls: B == 0 with a null one is E_ARG)
+  if (bad_threshold(t_occ) || bad_gain(w_gain, g_cap, min_gain) ||
+      any_null(evidence, frontier, gain, ufield, n_sources, settled, start, sub_goals, n_sub, status, path_cost, target_cell, target_gain))
     return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(tile_utility_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier,
-                     gain, ufield, n_sources, settled, w_gain, g_cap, min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
-                     path_cost, target_cell, target_gain);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(tile_utility_descent_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
+                     origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier, gain, ufield, n_sources, settled, w_gain, g_cap,
+                     min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, target_gain);
+  return launched();
 }
 
+// THREE SEQUENCES, each read top to bottom as set-up, robots, per slot (mode,) seed, rounds, pick, take, and finish: claim_tiled (plain
+// and keep) and the two gain-seeded forms, whose set-up, seed and take kernels take the gain's arguments as well -- one sequence for
+// all four would choose among four argument lists at three of its launches.  They share their refusals and the ClaimCall.
 namespace {
 
 // what the keep call adds to the claim call's arguments
@@ -3482,6 +3498,41 @@ struct KeepArgs {
   int32_t* n_kept;
 };
 
+// what the claim calls refuse behind their E_ARG scalars and pointers: the placed grid (E_ARG), the caps for one field, then a
+// `work` too small for a shape within the caps (E_ARG: beyond them no size is defined)
+int claim_shape_refusal(int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate, int64_t work_bytes, int ctl_words) {
+  if (bad_placed_grid(W, H, origin, cell, r_inflate)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  return work_bytes < claim_bytes(W, H, ctl_words) ? LIPMPC_E_ARG : LIPMPC_OK;
+}
+
+// the four workspace sizes
+int64_t claim_workspace_bytes(int32_t W, int32_t H, int ctl_words) {
+  if (bad_shape(W, H)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
+  return claim_bytes(W, H, ctl_words);
+}
+
+// what a tiled claim call derives from its shape: the workspace's layout, the set-up launch's blocks (a wave per 64 cells of the
+// padded map), the tiles, the grids of its launches, the placement and what the rounds read
+struct ClaimCall {
+  ClaimLayout c;
+  int ncells, chunks, tiles, tiles_j;
+  dim3 cells, robots, setup, tile_grid, tile_block, one, group;
+  double ox, oy, dx, dy;
+  uint32_t* w;
+  RoundBuffers rounds;
+  int32_t* round_settled;
+};
+ClaimCall claim_call(int64_t B, int W, int H, int ctl_words, const double* origin, const double* cell, void* work) {
+  const ClaimLayout c = claim_layout(W, H, ctl_words);
+  const int chunks = ((int)(c.bm_words - 2) * 32 + SETUP_THREADS - 1) / SETUP_THREADS, tiles = (int)c.tiles;
+  uint32_t* w = (uint32_t*)work;
+  return {c, W * H, chunks, tiles, tiles_along(H, TILE_H), dim3((unsigned)chunks), dim3((unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS)),
+          dim3(SETUP_THREADS), dim3((unsigned)tiles), dim3(TILE_THREADS), dim3(1), dim3(FIELD_THREADS), origin[0], origin[1], cell[0], cell[1],
+          w, round_buffers(c, w), (int32_t*)(w + CTL_ROUND_SETTLED)};
+}
+
 // lipmpc_grid_frontier_assign_tiled_batch and, `keep` not null, lipmpc_grid_frontier_assign_keep_tiled_batch.  3 launches round
 // the slots, and per slot (the mode,) the seed, max_rounds rounds and their settle, the pick and the take:
 // max_claims * (max_rounds + 4) + 3, with the mode max_claims * (max_rounds + 5) + 3
@@ -3490,65 +3541,52 @@ int claim_tiled(int device, int64_t B, int32_t W, int32_t H, const double* origi
                 int32_t r_claim, int32_t max_claims, int32_t max_seg, int32_t S_max, void* work, int64_t work_bytes, int32_t max_rounds,
                 double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, int32_t* target_cell, int32_t* claim_round,
                 int32_t* n_claims, int32_t* claims_settled, const KeepArgs* keep, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
-      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS ||
-      (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, settled, start, work, sub_goals, n_sub, status, path_cost,
+                target_cell, claim_round, n_claims, claims_settled) ||
+      bad_claim_rounds(work, max_rounds) || too_many_launches(max_claims, max_rounds) ||
+      (keep && (bad_keep(keep->r_keep, keep->keep_ratio16, keep->keep_slack) || any_null(keep->prev_target, keep->kept, keep->n_kept))))
     return LIPMPC_E_ARG;
-  if (keep && (keep->r_keep < 0 || keep->r_keep > R_KEEP_MAX || keep->keep_ratio16 < KEEP_RATIO_MIN || keep->keep_ratio16 > KEEP_RATIO_MAX ||
-               keep->keep_slack < 0 || keep->keep_slack > KEEP_SLACK_MAX || !keep->prev_target || !keep->kept || !keep->n_kept))
-    return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
   const int ctl_words = keep ? KEEP_CTL : CLAIM_CTL;
-  if (work_bytes < claim_bytes(W, H, ctl_words)) return LIPMPC_E_ARG;
+  if (const int rc = claim_shape_refusal(W, H, origin, cell, r_inflate, work_bytes, ctl_words)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
-  const ClaimLayout c = claim_layout(W, H, ctl_words);
-  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
-  const dim3 robots((unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS)), setup(SETUP_THREADS), one(1), group(FIELD_THREADS);
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  uint32_t* w = (uint32_t*)work;
-  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
-  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
-  hipLaunchKernelGGL(claim_setup_kernel, dim3((unsigned)chunks), setup, 0, s, ncells, c.tiles, max_claims, frontier, field, settled, w,
-                     w + c.blocked, w + c.sources, w + c.flags0);
+  const ClaimCall q = claim_call(B, W, H, ctl_words, origin, cell, work);
+  const ClaimLayout& c = q.c;
+  uint32_t* w = q.w;
+  hipLaunchKernelGGL(claim_setup_kernel, q.cells, q.setup, 0, s, q.ncells, c.tiles, max_claims, frontier, field, settled, w, w + c.blocked,
+                     w + c.sources, w + c.flags0);
   if (keep)
-    hipLaunchKernelGGL(keep_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round,
-                       keep->kept, w);
+    hipLaunchKernelGGL(keep_robots_kernel, q.robots, q.setup, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, start, may_claim, max_claims, status,
+                       claim_round, keep->kept, w);
   else
-    hipLaunchKernelGGL(claim_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round);
+    hipLaunchKernelGGL(claim_robots_kernel, q.robots, q.setup, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, start, may_claim, max_claims, status,
+                       claim_round);
   for (int slot = 0; slot < max_claims; ++slot) {
     if (keep)
-      hipLaunchKernelGGL(keep_mode_kernel, one, group, 0, s, B, W, H, keep->r_keep, w, w + c.sources, claim_round, keep->prev_target);
-    hipLaunchKernelGGL(keep ? keep_seed_kernel : claim_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w,
-                       w + c.sources, w + c.field, w + c.flags0, w + c.flags1);
-    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
-    hipLaunchKernelGGL(keep ? keep_pick_kernel : claim_pick_kernel, robots, setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+      hipLaunchKernelGGL(keep_mode_kernel, q.one, q.group, 0, s, B, W, H, keep->r_keep, w, w + c.sources, claim_round, keep->prev_target);
+    hipLaunchKernelGGL(keep ? keep_seed_kernel : claim_seed_kernel, q.tile_grid, q.tile_block, 0, s, W, H, q.tiles_j, w, w + c.sources,
+                       w + c.field, w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, q.rounds, w + c.field, max_rounds, q.round_settled)) return rc;
+    hipLaunchKernelGGL(keep ? keep_pick_kernel : claim_pick_kernel, q.robots, q.setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
     if (keep)
-      hipLaunchKernelGGL(keep_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, keep->keep_ratio16,
-                         keep->keep_slack, max_seg, S_max, tiles, w, w + c.sources, w + c.field, field, w + c.flags0, sub_goals, n_sub,
+      hipLaunchKernelGGL(keep_take_kernel, q.one, q.group, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, r_inflate, r_claim, keep->keep_ratio16,
+                         keep->keep_slack, max_seg, S_max, q.tiles, w, w + c.sources, w + c.field, field, w + c.flags0, sub_goals, n_sub,
                          status, path_cost, target_cell, claim_round, keep->kept);
     else
-      hipLaunchKernelGGL(claim_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, max_seg, S_max, slot, tiles, w,
-                         w + c.sources, w + c.field, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell, claim_round);
+      hipLaunchKernelGGL(claim_take_kernel, q.one, q.group, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, r_inflate, r_claim, max_seg, S_max, slot,
+                         q.tiles, w, w + c.sources, w + c.field, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell, claim_round);
   }
   if (keep)
-    hipLaunchKernelGGL(keep_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, keep->n_kept, claims_settled);
+    hipLaunchKernelGGL(keep_finish_kernel, q.robots, q.setup, 0, s, B, w, claim_round, n_claims, keep->n_kept, claims_settled);
   else
-    hipLaunchKernelGGL(claim_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, claims_settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+    hipLaunchKernelGGL(claim_finish_kernel, q.robots, q.setup, 0, s, B, w, claim_round, n_claims, claims_settled);
+  return launched();
 }
 
 }  // namespace
 
-extern "C" int64_t lipmpc_grid_frontier_assign_tiled_workspace_bytes(int32_t W, int32_t H) {
-  if (W < 2 || H < 2) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  return claim_bytes(W, H, CLAIM_CTL);
-}
+extern "C" int64_t lipmpc_grid_frontier_assign_tiled_workspace_bytes(int32_t W, int32_t H) { return claim_workspace_bytes(W, H, CLAIM_CTL); }
 
 extern "C" int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin, const double* cell,
                                                        const uint8_t* frontier, const uint32_t* field, const int32_t* settled,
@@ -3562,11 +3600,7 @@ extern "C" int lipmpc_grid_frontier_assign_tiled_batch(int device, int64_t B, in
                      claims_settled, nullptr, hip_stream);
 }
 
-extern "C" int64_t lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes(int32_t W, int32_t H) {
-  if (W < 2 || H < 2) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  return claim_bytes(W, H, KEEP_CTL);
-}
+extern "C" int64_t lipmpc_grid_frontier_assign_keep_tiled_workspace_bytes(int32_t W, int32_t H) { return claim_workspace_bytes(W, H, KEEP_CTL); }
 
 extern "C" int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t B, int32_t W, int32_t H, const double* origin,
                                                             const double* cell, const uint8_t* frontier, const uint32_t* field,
@@ -3585,9 +3619,7 @@ extern "C" int lipmpc_grid_frontier_assign_keep_tiled_batch(int device, int64_t 
 }
 
 extern "C" int64_t lipmpc_grid_frontier_assign_utility_tiled_workspace_bytes(int32_t W, int32_t H) {
-  if (W < 2 || H < 2) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  return claim_bytes(W, H, CLAIM_CTL);
+  return claim_workspace_bytes(W, H, CLAIM_CTL);
 }
 
 // claim_tiled's sequence without the keep forms: 3 launches round the rounds, and per round the seed, max_rounds rounds and their
@@ -3601,46 +3633,36 @@ extern "C" int lipmpc_grid_frontier_assign_utility_tiled_batch(int device, int64
                                                                int32_t* target_cell, int32_t* claim_round, int32_t* n_claims,
                                                                int32_t* claims_settled, const int32_t* gain, int32_t w_gain,
                                                                int32_t g_cap, int32_t min_gain, int32_t* target_gain, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
-      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS ||
-      (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX ||
-      min_gain < 0 || min_gain > G_CAP_MAX || !gain || !target_gain)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, settled, start, work, sub_goals, n_sub, status, path_cost,
+                target_cell, claim_round, n_claims, claims_settled, gain, target_gain) ||
+      bad_claim_rounds(work, max_rounds) || too_many_launches(max_claims, max_rounds) || bad_gain(w_gain, g_cap, min_gain))
     return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  if (work_bytes < claim_bytes(W, H, CLAIM_CTL)) return LIPMPC_E_ARG;
+  if (const int rc = claim_shape_refusal(W, H, origin, cell, r_inflate, work_bytes, CLAIM_CTL)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
-  const ClaimLayout c = claim_layout(W, H, CLAIM_CTL);
-  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
-  const dim3 robots((unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS)), setup(SETUP_THREADS), one(1), group(FIELD_THREADS);
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  uint32_t* w = (uint32_t*)work;
-  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
-  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
-  hipLaunchKernelGGL(utility_assign_setup_kernel, dim3((unsigned)chunks), setup, 0, s, ncells, c.tiles, max_claims, frontier, field, gain, min_gain,
+  const ClaimCall q = claim_call(B, W, H, CLAIM_CTL, origin, cell, work);
+  const ClaimLayout& c = q.c;
+  uint32_t* w = q.w;
+  hipLaunchKernelGGL(utility_assign_setup_kernel, q.cells, q.setup, 0, s, q.ncells, c.tiles, max_claims, frontier, field, gain, min_gain,
                      settled, w, w + c.blocked, w + c.sources, w + c.flags0);
-  hipLaunchKernelGGL(claim_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round);
+  hipLaunchKernelGGL(claim_robots_kernel, q.robots, q.setup, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, start, may_claim, max_claims, status,
+                     claim_round);
   for (int k = 0; k < max_claims; ++k) {
-    hipLaunchKernelGGL(utility_assign_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, gain, w_gain,
-                       g_cap, w + c.field, w + c.flags0, w + c.flags1);
-    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
-    hipLaunchKernelGGL(claim_pick_kernel, robots, setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
-    hipLaunchKernelGGL(utility_assign_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, max_seg, S_max, k, tiles, w,
-                       w + c.sources, w + c.field, gain, w_gain, g_cap, w + c.flags0, sub_goals, n_sub, status, path_cost, target_cell,
-                       target_gain, claim_round);
+    hipLaunchKernelGGL(utility_assign_seed_kernel, q.tile_grid, q.tile_block, 0, s, W, H, q.tiles_j, w, w + c.sources, gain, w_gain, g_cap,
+                       w + c.field, w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, q.rounds, w + c.field, max_rounds, q.round_settled)) return rc;
+    hipLaunchKernelGGL(claim_pick_kernel, q.robots, q.setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+    hipLaunchKernelGGL(utility_assign_take_kernel, q.one, q.group, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, r_inflate, r_claim, max_seg, S_max,
+                       k, q.tiles, w, w + c.sources, w + c.field, gain, w_gain, g_cap, w + c.flags0, sub_goals, n_sub, status, path_cost,
+                       target_cell, target_gain, claim_round);
   }
-  hipLaunchKernelGGL(claim_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, claims_settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(claim_finish_kernel, q.robots, q.setup, 0, s, B, w, claim_round, n_claims, claims_settled);
+  return launched();
 }
 
 extern "C" int64_t lipmpc_grid_frontier_assign_keep_utility_tiled_workspace_bytes(int32_t W, int32_t H) {
-  if (W < 2 || H < 2) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  return claim_bytes(W, H, KEEP_CTL);
+  return claim_workspace_bytes(W, H, KEEP_CTL);
 }
 
 // claim_tiled's sequence with the keep forms: 3 launches round the slots, and per slot the mode, the seed, max_rounds rounds and
@@ -3653,47 +3675,34 @@ extern "C" int lipmpc_grid_frontier_assign_keep_utility_tiled_batch(
     int32_t* claim_round, int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled, const int32_t* gain,
     const uint32_t* ufield, const int32_t* usettled, int32_t w_gain, int32_t g_cap, int32_t min_gain, int32_t* target_gain,
     void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
-      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS ||
-      (int64_t)max_claims * max_rounds > CLAIM_MAX_LAUNCHES)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, settled, start, prev_target, work, sub_goals, n_sub, status,
+                path_cost, target_cell, claim_round, n_claims, kept, n_kept, claims_settled, gain, ufield, usettled, target_gain) ||
+      bad_claim_rounds(work, max_rounds) || too_many_launches(max_claims, max_rounds) || bad_keep(r_keep, keep_ratio16, keep_slack) ||
+      bad_gain(w_gain, g_cap, min_gain))
     return LIPMPC_E_ARG;
-  if (r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
-      keep_slack > KEEP_SLACK_MAX || !prev_target || !kept || !n_kept)
-    return LIPMPC_E_ARG;
-  if (w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 || min_gain > G_CAP_MAX || !gain || !ufield ||
-      !usettled || !target_gain)
-    return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(1, W, H)) return rc;
-  if (work_bytes < claim_bytes(W, H, KEEP_CTL)) return LIPMPC_E_ARG;
+  if (const int rc = claim_shape_refusal(W, H, origin, cell, r_inflate, work_bytes, KEEP_CTL)) return rc;
   if (B == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
-  const ClaimLayout c = claim_layout(W, H, KEEP_CTL);
-  const int ncells = W * H, padded = (int)(c.bm_words - 2) * 32, chunks = (padded + SETUP_THREADS - 1) / SETUP_THREADS;
-  const int tiles = (int)c.tiles, tiles_j = tiles_along(H, TILE_H);
-  const dim3 robots((unsigned)((B + SETUP_THREADS - 1) / SETUP_THREADS)), setup(SETUP_THREADS), one(1), group(FIELD_THREADS);
-  const double ox = origin[0], oy = origin[1], dx = cell[0], dy = cell[1];
-  uint32_t* w = (uint32_t*)work;
-  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
-  l.bm_words = c.bm_words; l.tiles = c.tiles; l.blocked = c.blocked; l.flags0 = c.flags0; l.flags1 = c.flags1;
-  hipLaunchKernelGGL(keep_utility_setup_kernel, dim3((unsigned)chunks), setup, 0, s, ncells, c.tiles, max_claims, frontier, field, gain,
-                     min_gain, settled, usettled, w, w + c.blocked, w + c.sources, w + c.flags0);
-  hipLaunchKernelGGL(keep_robots_kernel, robots, setup, 0, s, B, W, H, ox, oy, dx, dy, start, may_claim, max_claims, status, claim_round,
-                     kept, w);
+  const ClaimCall q = claim_call(B, W, H, KEEP_CTL, origin, cell, work);
+  const ClaimLayout& c = q.c;
+  uint32_t* w = q.w;
+  hipLaunchKernelGGL(keep_utility_setup_kernel, q.cells, q.setup, 0, s, q.ncells, c.tiles, max_claims, frontier, field, gain, min_gain, settled,
+                     usettled, w, w + c.blocked, w + c.sources, w + c.flags0);
+  hipLaunchKernelGGL(keep_robots_kernel, q.robots, q.setup, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, start, may_claim, max_claims, status,
+                     claim_round, kept, w);
   for (int slot = 0; slot < max_claims; ++slot) {
-    hipLaunchKernelGGL(keep_mode_kernel, one, group, 0, s, B, W, H, r_keep, w, w + c.sources, claim_round, prev_target);
-    hipLaunchKernelGGL(keep_utility_seed_kernel, dim3((unsigned)tiles), dim3(TILE_THREADS), 0, s, W, H, tiles_j, w, w + c.sources, gain,
-                       w_gain, g_cap, w + c.field, w + c.flags0, w + c.flags1);
-    if (const int rc = tiled_rounds(s, 1, W, H, 0, l, w, w + c.field, max_rounds, (int32_t*)(w + CTL_ROUND_SETTLED))) return rc;
-    hipLaunchKernelGGL(keep_pick_kernel, robots, setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
-    hipLaunchKernelGGL(keep_utility_take_kernel, one, group, 0, s, B, W, H, ox, oy, dx, dy, r_inflate, r_claim, keep_ratio16, keep_slack,
-                       max_seg, S_max, tiles, w, w + c.sources, w + c.field, ufield, gain, w_gain, g_cap, w + c.flags0, sub_goals, n_sub,
-                       status, path_cost, target_cell, target_gain, claim_round, kept);
+    hipLaunchKernelGGL(keep_mode_kernel, q.one, q.group, 0, s, B, W, H, r_keep, w, w + c.sources, claim_round, prev_target);
+    hipLaunchKernelGGL(keep_utility_seed_kernel, q.tile_grid, q.tile_block, 0, s, W, H, q.tiles_j, w, w + c.sources, gain, w_gain, g_cap,
+                       w + c.field, w + c.flags0, w + c.flags1);
+    if (const int rc = tiled_rounds(s, 1, W, H, 0, q.rounds, w + c.field, max_rounds, q.round_settled)) return rc;
+    hipLaunchKernelGGL(keep_pick_kernel, q.robots, q.setup, 0, s, B, W, H, r_inflate, w, w + c.field, claim_round);
+    hipLaunchKernelGGL(keep_utility_take_kernel, q.one, q.group, 0, s, B, W, H, q.ox, q.oy, q.dx, q.dy, r_inflate, r_claim, keep_ratio16,
+                       keep_slack, max_seg, S_max, q.tiles, w, w + c.sources, w + c.field, ufield, gain, w_gain, g_cap, w + c.flags0, sub_goals,
+                       n_sub, status, path_cost, target_cell, target_gain, claim_round, kept);
   }
-  hipLaunchKernelGGL(keep_finish_kernel, robots, setup, 0, s, B, w, claim_round, n_claims, n_kept, claims_settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(keep_finish_kernel, q.robots, q.setup, 0, s, B, w, claim_round, n_claims, n_kept, claims_settled);
+  return launched();
 }
 
 // =====================================================================================================================
@@ -3836,21 +3845,17 @@ __device__ inline int soft_walk(const uint32_t* __restrict__ fld, const uint8_t*
 
 extern "C" int lipmpc_grid_clearance_cost_batch(int device, int64_t M, int32_t W, int32_t H, const uint8_t* occ, const int32_t* evidence,
                                                 int32_t t_occ, int32_t r_clear, int32_t w_clear, uint8_t* cost, void* hip_stream) {
-  if (M < 0 || M > 0x7fffffff || W < 2 || H < 2 || r_clear < 1 || r_clear > R_CLEAR_MAX || w_clear < 0 || w_clear > LIPMPC_COST_MAX)
-    return LIPMPC_E_ARG;
-  if ((occ != nullptr) == (evidence != nullptr) || !cost || (evidence && (t_occ < 1 || t_occ > THRESHOLD_MAX))) return LIPMPC_E_ARG;
+  if (bad_count(M) || bad_shape(W, H) || r_clear < 1 || r_clear > R_CLEAR_MAX || w_clear < 0 || w_clear > LIPMPC_COST_MAX) return LIPMPC_E_ARG;
+  // (the map is occ or evidence, never both; t_occ is read with evidence alone)
+  if ((occ != nullptr) == (evidence != nullptr) || !cost || (evidence && bad_threshold(t_occ))) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(M, W, H)) return rc;
   if (M == 0) return LIPMPC_OK;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   const int tiles_j = tiles_along(H, TILE_H), tiles = tiles_along(W, TILE_W) * tiles_j;
   const dim3 grid((unsigned)(M * tiles)), block(TILE_THREADS);
-  if (occ)
-    hipLaunchKernelGGL(soft_cost_kernel<0>, grid, block, 0, (hipStream_t)hip_stream, W, H, tiles_j, tiles, occ, evidence, t_occ, r_clear,
-                       w_clear, cost);
-  else
-    hipLaunchKernelGGL(soft_cost_kernel<1>, grid, block, 0, (hipStream_t)hip_stream, W, H, tiles_j, tiles, occ, evidence, t_occ, r_clear,
-                       w_clear, cost);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(occ ? soft_cost_kernel<0> : soft_cost_kernel<1>, grid, block, 0, (hipStream_t)hip_stream, W, H, tiles_j, tiles, occ,
+                     evidence, t_occ, r_clear, w_clear, cost);
+  return launched();
 }
 
 extern "C" int lipmpc_grid_field_weighted_batch(int device, int64_t F, int32_t W, int32_t H, int32_t grid_shared, const double* origin,
@@ -3875,17 +3880,15 @@ extern "C" int lipmpc_grid_path_weighted_batch(int device, int64_t B, int64_t F,
                                                const uint32_t* field, const int32_t* field_status, const int32_t* settled,
                                                const double* goal, const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
                                                double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!occ || !cost || !field || !field_status || !settled || !goal || !start || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
+  // LATE: B == 0 passes with any of them null
+  if (any_null(occ, cost, field, field_status, settled, goal, start, sub_goals, n_sub, status, path_cost)) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(soft_goal_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1],
-                     cell[0], cell[1], occ, cost, field, field_status, settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status,
-                     path_cost);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(soft_goal_descent_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
+                     grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1], cell[0], cell[1], occ, cost, field, field_status,
+                     settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_path_weighted_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -3894,17 +3897,16 @@ extern "C" int lipmpc_grid_frontier_path_weighted_batch(int device, int64_t B, i
                                                         const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
                                                         double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                                         int32_t* target_cell, void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1 || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  if (const int rc = tiled_cap_refusal(F, W, H)) return rc;
+  if (bad_threshold(t_occ)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!evidence || !cost || !field || !n_frontier || !settled || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell)
-    return LIPMPC_E_ARG;
+  // LATE: B == 0 passes with any of them null
+  if (any_null(evidence, cost, field, n_frontier, settled, start, sub_goals, n_sub, status, path_cost, target_cell)) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
-  hipLaunchKernelGGL(soft_frontier_descent_kernel, dim3((unsigned)((B + PATH_THREADS - 1) / PATH_THREADS)), dim3(PATH_THREADS), 0,
-                     (hipStream_t)hip_stream, B, (int)(F == 1), W, H, origin[0], origin[1], cell[0], cell[1], evidence, cost, t_occ, field,
-                     n_frontier, settled, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  hipLaunchKernelGGL(soft_frontier_descent_kernel, path_grid(B), dim3(PATH_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
+                     origin[0], origin[1], cell[0], cell[1], evidence, cost, t_occ, field, n_frontier, settled, start, r_inflate, max_seg,
+                     S_max, sub_goals, n_sub, status, path_cost, target_cell);
+  return launched();
 }
 
 // =====================================================================================================================

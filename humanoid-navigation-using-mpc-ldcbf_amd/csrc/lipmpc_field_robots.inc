@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(SETUP_THREADS) robot_finish_kernel(int64_t B, 
 }  // namespace
 
 extern "C" int64_t lipmpc_grid_frontier_assign_robot_fields_workspace_bytes(int64_t B, int32_t W, int32_t H) {
-  if (B < 0 || B > 0x7fffffff || W < 2 || H < 2) return LIPMPC_E_ARG;
+  if (bad_count(B) || bad_shape(W, H)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(B, W, H)) return rc;
   return robot_bytes(B, W, H);
 }
@@ -329,14 +329,13 @@ extern "C" int lipmpc_grid_frontier_assign_robot_fields_batch(
     int64_t work_bytes, int32_t max_rounds, int32_t resume, double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
     int32_t* target_cell, int32_t* claim_round, int32_t* n_claims, int8_t* kept, int32_t* n_kept, int32_t* claims_settled,
     void* hip_stream) {
-  if (B < 0 || B > 0x7fffffff || r_claim < 0 || r_claim > MAX_SIDE || max_claims < 0 || max_claims > 4096 || max_seg < 5 || S_max < 1 ||
-      !frontier || !field || !settled || !start || !work || !sub_goals || !n_sub || !status || !path_cost || !target_cell || !claim_round ||
-      !n_claims || !claims_settled || ((uintptr_t)work & 7) != 0 || max_rounds < 1 || max_rounds > MAX_ROUNDS || (resume != 0 && resume != 1))
+  // (the keep words are tested even without a previous target; kept and n_kept are needed with one alone.  The launches do not
+  // grow with max_claims, so max_claims * max_rounds has no limit here, unlike the claim calls by tiles)
+  if (bad_claim(B, r_claim, max_claims, max_seg, S_max, frontier, field, settled, start, work, sub_goals, n_sub, status, path_cost,
+                target_cell, claim_round, n_claims, claims_settled) ||
+      bad_claim_rounds(work, max_rounds, resume) || bad_keep(r_keep, keep_ratio16, keep_slack) ||
+      (prev_target && any_null(kept, n_kept)) || bad_placed_grid(W, H, origin, cell, r_inflate))
     return LIPMPC_E_ARG;
-  if (r_keep < 0 || r_keep > R_KEEP_MAX || keep_ratio16 < KEEP_RATIO_MIN || keep_ratio16 > KEEP_RATIO_MAX || keep_slack < 0 ||
-      keep_slack > KEEP_SLACK_MAX || (prev_target && (!kept || !n_kept)))
-    return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
   if (const int rc = tiled_cap_refusal(B, W, H)) return rc;
   if (work_bytes < robot_bytes(B, W, H)) return LIPMPC_E_ARG;
   if (B == 0) return LIPMPC_OK;
@@ -357,9 +356,7 @@ extern "C" int lipmpc_grid_frontier_assign_robot_fields_batch(
                        status, r_inflate, tiles, wi + r.entry, w + r.flags0);
     hipLaunchKernelGGL(robot_fill_kernel, dim3((unsigned)(B * chunks)), setup, 0, s, ncells, chunks, wi + r.entry, w + r.fields);
   }
-  TiledLayout l = {};                                   // what tiled_rounds reads: the tiles, the blocked bitmap, the two flag arrays
-  l.bm_words = r.bm_words; l.tiles = r.tiles; l.blocked = r.blocked; l.flags0 = r.flags0; l.flags1 = r.flags1;
-  if (const int rc = tiled_rounds(s, B, W, H, 0, l, w, w + r.fields, max_rounds, wi + r.fsettled)) return rc;
+  if (const int rc = tiled_rounds(s, B, W, H, 0, round_buffers(r, w), w + r.fields, max_rounds, wi + r.fsettled)) return rc;
   hipLaunchKernelGGL(robot_all_settled_kernel, one, setup, 0, s, B, settled, wi + r.fsettled, w);
   hipLaunchKernelGGL(robot_claim_kernel, one, dim3(FIELD_THREADS), 0, s, B, W, H, r_claim, r_keep, keep_ratio16, keep_slack, max_claims, w,
                      field, w + r.fields, prev_target, wi + r.entry, w + r.sources, w + r.live, wi + r.in_u, wi + r.target, wi + r.round,
@@ -368,5 +365,5 @@ extern "C" int lipmpc_grid_frontier_assign_robot_fields_batch(
                      w + r.fields, wi + r.target, wi + r.round, wi + r.was_kept, sub_goals, n_sub, status, path_cost, target_cell,
                      claim_round, kept);
   hipLaunchKernelGGL(robot_finish_kernel, robots, setup, 0, s, B, w, wi + r.target, claim_round, kept, n_claims, n_kept, claims_settled);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }

@@ -284,15 +284,6 @@ __global__ void __launch_bounds__(WAVEWALK_THREADS) wavewalk_utility_kernel(
   done(LIPMPC_RRT_FOUND, n, cost, last_cell);
 }
 
-// what the three wave calls refuse about the shape: E_ARG (the grid's placement included), then the tiled caps in every form -- a
-// path call needs no LDS sized to the map
-int wave_refusal(int64_t B, int64_t F, int32_t W, int32_t H, const double* origin, const double* cell, int32_t r_inflate, int32_t max_seg,
-                 int32_t S_max) {
-  if (B < 0 || B > 0x7fffffff || (F != 1 && F != B) || max_seg < 5 || S_max < 1) return LIPMPC_E_ARG;
-  if (W < 2 || H < 2 || r_inflate < 0 || r_inflate > R_INFLATE_MAX || bad_placement(origin, cell)) return LIPMPC_E_ARG;
-  return tiled_cap_refusal(F, W, H);
-}
-
 inline dim3 wave_grid(int64_t B) { return dim3((unsigned)((B + WAVEWALK_ROBOTS - 1) / WAVEWALK_ROBOTS)); }
 
 }  // namespace
@@ -303,14 +294,15 @@ extern "C" int lipmpc_grid_path_wave_batch(int device, int64_t B, int64_t F, int
                                            int32_t r_inflate, int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                            int32_t* status, double* path_cost, void* hip_stream) {
   if (cost && !settled) return LIPMPC_E_ARG;                           // (a weighted field has the word)
-  if (const int rc = wave_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!occ || !field || !field_status || !goal || !start || !sub_goals || !n_sub || !status || !path_cost) return LIPMPC_E_ARG;
+  // LATE, as in the three wave calls: B == 0 passes with any of them null (`settled` may be null, without `cost`)
+  if (any_null(occ, field, field_status, goal, start, sub_goals, n_sub, status, path_cost)) return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(wavewalk_goal_kernel, wave_grid(B), dim3(WAVEWALK_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
                      grid_shared ? (int64_t)0 : (int64_t)W * H, origin[0], origin[1], cell[0], cell[1], occ, cost, field, field_status,
                      settled, goal, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_path_wave_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -319,15 +311,15 @@ extern "C" int lipmpc_grid_frontier_path_wave_batch(int device, int64_t B, int64
                                                     const double* start, int32_t r_inflate, int32_t max_seg, int32_t S_max,
                                                     double* sub_goals, int32_t* n_sub, int32_t* status, double* path_cost,
                                                     int32_t* target_cell, void* hip_stream) {
-  if ((cost && !settled) || t_occ < 1 || t_occ > THRESHOLD_MAX) return LIPMPC_E_ARG;
-  if (const int rc = wave_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
+  if ((cost && !settled) || bad_threshold(t_occ)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!evidence || !field || !n_frontier || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell) return LIPMPC_E_ARG;
+  if (any_null(evidence, field, n_frontier, start, sub_goals, n_sub, status, path_cost, target_cell)) return LIPMPC_E_ARG;       // LATE
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(wavewalk_frontier_kernel, wave_grid(B), dim3(WAVEWALK_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
                      origin[0], origin[1], cell[0], cell[1], evidence, cost, t_occ, field, n_frontier, settled, start, r_inflate, max_seg,
                      S_max, sub_goals, n_sub, status, path_cost, target_cell);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
 
 extern "C" int lipmpc_grid_frontier_utility_path_wave_batch(int device, int64_t B, int64_t F, int32_t W, int32_t H, const double* origin,
@@ -338,17 +330,15 @@ extern "C" int lipmpc_grid_frontier_utility_path_wave_batch(int device, int64_t 
                                                             int32_t max_seg, int32_t S_max, double* sub_goals, int32_t* n_sub,
                                                             int32_t* status, double* path_cost, int32_t* target_cell,
                                                             int32_t* target_gain, void* hip_stream) {
-  if (t_occ < 1 || t_occ > THRESHOLD_MAX || w_gain < 0 || w_gain > W_GAIN_MAX || g_cap < 1 || g_cap > G_CAP_MAX || min_gain < 0 ||
-      min_gain > G_CAP_MAX)
-    return LIPMPC_E_ARG;
-  if (const int rc = wave_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
+  if (bad_threshold(t_occ) || bad_gain(w_gain, g_cap, min_gain)) return LIPMPC_E_ARG;
+  if (const int rc = tiled_path_refusal(B, F, W, H, origin, cell, r_inflate, max_seg, S_max)) return rc;
   if (B == 0) return LIPMPC_OK;
-  if (!evidence || !frontier || !gain || !ufield || !n_sources || !start || !sub_goals || !n_sub || !status || !path_cost || !target_cell ||
-      !target_gain)
+  // LATE, unlike lipmpc_grid_frontier_utility_path_batch and its tiled form (`settled` may be null)
+  if (any_null(evidence, frontier, gain, ufield, n_sources, start, sub_goals, n_sub, status, path_cost, target_cell, target_gain))
     return LIPMPC_E_ARG;
   if (hipSetDevice(device) != hipSuccess) return LIPMPC_E_HIP;
   hipLaunchKernelGGL(wavewalk_utility_kernel, wave_grid(B), dim3(WAVEWALK_THREADS), 0, (hipStream_t)hip_stream, B, (int)(F == 1), W, H,
                      origin[0], origin[1], cell[0], cell[1], evidence, t_occ, frontier, gain, ufield, n_sources, settled, w_gain, g_cap,
                      min_gain, start, r_inflate, max_seg, S_max, sub_goals, n_sub, status, path_cost, target_cell, target_gain);
-  return hipGetLastError() == hipSuccess ? LIPMPC_OK : LIPMPC_E_HIP;
+  return launched();
 }
